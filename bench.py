@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the CGNN neural-receiver forward pass on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,12 +17,17 @@ inputs already resident in HBM.  Multi-GPU: each rank runs its own 128-slot shar
 (independent slots, no collective on the data path -> weak scaling); one RCCL
 all-reduce of the per-rank elapsed time (MAX) after the timed region.
 
-Prints ONE JSON line (rank 0) with the headline metric (slots/s, whole job), the
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the
+outputs of the last timed step (``--dump-outputs DIR``: DIR/llr.npy and DIR/h_hat.npy, float32;
+the inputs are seeded, so two builds can be compared output for output) and print ONE JSON
+line (rank 0) with the headline metric (slots/s, whole job) and ``ms_per_step``.  ``--full`` adds
+every other measurement to that line, each in a run of its own after the timed steps: the
 per-slot p50 latency at batch 1, the roofline of the dominant kernel
 (the one-launch forward k_forward at this shape -- the state-update launch where the
 three-launch path runs -- measured with HIP events on the launch stream) and a CPU baseline
 (the torch-CPU restatement, fp32, BASELINE.md's plan: cfg1 latency and cfg2 throughput at
-all threads and at 1 thread, on a bounded sample on this host).
+all threads and at 1 thread, on a bounded sample on this host) and the end-to-end
+generate + receive + count step.
 """
 from __future__ import annotations
 
@@ -52,9 +57,17 @@ def parse():
     p.add_argument("--prewarm-s", type=float, default=0.3,
                    help="seconds of untimed forwards before the W warmup steps (GPU clock ramp)")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-latency", action="store_true")
-    p.add_argument("--no-e2e", action="store_true", help="skip the generate+receive+count measurement")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure the per-kernel roofline, the batch-1 latencies, "
+                        "the generate+receive+count step and the CPU baseline (a plain run reports the "
+                        "headline and ms_per_step only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step to DIR/llr.npy and DIR/h_hat.npy (float32; "
+                        "a fixed seeded sample of an output over its share of 64 MB)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-latency", action="store_true", help="with --full: skip the batch-1 latencies")
+    p.add_argument("--no-e2e", action="store_true",
+                   help="with --full: skip the generate+receive+count measurement")
     p.add_argument("--graph", action="store_true",
                    help="time replays of a captured hipGraph instead of direct nrx_forward calls")
     p.add_argument("--streams", type=int, default=2,
@@ -88,6 +101,23 @@ def spawn_ranks(n: int) -> int:
     rcs = [p.wait() for p in procs]
     bad = [rc for rc in rcs if rc != 0]
     return bad[0] if bad else 0
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays, rank):
+    """--dump-outputs: {name: device tensor} -> path/<name>.npy (float32; rank r > 0 of a multi-GPU
+    run writes <name>.rank<r>.npy).  An array over its share of DUMP_LIMIT_BYTES is written as a
+    fixed seeded sample of its elements (sorted flat indices, the same from run to run)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(64).integers(0, a.size, share // 4))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ("" if rank == 0 else f".rank{rank}") + ".npy"), a)
 
 
 def selftest(args, world, rank):
@@ -236,17 +266,22 @@ def main():
         st_e = e.fused_status(full=True)
         fused_st = {"error": fused_st["error"] | st_e["error"], "waited": fused_st["waited"] + st_e["waited"],
                     "polls": fused_st["polls"] + st_e["polls"]}
-    # one stream's own clock over a region of the same length (no per-launch markers): the step
-    # time the per-launch event-pair shares below are scaled to, so the per-kernel durations are
-    # those of kernels that do not overlap another batch's
-    with torch.cuda.stream(graph_stream):
-        ev_t0, ev_t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev_t0.record()
-        for _ in range(args.steps):
-            (step if n_streams == 1 else step_eager)()
-        ev_t1.record()
-    torch.cuda.synchronize()
-    stream_step_ms = ev_t0.elapsed_time(ev_t1) / args.steps
+    if args.dump_outputs:
+        # what the last timed step returned (the pipeline's batch i wrote the outputs of engine i % S)
+        last = outs[(pipe_i[0] - 1) % n_streams] if step is step_pipe else out
+        dump_outputs(args.dump_outputs, {"llr": last[0], "h_hat": last[1]}, rank)
+    if args.full or args.profile_only:
+        # one stream's own clock over a region of the same length (no per-launch markers): the step
+        # time the per-launch event-pair shares below are scaled to, so the per-kernel durations are
+        # those of kernels that do not overlap another batch's
+        with torch.cuda.stream(graph_stream):
+            ev_t0, ev_t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev_t0.record()
+            for _ in range(args.steps):
+                (step if n_streams == 1 else step_eager)()
+            ev_t1.record()
+        torch.cuda.synchronize()
+        stream_step_ms = ev_t0.elapsed_time(ev_t1) / args.steps
     if world > 1:
         e = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
@@ -261,11 +296,44 @@ def main():
     slots_total = world * B * args.steps
     value = slots_total / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
+    re_users = B * U * F * 14
+    whole_tflops = metrics.forward_flops_per_re_user(spec, num_it) * re_users * world / (elapsed / args.steps) / 1e12
+    head = {
+        "metric": "5G NR slots/sec + p50 per-slot latency, nrx_rt config",
+        "value": round(value, 1),
+        "unit": "slots/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f16" if args.precision == "f16" else "f32/f64",
+        "data": "synthetic (seeded PUSCH slots: 16-QAM, DMRS type 1, TDL channel, LS+NN h_hat; trained nrx_rt weights)",
+        "config": {"workload": f"{args.config}, {U} users, {args.prbs} PRB, 4 rx_ant, 16-QAM, "
+                               f"batch={B} slots per GPU",
+                   "global_batch": B * world, "num_it": num_it, "parallelism": f"dp{world} (slot shards)",
+                   "launch": "hipGraph replay of nrx_forward" if args.graph else (
+                       "direct nrx_forward calls" if n_streams == 1 else
+                       f"direct nrx_forward calls, consecutive batches alternated over {n_streams} HIP "
+                       f"streams (one engine: handle + workspace + outputs each; every batch a whole forward)"),
+                   "streams": n_streams,
+                   "prewarm_s": args.prewarm_s},
+    }
+    if not args.full:
+        # a plain run ends here: the headline, the step time and the fused-forward error bits
+        if fused_st["error"]:
+            print(f"bench.py: one-launch forward error bits {fused_st['error']}: outputs invalid", file=sys.stderr)
+        if rank == 0:
+            print(json.dumps({**head, "whole_forward_tflops": round(whole_tflops, 2), "full": False}))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline of the dominant kernel: HIP events around each launch, on the
     # launch stream, over a second timed region of the same length
     kflops = metrics.launch_flops_per_re_user(spec, num_it)
-    re_users = B * U * F * 14
     eng.profile(True)
     for _ in range(args.steps):
         step_eager()
@@ -361,7 +429,6 @@ def main():
     if not match:
         traffic = fwd_traffic = pmc_src = None
         sq = {k: v for k, v in sq.items() if k in ("source", "build_id")}
-    whole_tflops = metrics.forward_flops_per_re_user(spec, num_it) * re_users * world / (elapsed / args.steps) / 1e12
     roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
                 "frac": round(achieved / peak, 4), "traffic": traffic,
                 "kernel": kname,
@@ -430,33 +497,14 @@ def main():
 
     if rank == 0:
         line = {
-            "metric": "5G NR slots/sec + p50 per-slot latency, nrx_rt config",
-            "value": round(value, 1),
-            "unit": "slots/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f16" if args.precision == "f16" else "f32/f64",
-            "data": "synthetic (seeded PUSCH slots: 16-QAM, DMRS type 1, TDL channel, LS+NN h_hat; trained nrx_rt weights)",
-            "config": {"workload": f"{args.config}, {U} users, {args.prbs} PRB, 4 rx_ant, 16-QAM, "
-                                   f"batch={B} slots per GPU",
-                       "global_batch": B * world, "num_it": num_it, "parallelism": f"dp{world} (slot shards)",
-                       "launch": "hipGraph replay of nrx_forward" if args.graph else (
-                           "direct nrx_forward calls" if n_streams == 1 else
-                           f"direct nrx_forward calls, consecutive batches alternated over {n_streams} HIP "
-                           f"streams (one engine: handle + workspace + outputs each; every batch a whole forward)"),
-                       "streams": n_streams,
-                       "prewarm_s": args.prewarm_s},
+            **head,
             "roofline": roofline,
             "cpu_baseline": cpu,
             "p50_latency_ms": latency,
             "e2e_generate_receive_count": e2e,
             "whole_forward_tflops": round(whole_tflops, 2),
             "kernels": kern,
+            "full": True,
         }
         print(json.dumps(line))
     if world > 1:

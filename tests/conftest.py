@@ -10,10 +10,3 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (HIP device) and libnrx.so")
-
-
-REF = "/root/reference"
-
-
-def have_reference():
-    return os.path.isdir(REF)

@@ -1,17 +1,18 @@
-"""Config parsing: built-in table vs the reference cfg files; no eval."""
+"""Config parsing: built-in table vs the reference cfg files (stored under tests/golden/config);
+no eval."""
 import dataclasses
 import os
 
 import pytest
 
 from neural_rx_amd.config import BUILTIN, parse_cfg, spec_from_config, mcs_to_bits
-from tests.conftest import have_reference
+
+GOLDEN_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config")
 
 
-@pytest.mark.skipif(not have_reference(), reason="reference cfg files not present")
 @pytest.mark.parametrize("name", sorted(BUILTIN))
 def test_builtin_matches_reference_cfg(name):
-    got = parse_cfg(f"/root/reference/config/{name}.cfg")
+    got = parse_cfg(os.path.join(GOLDEN_CFG, f"{name}.cfg"))
     want = BUILTIN[name]
     diff = {f.name: (getattr(got, f.name), getattr(want, f.name))
             for f in dataclasses.fields(want) if getattr(got, f.name) != getattr(want, f.name)}

@@ -5,17 +5,18 @@ import pickle
 import numpy as np
 import pytest
 
-from tests.conftest import have_reference
-
 import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import convert_weights  # noqa: E402
 
 
-@pytest.mark.skipif(not have_reference(), reason="reference weights not present")
+GOLDEN_WEIGHTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "weights")
+
+
 def test_static_reader_matches_committed_npz():
+    # tests/golden/weights/nrx_rt_weights: the reference's pickled weight list, as distributed
     from neural_rx_amd import weights as W
-    arrs = convert_weights.read_weight_list("/root/reference/weights/nrx_rt_weights")
+    arrs = convert_weights.read_weight_list(os.path.join(GOLDEN_WEIGHTS, "nrx_rt_weights"))
     ref = W.load("nrx_rt")
     assert len(arrs) == len(ref) == 43
     for a, b in zip(arrs, ref):

@@ -13,7 +13,7 @@ if [ "$3" = "full" ]; then
 fi
 for r in $(seq 1 $R); do
   for m in ${MASKS:-1 28}; do
-    NRX_UPDATE_RR=$m timeout -k 10 200 python bench.py --steps 400 --warmup 30 --no-cpu-baseline --no-latency --no-e2e > $O/bench_m${m}_$r.json 2> $O/bench_m${m}_$r.err || exit 1
+    NRX_UPDATE_RR=$m timeout -k 10 200 python bench.py --full --steps 400 --warmup 30 --no-cpu-baseline --no-latency --no-e2e > $O/bench_m${m}_$r.json 2> $O/bench_m${m}_$r.err || exit 1
     python -c "import json; d=json.load(open('$O/bench_m${m}_$r.json')); r=d['roofline']; k=d['kernels']; print('mask $m', round(d['value']), r['avg_launch_us'], r['frac'], {n: v['avg_us'] for n, v in k.items()})"
   done
 done

@@ -19,7 +19,7 @@ for r in $(seq 1 $R); do
     F=1
     if [ $n = default ] || [ $n = three ]; then L=$PWD/neural_rx_amd/lib/libnrx.so; else L=$PWD/neural_rx_amd/lib/var/$n/libnrx.so; fi
     if [ $n = three ]; then F=0; fi
-    NRX_FUSED=$F NRX_LIB_PATH=$L timeout -k 10 200 python bench.py --steps 400 --warmup 30 --no-cpu-baseline --no-latency --no-e2e > $O/bench_${n}_$r.json 2> $O/bench_${n}_$r.err || exit 1
+    NRX_FUSED=$F NRX_LIB_PATH=$L timeout -k 10 200 python bench.py --full --steps 400 --warmup 30 --no-cpu-baseline --no-latency --no-e2e > $O/bench_${n}_$r.json 2> $O/bench_${n}_$r.err || exit 1
     python -c "import json; d=json.load(open('$O/bench_${n}_$r.json')); r=d['roofline']; print('$n', $r, round(d['value']), r['avg_launch_us'], r['frac'], r.get('fused_queue', {}).get('update_items_waited'))"
   done
 done
