@@ -27,6 +27,11 @@
  *   h_ref    [B][U][F][T][2A]       f32 out (NULL to skip the ChEst readout)
  * Sign convention: Sionna's LLR = log p(b=1)/p(b=0) (the Aerial layout negates,
  * neural_rx.py:1811; the Python layer does that, not the kernels).
+ *
+ * Besides the CGNN, the library holds what an evaluation loop needs on the device: the seeded
+ * slot generator and the uncoded error counters, and the classical baseline detector the
+ * reference's tables put next to the NRX (per-RE MIMO LMMSE + max-log demapper;
+ * utils/baseline_rx.py), which reads the generator's tensors and writes LLRs in the layout above.
  */
 #ifndef NRX_H_
 #define NRX_H_
@@ -267,6 +272,44 @@ typedef struct nrx_count_io {
 } nrx_count_io;
 
 int nrx_count_errors(const nrx_count_io* io, void* stream);
+
+/* ---------------------------------------------------------------- classical baseline
+ * Per-resource-element MIMO LMMSE equaliser + max-log QAM demapper: the detector of the
+ * reference's baseline receivers (utils/baseline_rx.py:262-272, LinearDetector("lmmse", "bit",
+ * "maxlog"); every cfg sets demapping_type = 'maxlog').  It consumes the generator's tensors as
+ * they are (y, and h_hat or the true h as `h`) and writes LLRs in the engine's layout, so the
+ * error counters above read them unchanged.  Per RE (b, f, t), with s = no + err_var and H [A x U]
+ * the channel whose columns of inactive users (active <= 0) are zero:
+ *   G = H^H H + s I,  x^ = G^-1 H^H y,  a_u = (G^-1)_uu,  mu_u = 1 - s a_u,
+ *   x~_u = x^_u / mu_u,  nu_u = s a_u / mu_u      (Sionna lmmse_equalizer with whiten_interference:
+ *                                                  no_eff = 1 / diag(G H) - 1)
+ *   llr[k] = (min_{c: b_k = 0} |x~_u - c|^2 - min_{c: b_k = 1} |x~_u - c|^2) / nu_u,  k < m,
+ * over the Gray QAM of TS 38.211 5.1 with m = mcs_bits[mcs[b][u]] bits (the generator's
+ * constellation).  Entries k >= m, inactive users, DMRS symbols and RE-users with mu_u < 1e-6 are
+ * written exactly 0; every element of llr is written on every call.  f32 arithmetic, no atomics
+ * (bit-identical from call to call), no workspace, no allocation, no host synchronisation;
+ * asynchronous on `stream`.  Every argument is checked before the first HIP call: a NULL io / y /
+ * h / active / llr, no <= 0, err_var < 0 or a bit width outside {2, 4, 6} is NRX_ERR_INVALID_ARG; T != 14,
+ * B outside 1..65535, F outside 1..3300, U < 1, A outside 1..16, num_mcs outside 1..8 or bits_stride <
+ * max(mcs_bits) is NRX_ERR_SHAPE; U > 8 is NRX_ERR_UNSUPPORTED. */
+typedef struct nrx_lmmse_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B (1..65535), U (1..8), F (1..3300), T = 14 */
+  int32_t num_rx_ant;          /* A, 1..16 */
+  int32_t bits_stride;         /* last dim of llr, >= max(mcs_bits) */
+  int32_t num_mcs;             /* 1..8 */
+  int32_t mcs_bits[8];         /* 2, 4 or 6 */
+  int32_t dmrs_symbol_mask;    /* bit t set: symbol t carries no data, its LLRs are written 0 */
+  int32_t pad_;
+  double  no;                  /* noise variance per complex RE, > 0 */
+  double  err_var;             /* >= 0, added to no: channel-estimation error power (0 for perfect CSI) */
+  const float*   y;            /* [B][F][T][2A]      nrx_io.y layout */
+  const float*   h;            /* [B][U][F][T][2A]   h_hat or the true h (nrx_gen_out layouts) */
+  const float*   active;       /* [B][U] */
+  const uint8_t* mcs;          /* [B][U] or NULL (= 0) */
+  float*         llr;          /* [1][B][U][F][T][bits_stride], Sionna sign log p(1)/p(0) */
+} nrx_lmmse_io;
+
+int nrx_lmmse_detect(const nrx_lmmse_io* io, void* stream);
 
 /* Host helper: nearest-pilot positional encoding pe[U][F][T][2] for DMRS
  * configuration type 1 (restates onnx_utils.py:172-260 for the product path).

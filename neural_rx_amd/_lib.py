@@ -29,7 +29,7 @@ EXPORTS = [
     "nrx_profile_enable", "nrx_profile_read", "nrx_aerial_workspace_size", "nrx_forward_aerial",
     "nrx_llr_demap", "nrx_gen_workspace_size", "nrx_generate_slots", "nrx_count_errors",
     "nrx_workspace_size_ex", "nrx_forward_ex", "nrx_fused_status", "nrx_fused_config",
-    "nrx_build_id", "nrx_update_schedule",
+    "nrx_build_id", "nrx_update_schedule", "nrx_lmmse_detect",
 ]
 # enum nrx_y_layout
 Y_LAYOUTS = {"cgnn": 0, "sionna": 1, "split": 2}
@@ -170,6 +170,28 @@ class nrx_count_io(ctypes.Structure):
     ]
 
 
+class nrx_lmmse_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_rx_ant", ctypes.c_int32),
+        ("bits_stride", ctypes.c_int32),
+        ("num_mcs", ctypes.c_int32),
+        ("mcs_bits", ctypes.c_int32 * 8),
+        ("dmrs_symbol_mask", ctypes.c_int32),
+        ("pad_", ctypes.c_int32),
+        ("no", ctypes.c_double),
+        ("err_var", ctypes.c_double),
+        ("y", ctypes.c_void_p),
+        ("h", ctypes.c_void_p),
+        ("active", ctypes.c_void_p),
+        ("mcs", ctypes.c_void_p),
+        ("llr", ctypes.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -239,6 +261,8 @@ def load(path: str = LIB_PATH):
     lib.nrx_generate_slots.restype = c.c_int
     lib.nrx_count_errors.argtypes = [P(nrx_count_io), c.c_void_p]
     lib.nrx_count_errors.restype = c.c_int
+    lib.nrx_lmmse_detect.argtypes = [P(nrx_lmmse_io), c.c_void_p]
+    lib.nrx_lmmse_detect.restype = c.c_int
     lib.nrx_api_version.argtypes = []
     lib.nrx_api_version.restype = c.c_int32
     lib.nrx_update_schedule.argtypes = [c.c_void_p, c.c_int32]

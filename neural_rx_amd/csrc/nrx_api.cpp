@@ -880,6 +880,31 @@ int nrx_count_errors(const nrx_count_io* io, void* stream) {
   return NRX_OK;
 }
 
+int nrx_lmmse_detect(const nrx_lmmse_io* io, void* stream) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->y || !io->h || !io->active || !io->llr) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
+  if (!(io->err_var >= 0.0) || !std::isfinite(io->err_var))
+    return fail(NRX_ERR_INVALID_ARG, "err_var must be finite and >= 0");
+  if (io->num_mcs < 1 || io->num_mcs > 8) return fail(NRX_ERR_SHAPE, "num_mcs must be 1..8");
+  int bmax = 0;
+  for (int m = 0; m < io->num_mcs; ++m) {
+    if (io->mcs_bits[m] != 2 && io->mcs_bits[m] != 4 && io->mcs_bits[m] != 6)
+      return fail(NRX_ERR_INVALID_ARG, "mcs_bits must be 2, 4 or 6");
+    bmax = io->mcs_bits[m] > bmax ? io->mcs_bits[m] : bmax;
+  }
+  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
+  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
+  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
+  if (io->num_tx < 1) return fail(NRX_ERR_SHAPE, "num_tx must be >= 1");
+  if (io->num_tx > 8) return fail(NRX_ERR_UNSUPPORTED, "the LMMSE kernel is built for num_tx <= 8");
+  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
+  if (io->bits_stride < bmax) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
+  hipError_t e = launch_lmmse(*io, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "lmmse detector launch");
+  return NRX_OK;
+}
+
 int nrx_profile_enable(nrx_handle* h, int32_t enable) {
   if (!h) return fail(NRX_ERR_INVALID_ARG, "null handle");
   if (enable) {

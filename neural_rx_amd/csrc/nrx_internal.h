@@ -170,6 +170,9 @@ size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base);
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_out& o, void* ws, hipStream_t st);
 hipError_t launch_count_errors(const nrx_count_io& c, hipStream_t st);
 
+// LMMSE + max-log baseline detector (nrx_lmmse.hip); io validated by nrx_lmmse_detect
+hipError_t launch_lmmse(const nrx_lmmse_io& io, hipStream_t st);
+
 hipError_t launch_llr_demap(const float* llr, int B, int U, int F, int T, int bits_stride, int bits,
                             const int32_t* data_re, int n_data, float* out, hipStream_t st);
 

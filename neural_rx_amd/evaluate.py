@@ -31,6 +31,7 @@ import numpy as np
 
 from .config import dmrs_symbols, get_config
 from .generator import GenParams, SlotGenerator, count_errors, ebno_to_no
+from .baseline import BaselineReceiver
 from .receiver import CGNNEngine, compute_pe, spec_for
 
 
@@ -53,14 +54,13 @@ def _dist():
     return dist if dist.is_available() and dist.is_initialized() else None
 
 
-def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int,
-            max_mc_iter: int = 100, num_target_block_errors: int = 100, target_bler: Optional[float] = None,
-            early_stop: bool = True, num_it: Optional[int] = None, precision: str = "f16",
-            verbose: bool = False, sync_every: int = 8) -> SimResult:
-    """Sionna ``sim_ber`` loop on the GPU (this rank's shard of every Monte-Carlo batch:
-    global slot ``(it * world + rank) * batch_size + b``).  The counters are reduced
-    over ranks (and copied to the host) every ``sync_every`` batches and at the end of a
-    point; every rank runs the same number of batches, so the collectives pair up."""
+def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int, max_mc_iter: int,
+             num_target_block_errors: int, target_bler: Optional[float], early_stop: bool, verbose: bool,
+             sync_every: int, label: Optional[str] = None) -> SimResult:
+    """The Monte-Carlo loop shared by every system: ``step(sb, no) -> llr`` turns a generated batch
+    into LLRs in the engine's layout, ``check()`` runs before every counter reduction.  Slot
+    offsets, reductions and stopping rules do not depend on the system, so point k, iteration i
+    is the same slot for every receiver and their curves are paired."""
     import torch
     dist = _dist()
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
@@ -69,9 +69,6 @@ def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], b
     sync_every = max(1, int(sync_every))
     p = gen.p
     dev = torch.device(f"cuda:{gen.device}")
-    pe = torch.from_numpy(compute_pe(p.num_tx, p.num_subcarriers, p.dmrs_symbols, p.cdm_group)).to(dev)
-    spec = engine.spec
-    llr_out = engine.alloc_outputs(batch_size, p.num_tx, p.num_subcarriers, want_h=False)
     res = SimResult([], [], [], [], [], 0.0, 0)
     t0 = time.perf_counter()
     point_seed = 0
@@ -83,16 +80,12 @@ def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], b
         while it < max_mc_iter:
             off = ((point_seed * max_mc_iter + it) * world + rank) * batch_size
             sb = gen(batch_size, no, slot_offset=off)
-            mcs_mask = sb.mcs_mask if spec.num_mcs > 1 else None
-            llr, _ = engine.forward(sb.y, pe, sb.h_hat, sb.active, mcs_mask=mcs_mask, num_it=num_it,
-                                    precision=precision, out=llr_out, want_h=False)
+            llr = step(sb, no)
             count_errors(llr, sb.bits, sb.active, sb.mcs, p.mcs_bits, p.dmrs_symbols, counts=counts)
             it += 1
             if it % sync_every and it < max_mc_iter:
                 continue
-            # the one-launch forward's error word: a timed-out or incomplete forward raises here
-            # instead of entering the counts (include/nrx.h nrx_fused_status)
-            engine.check()
+            check()
             tot = counts.sum(0)
             if host_reduce:
                 tot = tot.cpu()
@@ -110,7 +103,7 @@ def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], b
         res.mc_iters.append(it)
         res.slots += it * batch_size * world
         if verbose and rank == 0:
-            print(f"EbNo {ebno:6.2f} dB  BER {ber:.4e}  BLER(uncoded) {bler:.4e}  "
+            print(f"{label + '  ' if label else ''}EbNo {ebno:6.2f} dB  BER {ber:.4e}  BLER(uncoded) {bler:.4e}  "
                   f"bit errors {total[0]}  blocks {total[3]}  iters {it}", flush=True)
         point_seed += 1
         if early_stop and total[0] == 0:
@@ -120,6 +113,62 @@ def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], b
     torch.cuda.synchronize(dev)
     res.seconds = time.perf_counter() - t0
     return res
+
+
+def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int,
+            max_mc_iter: int = 100, num_target_block_errors: int = 100, target_bler: Optional[float] = None,
+            early_stop: bool = True, num_it: Optional[int] = None, precision: str = "f16",
+            verbose: bool = False, sync_every: int = 8) -> SimResult:
+    """Sionna ``sim_ber`` loop on the GPU (this rank's shard of every Monte-Carlo batch:
+    global slot ``(it * world + rank) * batch_size + b``).  The counters are reduced
+    over ranks (and copied to the host) every ``sync_every`` batches and at the end of a
+    point; every rank runs the same number of batches, so the collectives pair up."""
+    return _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors, target_bler,
+                        early_stop, num_it, precision, verbose, sync_every, None)
+
+
+def _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors, target_bler,
+                 early_stop, num_it, precision, verbose, sync_every, label) -> SimResult:
+    """sim_ber; ``label`` prefixes the verbose lines (the CLI's runs with baselines)"""
+    import torch
+    p = gen.p
+    dev = torch.device(f"cuda:{gen.device}")
+    pe = torch.from_numpy(compute_pe(p.num_tx, p.num_subcarriers, p.dmrs_symbols, p.cdm_group)).to(dev)
+    spec = engine.spec
+    llr_out = engine.alloc_outputs(batch_size, p.num_tx, p.num_subcarriers, want_h=False)
+
+    def step(sb, no):
+        mcs_mask = sb.mcs_mask if spec.num_mcs > 1 else None
+        llr, _ = engine.forward(sb.y, pe, sb.h_hat, sb.active, mcs_mask=mcs_mask, num_it=num_it,
+                                precision=precision, out=llr_out, want_h=False)
+        return llr
+
+    # engine.check: the one-launch forward's error word -- a timed-out or incomplete forward raises
+    # at the reduction instead of entering the counts (include/nrx.h nrx_fused_status)
+    return _mc_loop(step, engine.check, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors,
+                    target_bler, early_stop, verbose, sync_every, label)
+
+
+def sim_ber_baseline(receiver: BaselineReceiver, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int,
+                     max_mc_iter: int = 100, num_target_block_errors: int = 100,
+                     target_bler: Optional[float] = None, early_stop: bool = True, verbose: bool = False,
+                     sync_every: int = 8, label: Optional[str] = None) -> SimResult:
+    """``sim_ber`` with a classical baseline (``baseline.BaselineReceiver``) in place of the
+    engine: the same loop on the same slots (``_mc_loop``), so a baseline curve and the NRX curve
+    of one generator are paired.  ``baseline_perf_csi_lmmse`` needs ``SlotGenerator(want_h=True)``."""
+    if receiver.perfect_csi and not gen.want_h:
+        raise ValueError("baseline_perf_csi_lmmse needs SlotGenerator(want_h=True)")
+    return _mc_loop(receiver, lambda: None, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors,
+                    target_bler, early_stop, verbose, sync_every, label)
+
+
+def baseline_note(name: str, receiver: BaselineReceiver) -> Optional[str]:
+    """The line the CLI prints beside a baseline curve that is not meaningful (baseline.py: LS
+    estimates with two active ports on one CDM group), or None."""
+    if not receiver.contaminated:
+        return None
+    return (f"{name}: note: active ports can share a CDM group and the generator applies no cover code, "
+            "so h_hat is pilot-contaminated and this curve is not a meaningful baseline")
 
 
 def main(argv=None):
@@ -138,6 +187,9 @@ def main(argv=None):
     ap.add_argument("-sync_every", type=int, default=8, help="MC batches per counter all-reduce")
     ap.add_argument("-gpu", type=int, default=None)
     ap.add_argument("-out", default=None, help="write the result JSON here")
+    ap.add_argument("-baselines", nargs="*", default=[], choices=["lsnn_lmmse", "perf_csi_lmmse"],
+                    help="classical baselines run on the same slots (baseline.BaselineReceiver); the JSON "
+                         "gains \"baselines\": {name: result}")
     a = ap.parse_args(argv)
 
     import torch
@@ -156,20 +208,33 @@ def main(argv=None):
     u = cfg.max_num_tx
     params = GenParams.from_config(cfg, num_tx=u, num_prbs=a.num_prbs, var_mcs=a.var_mcs, seed=a.seed)
     params.num_active = a.num_tx_eval or u
-    gen = SlotGenerator(params, device=device)
+    systems = {n: "baseline_" + n for n in a.baselines}
+    gen = SlotGenerator(params, device=device, want_h="perf_csi_lmmse" in systems)
     ebno = a.ebno_db if a.ebno_db is not None else list(np.arange(-2.0, 8.0, 1.0))
-    res = sim_ber(engine, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors, a.target_bler,
-                  num_it=cfg.num_nrx_iter_eval, precision=a.precision, verbose=True, sync_every=a.sync_every)
+    res = _sim_ber_nrx(engine, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors, a.target_bler,
+                       True, cfg.num_nrx_iter_eval, a.precision, True, a.sync_every, "nrx" if systems else None)
+    base = {}
+    for name, system in systems.items():
+        rx = BaselineReceiver(system, params, device=device)
+        note = baseline_note(name, rx)
+        if note and rank == 0:
+            print(note, flush=True)
+        base[name] = sim_ber_baseline(rx, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors,
+                                      a.target_bler, verbose=True, sync_every=a.sync_every, label=name)
+    d = None
     if rank == 0:
         d = res.as_dict()
         d.update(config=cfg.label, num_tx_eval=params.num_active, dmrs_symbols=list(dmrs_symbols(cfg)),
                  world=world, slots_per_s=res.slots / res.seconds)
+        if base:
+            d["baselines"] = {name: r.as_dict() for name, r in base.items()}
         print(json.dumps(d))
         if a.out:
             with open(a.out, "w") as f:
                 json.dump(d, f)
     if world > 1:
         dist.destroy_process_group()
+    return d
 
 
 if __name__ == "__main__":
