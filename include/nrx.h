@@ -311,6 +311,82 @@ typedef struct nrx_lmmse_io {
 
 int nrx_lmmse_detect(const nrx_lmmse_io* io, void* stream);
 
+/* ---------------------------------------------------------------- channel-estimation baselines
+ * The estimators of the reference's baseline_lmmse_lmmse / baseline_lslin_lmmse systems
+ * (utils/baseline_rx.py:100-229) and the statistics of its scripts/compute_cov_mat.py, for the
+ * generator's channel.  The host side (covariance matrices, filter design) is
+ * neural_rx_amd/chest.py.
+ *
+ * Covariance lag sums of the true channel h [B][U][F][T][2A] (nrx_gen_out.h), over all (b, u)
+ * planes, antennas and the other axis, in float64:
+ *   acc[d]     += sum_{b,u,a,t} sum_{f < F - d} h[f + d] conj(h[f])      d = 0..F-1   (frequency)
+ *   acc[F + d] += sum_{b,u,a,f} sum_{t < 14 - d} h[t + d] conj(h[t])     d = 0..13    (time)
+ * acc is a device array double[F + 14][2] (re, im) that the caller zeroes once; every call adds
+ * to it, so several batches accumulate.  The caller divides by the product counts
+ * B U A 14 (F - d) / B U A F (14 - d) and builds the Hermitian Toeplitz matrices R_f, R_t: the
+ * generator's channel is stationary in f and t (oracle/synth_ref.py), so lags estimate what the
+ * reference's full matrices estimate, with less variance; its spatial covariance is the identity.
+ * f64 products and sums in a fixed order (per-workgroup partial sums in the workspace, then one
+ * ordered reduction), no atomics: the same input gives the same bits.  Asynchronous on `stream`.
+ * A NULL io / h / acc / workspace / bytes is NRX_ERR_INVALID_ARG; T != 14, B outside 1..65535,
+ * U outside 1..16, F outside 1..3300 or A outside 1..16 is NRX_ERR_SHAPE; a workspace smaller than
+ * nrx_cov_workspace_size is NRX_ERR_WORKSPACE.  Every argument is checked before the first HIP call. */
+typedef struct nrx_cov_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B, U (1..16), F (1..3300), T = 14 */
+  int32_t num_rx_ant;          /* A, 1..16 */
+  int32_t pad_;
+  const float* h;              /* [B][U][F][T][2A] */
+  double*      acc;            /* [F + 14][2], accumulated */
+} nrx_cov_io;
+
+int nrx_cov_workspace_size(const nrx_cov_io* io, size_t* bytes);
+int nrx_cov_accumulate(const nrx_cov_io* io, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Channel estimators on the LS estimates at the own pilots.  Both read only the own-pilot REs of
+ * h_hat (subcarriers f with f mod 2 = cdm_group[u] on the DMRS symbols; the generator's
+ * nearest-neighbour h_hat holds the LS estimate there) and write every element of h_out
+ * [B][U][F][T][2A], zeros for inactive users (active <= 0) and for a user without a pilot (F = 1,
+ * group 1).  f32, no atomics, no workspace, no allocation, no host synchronisation; asynchronous on
+ * `stream`; bit-identical from call to call and independent of how slots are split into batches.
+ *
+ * nrx_chest_lmmse: the exact 2-D Wiener filter under the separable covariance R_t (x) R_f, from
+ * host-designed tables (|P| own pilots, nd DMRS symbols D, k < nd eigen-components of R_t[D, D]):
+ *   z_k[p]  = sum_d vconj[k][d] h_ls[P_p, D_d]           vconj[k][d] = conj(v_k[d])
+ *   h^[f,t] = sum_k tcoef[k][t] (W_k z_k)[f]             W_k = filt[cdm_group[u]][k], F x |P|
+ * filt [2][nd][F][Pmax][2] with Pmax = (F + 1) / 2 (rows of group 1 zero-padded at odd F), tcoef
+ * [nd][14][2], vconj [nd][nd][2]: f32 (re, im) device arrays; filt 8-byte aligned.  The products
+ * W_k z_k run on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32).
+ *
+ * nrx_chest_lin: per DMRS symbol linear in frequency between the own pilots that bracket f -- beyond
+ * the first / last pilot the line through the two nearest ones is extended -- then the same along
+ * time between the DMRS symbols; a single pilot or a single DMRS symbol is repeated.  With f between
+ * pilots p0 < p1 = p0 + 2, wf = (f - p0) / 2, and t between symbols t0 < t1, wt = (t - t0) / (t1 - t0):
+ *   h^ = (1 - wt) ((1 - wf) x[p0,t0] + wf x[p1,t0]) + wt ((1 - wf) x[p0,t1] + wf x[p1,t1]).
+ * filt / tcoef / vconj are not read.
+ *
+ * A NULL io / h_hat / active / h_out (nrx_chest_lmmse: or table), a filt that is not 8-byte
+ * aligned, no <= 0, a DMRS symbol outside 0..13 or not ascending, or a cdm_group outside {0, 1} is
+ * NRX_ERR_INVALID_ARG; T != 14, B outside 1..65535, U outside 1..16, F outside
+ * 1..3300, A outside 1..16 or num_dmrs_symbols outside 1..4 is NRX_ERR_SHAPE.  Every argument is
+ * checked before the first HIP call. */
+typedef struct nrx_chest_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B, U (1..16), F (1..3300), T = 14 */
+  int32_t num_rx_ant;          /* A, 1..16 */
+  int32_t num_dmrs_symbols;    /* nd, 1..4 */
+  int32_t dmrs_symbols[4];     /* ascending */
+  int32_t cdm_group[16];       /* per port, 0/1 */
+  double  no;                  /* noise variance per complex RE the estimate is made at, > 0 */
+  const float* h_hat;          /* [B][U][F][T][2A], read at the own pilots only */
+  const float* active;         /* [B][U] */
+  const float* filt;           /* [2][nd][F][(F + 1) / 2][2] */
+  const float* tcoef;          /* [nd][14][2] */
+  const float* vconj;          /* [nd][nd][2] */
+  float*       h_out;          /* [B][U][F][T][2A] */
+} nrx_chest_io;
+
+int nrx_chest_lmmse(const nrx_chest_io* io, void* stream);
+int nrx_chest_lin(const nrx_chest_io* io, void* stream);
+
 /* Host helper: nearest-pilot positional encoding pe[U][F][T][2] for DMRS
  * configuration type 1 (restates onnx_utils.py:172-260 for the product path).
  * dmrs_symbols: the DMRS OFDM symbol indices; cdm_group[u] in {0,1}. */

@@ -29,7 +29,8 @@ EXPORTS = [
     "nrx_profile_enable", "nrx_profile_read", "nrx_aerial_workspace_size", "nrx_forward_aerial",
     "nrx_llr_demap", "nrx_gen_workspace_size", "nrx_generate_slots", "nrx_count_errors",
     "nrx_workspace_size_ex", "nrx_forward_ex", "nrx_fused_status", "nrx_fused_config",
-    "nrx_build_id", "nrx_update_schedule", "nrx_lmmse_detect",
+    "nrx_build_id", "nrx_update_schedule", "nrx_lmmse_detect", "nrx_cov_workspace_size", "nrx_cov_accumulate",
+    "nrx_chest_lmmse", "nrx_chest_lin",
 ]
 # enum nrx_y_layout
 Y_LAYOUTS = {"cgnn": 0, "sionna": 1, "split": 2}
@@ -192,6 +193,39 @@ class nrx_lmmse_io(ctypes.Structure):
     ]
 
 
+class nrx_cov_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_rx_ant", ctypes.c_int32),
+        ("pad_", ctypes.c_int32),
+        ("h", ctypes.c_void_p),
+        ("acc", ctypes.c_void_p),
+    ]
+
+
+class nrx_chest_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_rx_ant", ctypes.c_int32),
+        ("num_dmrs_symbols", ctypes.c_int32),
+        ("dmrs_symbols", ctypes.c_int32 * 4),
+        ("cdm_group", ctypes.c_int32 * 16),
+        ("no", ctypes.c_double),
+        ("h_hat", ctypes.c_void_p),
+        ("active", ctypes.c_void_p),
+        ("filt", ctypes.c_void_p),
+        ("tcoef", ctypes.c_void_p),
+        ("vconj", ctypes.c_void_p),
+        ("h_out", ctypes.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -263,6 +297,14 @@ def load(path: str = LIB_PATH):
     lib.nrx_count_errors.restype = c.c_int
     lib.nrx_lmmse_detect.argtypes = [P(nrx_lmmse_io), c.c_void_p]
     lib.nrx_lmmse_detect.restype = c.c_int
+    lib.nrx_cov_workspace_size.argtypes = [P(nrx_cov_io), P(c.c_size_t)]
+    lib.nrx_cov_workspace_size.restype = c.c_int
+    lib.nrx_cov_accumulate.argtypes = [P(nrx_cov_io), c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.nrx_cov_accumulate.restype = c.c_int
+    lib.nrx_chest_lmmse.argtypes = [P(nrx_chest_io), c.c_void_p]
+    lib.nrx_chest_lmmse.restype = c.c_int
+    lib.nrx_chest_lin.argtypes = [P(nrx_chest_io), c.c_void_p]
+    lib.nrx_chest_lin.restype = c.c_int
     lib.nrx_api_version.argtypes = []
     lib.nrx_api_version.restype = c.c_int32
     lib.nrx_update_schedule.argtypes = [c.c_void_p, c.c_int32]

@@ -905,6 +905,71 @@ int nrx_lmmse_detect(const nrx_lmmse_io* io, void* stream) {
   return NRX_OK;
 }
 
+static int check_cov(const nrx_cov_io* io) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->h || !io->acc) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
+  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
+  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
+  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
+  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
+  return NRX_OK;
+}
+
+int nrx_cov_workspace_size(const nrx_cov_io* io, size_t* bytes) {
+  if (int rc = check_cov(io)) return rc;
+  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
+  *bytes = cov_workspace_bytes(*io);
+  return NRX_OK;
+}
+
+int nrx_cov_accumulate(const nrx_cov_io* io, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_cov(io)) return rc;
+  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
+  const size_t need = cov_workspace_bytes(*io);
+  if (workspace_bytes < need)
+    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  hipError_t e = launch_cov_accumulate(*io, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "covariance launch");
+  return NRX_OK;
+}
+
+static int check_chest(const nrx_chest_io* io, bool lmmse) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->h_hat || !io->active || !io->h_out) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (lmmse && (!io->filt || !io->tcoef || !io->vconj)) return fail(NRX_ERR_INVALID_ARG, "null table pointer");
+  if (lmmse && ((uintptr_t)io->filt & 7)) return fail(NRX_ERR_INVALID_ARG, "filt must be 8-byte aligned");
+  if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
+  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
+  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
+  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
+  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
+  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
+  if (io->num_dmrs_symbols < 1 || io->num_dmrs_symbols > 4) return fail(NRX_ERR_SHAPE, "num_dmrs_symbols must be 1..4");
+  for (int k = 0; k < io->num_dmrs_symbols; ++k) {
+    const int t = io->dmrs_symbols[k];
+    if (t < 0 || t >= kT || (k && t <= io->dmrs_symbols[k - 1]))
+      return fail(NRX_ERR_INVALID_ARG, "dmrs_symbols must be ascending symbol indices below 14");
+  }
+  for (int u = 0; u < io->num_tx; ++u)
+    if (io->cdm_group[u] != 0 && io->cdm_group[u] != 1) return fail(NRX_ERR_INVALID_ARG, "cdm_group must be 0/1");
+  return NRX_OK;
+}
+
+int nrx_chest_lmmse(const nrx_chest_io* io, void* stream) {
+  if (int rc = check_chest(io, true)) return rc;
+  hipError_t e = launch_chest_lmmse(*io, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "lmmse channel estimator launch");
+  return NRX_OK;
+}
+
+int nrx_chest_lin(const nrx_chest_io* io, void* stream) {
+  if (int rc = check_chest(io, false)) return rc;
+  hipError_t e = launch_chest_lin(*io, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "linear channel estimator launch");
+  return NRX_OK;
+}
+
 int nrx_profile_enable(nrx_handle* h, int32_t enable) {
   if (!h) return fail(NRX_ERR_INVALID_ARG, "null handle");
   if (enable) {

@@ -32,6 +32,7 @@ import numpy as np
 from .config import dmrs_symbols, get_config
 from .generator import GenParams, SlotGenerator, count_errors, ebno_to_no
 from .baseline import BaselineReceiver
+from .chest import COV_SLOT_OFFSET, EstimatorBaselineReceiver, estimate_covariance
 from .receiver import CGNNEngine, compute_pe, spec_for
 
 
@@ -149,7 +150,7 @@ def _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_bloc
                     target_bler, early_stop, verbose, sync_every, label)
 
 
-def sim_ber_baseline(receiver: BaselineReceiver, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int,
+def sim_ber_baseline(receiver, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int,
                      max_mc_iter: int = 100, num_target_block_errors: int = 100,
                      target_bler: Optional[float] = None, early_stop: bool = True, verbose: bool = False,
                      sync_every: int = 8, label: Optional[str] = None) -> SimResult:
@@ -162,7 +163,7 @@ def sim_ber_baseline(receiver: BaselineReceiver, gen: SlotGenerator, ebno_dbs: S
                     target_bler, early_stop, verbose, sync_every, label)
 
 
-def baseline_note(name: str, receiver: BaselineReceiver) -> Optional[str]:
+def baseline_note(name: str, receiver) -> Optional[str]:
     """The line the CLI prints beside a baseline curve that is not meaningful (baseline.py: LS
     estimates with two active ports on one CDM group), or None."""
     if not receiver.contaminated:
@@ -187,9 +188,13 @@ def main(argv=None):
     ap.add_argument("-sync_every", type=int, default=8, help="MC batches per counter all-reduce")
     ap.add_argument("-gpu", type=int, default=None)
     ap.add_argument("-out", default=None, help="write the result JSON here")
-    ap.add_argument("-baselines", nargs="*", default=[], choices=["lsnn_lmmse", "perf_csi_lmmse"],
-                    help="classical baselines run on the same slots (baseline.BaselineReceiver); the JSON "
-                         "gains \"baselines\": {name: result}")
+    ap.add_argument("-baselines", nargs="*", default=[],
+                    choices=["lsnn_lmmse", "lslin_lmmse", "lmmse_lmmse", "perf_csi_lmmse"],
+                    help="classical baselines run on the same slots (baseline.BaselineReceiver, "
+                         "chest.EstimatorBaselineReceiver); the JSON gains \"baselines\": {name: result}")
+    ap.add_argument("-num_cov_slots", type=int, default=2048,
+                    help="slots the covariance of lmmse_lmmse is estimated from (drawn at slot offset 2^40, "
+                         "disjoint from every Monte-Carlo slot)")
     a = ap.parse_args(argv)
 
     import torch
@@ -209,13 +214,26 @@ def main(argv=None):
     params = GenParams.from_config(cfg, num_tx=u, num_prbs=a.num_prbs, var_mcs=a.var_mcs, seed=a.seed)
     params.num_active = a.num_tx_eval or u
     systems = {n: "baseline_" + n for n in a.baselines}
-    gen = SlotGenerator(params, device=device, want_h="perf_csi_lmmse" in systems)
+    gen = SlotGenerator(params, device=device, want_h=bool({"perf_csi_lmmse", "lmmse_lmmse"} & set(systems)))
     ebno = a.ebno_db if a.ebno_db is not None else list(np.arange(-2.0, 8.0, 1.0))
     res = _sim_ber_nrx(engine, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors, a.target_bler,
                        True, cfg.num_nrx_iter_eval, a.precision, True, a.sync_every, "nrx" if systems else None)
     base = {}
+    cov = None
+    if "lmmse_lmmse" in systems:
+        # the counterpart of compute_cov_mat.py before evaluate (scripts/evaluate.py:159); every rank
+        # estimates the same matrices from the same slots
+        if a.num_cov_slots < 1 or COV_SLOT_OFFSET <= len(ebno) * a.max_mc_iter * world * a.batch_size:
+            raise ValueError("-num_cov_slots must be >= 1 and the Monte-Carlo slots must end below 2^40")
+        cov = estimate_covariance(gen, a.num_cov_slots, a.batch_size).matrices()
     for name, system in systems.items():
-        rx = BaselineReceiver(system, params, device=device)
+        if system in EstimatorBaselineReceiver.SYSTEMS:
+            # the filter is designed again at every Eb/N0 point (ChannelEstimator.prepare)
+            rx = EstimatorBaselineReceiver(system, params, device=device)
+            if cov is not None:
+                rx.set_covariance(*cov)
+        else:
+            rx = BaselineReceiver(system, params, device=device)
         note = baseline_note(name, rx)
         if note and rank == 0:
             print(note, flush=True)
@@ -228,6 +246,8 @@ def main(argv=None):
                  world=world, slots_per_s=res.slots / res.seconds)
         if base:
             d["baselines"] = {name: r.as_dict() for name, r in base.items()}
+        if cov is not None:
+            d["num_cov_slots"] = a.num_cov_slots
         print(json.dumps(d))
         if a.out:
             with open(a.out, "w") as f:

@@ -1,0 +1,273 @@
+"""The channel-estimation baselines on the GPU (``nrx_cov_accumulate``, ``nrx_chest_lmmse``,
+``nrx_chest_lin``) against the numpy statements of tests/chest_ref.py, and their leg of the
+evaluation (needs an MI355X).
+
+Cases (tests/chest_ref.CASES; slots from the GPU generator with ``want_h=True``, seed 7,
+cdm_group[u] = u % 2, 5 dB):
+
+    K1  U 2  A 4   F 24   DMRS (2, 11)     B 3              the bench model's geometry
+    K2  U 1  A 2   F 13   DMRS (2,)        B 1              odd F, one DMRS symbol, 7 / 6 pilots, partial tiles
+    K3  U 4  A 16  F 36   DMRS (2, 7, 11)  B 2, 2 active    nd = 3, 2A = 32, inactive users written zero
+    K4  U 2  A 4   F 132  DMRS (2, 11)     B 2              several M tiles, K = 264 not a tile multiple
+    K5  U 2  A 1   F 12   DMRS (2, 11)     B 2              2A = 2: N far below a tile
+
+Estimator gate (the gate of tests/test_gpu_lmmse.py).  e = max |gpu - ref| / max(1, |ref|) against
+the float64 oracle over EVERY element of the output; floor = the same expression for the oracle's
+own float32 run against its float64 run (reference against reference, never the kernel); the test
+asserts e <= 8 * max(floor, 1e-6).  The LMMSE oracle applies the same f32-rounded tables as the
+kernel (chest_ref.lmmse_apply); the tables come from chest.lmmse_design on the analytic covariance
+of chest_ref.model_covariance, and the design itself is checked against the brute-force Kronecker
+filter in tests/test_chest_ref.py.
+
+Figures of an MI355X run (as the test prints them: floor from numpy, e from the kernel):
+
+    case  estimator  floor    e        gate
+    K1    lmmse      4.2e-7   3.8e-7   8.0e-6
+    K1    lin        2.0e-7   2.0e-7   8.0e-6
+    K2    lmmse      1.5e-7   1.1e-7   8.0e-6
+    K2    lin        5.2e-8   5.2e-8   8.0e-6
+    K3    lmmse      3.8e-7   5.9e-7   8.0e-6
+    K3    lin        2.2e-7   1.9e-7   8.0e-6
+    K4    lmmse      9.0e-7   9.0e-7   8.0e-6
+    K4    lin        2.0e-7   1.7e-7   8.0e-6
+    K5    lmmse      1.5e-7   2.3e-7   8.0e-6
+    K5    lin        1.5e-7   1.5e-7   8.0e-6
+
+Covariance: every lag of K1 / K2 / K4 within N 2^-52 sf[0] of numpy float64 (N = products in the
+lag: the float64 summation bound); measured max |gpu - ref| / bound: K1 0.001, K2 0.004, K4 < 0.001.
+Quality: channel MSE at 5 dB nearest neighbour 0.157, linear 0.103, LMMSE 0.014.  Evaluation at
+10 dB, 2 PRB, 32 slots: BER perfect CSI 0.0167, lmmse_lmmse 0.0203, lslin_lmmse 0.0394, lsnn_lmmse
+0.0610 (NRX 0.0273); both inequalities of the issue hold with a wide margin and both are asserted.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+from tests import chest_ref as R
+
+pytestmark = pytest.mark.gpu
+
+NAMES = list(R.CASES)
+KINDS = ["lmmse", "lin"]
+
+
+def _params(name, num_active="case"):
+    from neural_rx_amd.generator import GenParams
+    U, A, F, dmrs, _, na = R.CASES[name]
+    return GenParams(num_tx=U, num_subcarriers=F, num_rx_ant=A, dmrs_symbols=dmrs,
+                     cdm_group=tuple(u % 2 for u in range(U)), num_active=na if num_active == "case" else num_active,
+                     seed=R.SEED)
+
+
+def _no(name):
+    from neural_rx_amd.generator import ebno_to_no
+    return ebno_to_no(R.EBNO_DB, len(R.CASES[name][3]))
+
+
+@functools.lru_cache(maxsize=None)
+def _slots(name, batch=None, offset=0):
+    """(device SlotBatch, host copies of h_hat / h / active), generated once"""
+    import torch
+    from neural_rx_amd.generator import SlotGenerator
+    sb = SlotGenerator(_params(name), want_h=True)(batch or R.CASES[name][4], _no(name), slot_offset=offset)
+    torch.cuda.synchronize()
+    g = {k: getattr(sb, k).cpu().numpy() for k in ("h_hat", "h", "active")}
+    for a in g.values():
+        a.setflags(write=False)
+    return sb, g
+
+
+@functools.lru_cache(maxsize=None)
+def _design(name):
+    from neural_rx_amd.chest import lmmse_design
+    p = _params(name)
+    return lmmse_design(*R.model_covariance(p.num_subcarriers), p, _no(name))
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name, kind):
+    """(float64 oracle, float32 floor) of a case, computed once and shared read-only"""
+    p = _params(name)
+    _, g = _slots(name)
+    if kind == "lmmse":
+        d = _design(name)
+        run = lambda dt: R.lmmse_apply(g["h_hat"], g["active"], d.filt, d.tcoef, d.vconj, p.dmrs_symbols,  # noqa: E731
+                                       p.cdm_group, dtype=dt)
+    else:
+        run = lambda dt: R.lin_interp(g["h_hat"], g["active"], p.dmrs_symbols, p.cdm_group, dtype=dt)  # noqa: E731
+    ref = run(np.float64)
+    floor = float(np.max(np.abs(run(np.float32) - ref) / np.maximum(1.0, np.abs(ref))))
+    ref.setflags(write=False)
+    return ref, floor
+
+
+def _estimator(name, kind):
+    from neural_rx_amd.chest import ChannelEstimator
+    return ChannelEstimator(kind, _params(name), tables=_design(name) if kind == "lmmse" else None)
+
+
+def _run(name, kind, sb=None, out=None):
+    import torch
+    h = _estimator(name, kind)(sb if sb is not None else _slots(name)[0], _no(name), out=out)
+    torch.cuda.synchronize()
+    return h
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("name", NAMES)
+def test_estimator_against_the_oracle(name, kind):
+    import torch
+    _, g = _slots(name)
+    ref, floor = _reference(name, kind)
+    # every element is written: the buffer starts as NaN
+    out = torch.full(ref.shape, float("nan"), dtype=torch.float32, device="cuda")
+    got = _run(name, kind, out=out).cpu().numpy()
+    assert np.isfinite(got).all()
+    gate = 8.0 * max(floor, 1e-6)
+    e = float(np.max(np.abs(got - ref) / np.maximum(1.0, np.abs(ref))))
+    print(f"{name} {kind}: floor {floor:.2e}  e {e:.2e}  gate {gate:.2e}  max|ref| {np.abs(ref).max():.2f}")
+    assert e <= gate, (name, kind, e, gate)
+    # inactive (b, u) planes are exactly 0
+    assert np.all(got[g["active"] <= 0] == 0.0)
+    if name == "K3":
+        assert (g["active"] <= 0).any() and (g["active"] > 0).any()
+    # determinism: a second call into a fresh buffer is bit-identical
+    again = _run(name, kind, out=torch.empty_like(out)).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), again.view(np.uint32))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("name", ["K1", "K3", "K4"])
+def test_slot_0_alone_is_bit_identical(name, kind):
+    """the estimate of a slot does not depend on the batch it is in"""
+    whole = _run(name, kind).cpu().numpy()
+    sb1, _ = _slots(name, batch=1)
+    alone = _run(name, kind, sb=sb1).cpu().numpy()
+    assert np.array_equal(whole[:1].view(np.uint32), alone.view(np.uint32))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_only_the_own_pilots_are_read(kind):
+    """NaN everywhere but the own pilots of h_hat: the estimate is unchanged"""
+    import dataclasses
+    import torch
+    name = "K1"
+    p = _params(name)
+    sb, _ = _slots(name)
+    masked = torch.full_like(sb.h_hat, float("nan"))
+    for u in range(p.num_tx):
+        for t in p.dmrs_symbols:
+            masked[:, u, p.cdm_group[u]::2, t] = sb.h_hat[:, u, p.cdm_group[u]::2, t]
+    got = _run(name, kind, sb=dataclasses.replace(sb, h_hat=masked)).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), _run(name, kind).cpu().numpy().view(np.uint32))
+
+
+def test_unaligned_output_takes_the_scalar_path():
+    import torch
+    for kind in KINDS:
+        ref, floor = _reference("K1", kind)
+        buf = torch.full((ref.size + 1,), float("nan"), dtype=torch.float32, device="cuda")
+        out = buf[1:].view(ref.shape)
+        assert out.data_ptr() % 16 == 4
+        got = _run("K1", kind, out=out).cpu().numpy()
+        e = float(np.max(np.abs(got - ref) / np.maximum(1.0, np.abs(ref))))
+        assert e <= 8.0 * max(floor, 1e-6), (kind, e)
+
+
+# ---- covariance --------------------------------------------------------------------------------
+
+def _cov(name, batches):
+    """lag sums (complex [F + 14]) of nrx_cov_accumulate over the given SlotBatches"""
+    import torch
+    from neural_rx_amd.chest import CovarianceEstimator
+    cov = CovarianceEstimator(_params(name))
+    for sb in batches:
+        cov.accumulate(sb)
+    torch.cuda.synchronize()
+    a = cov.acc.cpu().numpy()
+    return a[:, 0] + 1j * a[:, 1], cov
+
+
+@pytest.mark.parametrize("name", ["K1", "K2", "K4"])
+def test_covariance_lags(name):
+    U, A, F, _, B, _ = R.CASES[name]
+    sb, g = _slots(name)
+    got, cov = _cov(name, [sb])
+    sf, st = R.lag_sums(g["h"])
+    ref = np.concatenate([sf, st])
+    nf, nt = R.lag_counts(B, U, F, A)
+    bound = np.concatenate([nf, nt]) * 2.0 ** -52 * sf[0].real
+    ratio = np.abs(got - ref) / bound
+    print(f"{name}: cov max |gpu - ref| / (N 2^-52 sf[0]) = {ratio.max():.3f}")
+    assert np.all(ratio <= 1.0), (name, ratio.max())
+    # two calls give identical bits
+    again, _ = _cov(name, [sb])
+    assert np.array_equal(got.view(np.uint64), again.view(np.uint64))
+    # the matrices: Hermitian Toeplitz of the lag means
+    R_f, R_t = cov.matrices()
+    assert R_f.shape == (F, F) and R_t.shape == (14, 14) and np.array_equal(R_f, R_f.conj().T)
+    assert np.allclose(R_f[F - 1, 0], sf[F - 1] / nf[F - 1], rtol=1e-12, atol=1e-15)
+    assert np.allclose(R_t[13, 0], st[13] / nt[13], rtol=1e-12, atol=1e-15)
+    assert np.isclose(R_f[0, 0].real, R_t[0, 0].real, rtol=1e-12)
+
+
+@pytest.mark.parametrize("name", ["K1", "K2", "K4"])
+def test_covariance_accumulates_over_batches(name):
+    """two batches accumulated = one call on their concatenation, within the summation bound"""
+    import dataclasses
+    import torch
+    U, A, F, _, B, _ = R.CASES[name]
+    sb0, _ = _slots(name)
+    sb1, _ = _slots(name, batch=B, offset=B)
+    both = dataclasses.replace(sb0, h=torch.cat([sb0.h, sb1.h]).contiguous())
+    two, _ = _cov(name, [sb0, sb1])
+    one, _ = _cov(name, [both])
+    nf, nt = R.lag_counts(2 * B, U, F, A)
+    bound = np.concatenate([nf, nt]) * 2.0 ** -52 * one[0].real
+    assert np.all(np.abs(two - one) <= bound)
+
+
+# ---- estimate quality ----------------------------------------------------------------------------
+
+def test_lmmse_estimate_beats_nearest_neighbour():
+    """K1's geometry at 5 dB, 24 slots, covariance from 256 disjoint slots: the LMMSE estimate's MSE
+    against the true channel is below half the nearest-neighbour h_hat's (float64 CPU oracle: 0.013
+    against 0.154 -- a condition with a 6x margin, not a measurement)"""
+    import torch
+    from neural_rx_amd.chest import ChannelEstimator, estimate_covariance
+    from neural_rx_amd.generator import SlotGenerator
+    p, no = _params("K1"), _no("K1")
+    gen = SlotGenerator(p, want_h=True)
+    R_f, R_t = estimate_covariance(gen, 256, 128).matrices()
+    sb = gen(24, no, slot_offset=0)
+    mse = lambda x: float(((x - sb.h) ** 2).sum() / sb.h.shape[0] / p.num_tx / p.num_subcarriers / 14  # noqa: E731
+                          / p.num_rx_ant)
+    est = {k: mse(ChannelEstimator(k, p, R_f=R_f, R_t=R_t)(sb, no)) for k in KINDS}
+    nn = mse(sb.h_hat)
+    torch.cuda.synchronize()
+    print(f"channel MSE at 5 dB: nearest neighbour {nn:.4f}  linear {est['lin']:.4f}  lmmse {est['lmmse']:.4f}")
+    assert est["lmmse"] < 0.5 * nn
+    assert abs(R_f[0, 0].real - 1.0) < 0.1 and abs(R_t[0, 0].real - 1.0) < 0.1
+
+
+# ---- the evaluation's estimator legs -------------------------------------------------------------
+
+def test_evaluate_cli_estimator_baselines(capsys):
+    from neural_rx_amd import evaluate
+    names = ["lsnn_lmmse", "lmmse_lmmse", "lslin_lmmse", "perf_csi_lmmse"]
+    d = evaluate.main(["-config_name", "nrx_rt", "-num_tx_eval", "2", "-num_prbs", "2", "-ebno_db", "10",
+                       "-batch_size", "16", "-max_mc_iter", "2", "-num_cov_slots", "256", "-baselines"] + names)
+    assert list(d["baselines"]) == names and d["num_cov_slots"] == 256
+    ber = {}
+    for n in names:
+        r = d["baselines"][n]
+        assert r["mc_iters"] == [2] and r["counts"][0][1] == d["counts"][0][1]       # paired: the same bits
+        assert r["counts"][0][3] == d["counts"][0][3]
+        ber[n] = r["ber"][0]
+    text = capsys.readouterr().out
+    print("BER at 10 dB:", ber, " nrx", d["ber"][0])
+    assert ber["perf_csi_lmmse"] <= ber["lmmse_lmmse"] < ber["lsnn_lmmse"]
+    for n in names:
+        assert n + "  EbNo" in text
+    assert "pilot-contaminated" not in text
