@@ -66,13 +66,16 @@ enum nrx_precision {
 };
 
 /* Model topology.  Mirrors the [neural_receiver] block of the reference cfg
- * (config/nrx_rt.cfg:57-75) plus [system] num_rx_antennas / mcs_index. */
+ * (config/nrx_rt.cfg:57-75) plus [system] num_rx_antennas / mcs_index.  Everything nrx_create
+ * accepts runs every schedule of both precisions (tests/test_gpu_topologies.py: 1, 3, 4, 6, 8, 9
+ * antennas, 1..8 bits, 3 heads / 8 masked MCS, with and without h_hat, 1..16 users); a topology
+ * outside the ranges below is refused with NRX_ERR_UNSUPPORTED. */
 typedef struct nrx_desc {
-  int32_t num_rx_ant;        /* A (4 or 16) */
+  int32_t num_rx_ant;        /* A, 1..16 (odd A included) */
   int32_t d_s;               /* state width; kernels are built for 56 */
   int32_t num_it;            /* trained CGNN iterations (len(iterations)) */
-  int32_t num_mcs;           /* M = len(mcs_index), 1..8 */
-  int32_t bits[8];           /* bits per symbol of each MCS (2, 4 or 6) */
+  int32_t num_mcs;           /* M = len(mcs_index), 1..8 with var_mcs_masking, 1..3 without */
+  int32_t bits[8];           /* bits per symbol of each MCS, 1..8 */
   int32_t var_mcs_masking;   /* 1: one StateInit + one LLR head of max(bits), sliced */
   int32_t init_units[2];     /* num_units_init, kernels built for {128,128} */
   int32_t agg_units;         /* num_units_agg[i] = [64] */
@@ -83,7 +86,7 @@ typedef struct nrx_desc {
 
 typedef struct nrx_shape {
   int32_t batch;             /* B slots */
-  int32_t num_tx;            /* U users (DMRS ports) */
+  int32_t num_tx;            /* U users (DMRS ports), 1..16 */
   int32_t num_subcarriers;   /* F = 12 * PRBs */
   int32_t num_symbols;       /* T, must be 14 */
 } nrx_shape;

@@ -531,7 +531,8 @@ __device__ __forceinline__ void col_init_item(const BlockParams<P16>& prm, char*
   // first = m == 0), as the strip kernel's launches do; an item of weight 0 runs its math (0 *
   // finite: the same state bits as the strip kernel's skipped item)
   const int m = prm.m;
-  const float wm = a.masking ? 1.f : (a.mcs_mask ? a.mcs_mask[((size_t)b * a.U + u) * a.M + m] : 1.f);
+  // (no mask: one-hot on MCS 0, as the strip kernels take it)
+  const float wm = a.masking ? 1.f : (a.mcs_mask ? a.mcs_mask[((size_t)b * a.U + u) * a.M + m] : (m == 0 ? 1.f : 0.f));
   if constexpr (FIRST) {
     stage->store_w1(smem);   // the weights were loaded before the norm / z rows above; slot_norm's
     if (prm.norm_pre) __syncthreads();   // barrier (or this one) publishes them before conv1

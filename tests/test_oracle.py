@@ -174,3 +174,54 @@ def test_torch_cpu_restatement_matches_numpy_oracle(config, users, kw):
         assert r.shape == g.shape
         assert np.abs(r - g).max() < 2e-3
     assert np.abs(ref["h_hat"] - got["h_hat"]).max() < 1e-4
+
+
+def test_f16_rounded_oracle_identity_is_the_oracle():
+    # tests/f16_ref.py swaps the oracle's sepconv / dense for a rounding model: with the identity
+    # as the rounding and the oracle's tap order it is the oracle's own arithmetic, bit for bit
+    # (soft MCS mask, no h_hat, three heads, inactive users), and the swap is undone afterwards
+    from tests.f16_ref import f16_rounded_oracle, r16
+    from tests.helpers import compare
+    from tests.test_gpu_topologies import TOPOLOGIES, topo_case
+    t = TOPOLOGIES["a3_noh_3heads_u5"]
+    case = topo_case(t["spec"], 3, 12, 2, seed=5, mcs_mask="soft",
+                     active=np.array([[1, 0, 1], [0, 1, 0]], np.float32))
+    orig = cgnn_ref.sepconv, cgnn_ref.dense
+    ref = run_oracle(case)
+    same = f16_rounded_oracle(case, rnd=lambda x: x, dw_order="oracle")
+    assert (cgnn_ref.sepconv, cgnn_ref.dense) == orig
+    for a, b in zip(ref["llr"] + [ref["h_hat"]], same["llr"] + [same["h_hat"]]):
+        assert np.array_equal(a, b)
+    # the kernels' tap order only reorders an fp64 sum
+    reord = compare(ref, f16_rounded_oracle(case, rnd=lambda x: x))
+    assert reord["llr_maxabs"] < 1e-12 and reord["h_maxabs"] < 1e-12, reord
+    # and the f16 model moves the LLRs, but far less than the project's f16 gate allows
+    dev = compare(ref, f16_rounded_oracle(case, rnd=r16))
+    assert 0 < dev["llr_rel"] < 0.01 and 0 < dev["llr_rms_rel"] < 0.005, dev
+    with pytest.raises(KeyError):
+        f16_rounded_oracle(case, dw_order="nope")
+    assert (cgnn_ref.sepconv, cgnn_ref.dense) == orig
+
+
+def test_dispatch_model_matches_the_schedules_other_gpu_tests_assert():
+    # tests/test_gpu_topologies.py restates the f16 dispatcher; pinned here to what
+    # tests/test_gpu_col.py / test_gpu_fused.py observe on 256 CUs for nrx_rt
+    from tests.test_gpu_topologies import dispatch_model
+    spec = spec_from_config(get_config("nrx_rt"))
+    z = lambda **kw: {k: v for k, v in kw.items()}   # noqa: E731
+    pick = lambda n: {k: v for k, v in n.items() if v}   # noqa: E731
+    assert dispatch_model(spec, 2, 2, 48, 2, 29, 1, 256)[0] == "strips8"
+    tier, n = dispatch_model(spec, 128, 2, 48, 2, 4 | 8 | 16, 0, 256)
+    assert tier == "strips24" and pick(n) == z(state_init_col=1, state_update_col=2)
+    assert pick(dispatch_model(spec, 128, 2, 48, 2, 0, 0, 256)[1]) == z(state_init=1, state_update=2)
+    assert pick(dispatch_model(spec, 64, 2, 96, 2, 29, 0, 256)[1]) == \
+        z(state_init_col=1, state_update_rr=1, state_update=1)
+    assert pick(dispatch_model(spec, 64, 3, 48, 2, 4 | 8 | 16, 0, 256)[1]) == \
+        z(state_init_col=1, state_update_col=2, combine=2)
+    assert dispatch_model(spec, 128, 2, 48, 2, 4 | 8 | 16 | 32, 1, 256)[0] == "fwd_col"
+    assert dispatch_model(spec, 256, 2, 48, 2, 4 | 8 | 16 | 32, 1, 256)[0] == "strips24"
+    assert dispatch_model(spec, 128, 2, 48, 2, 29, 2, 256) == ("k_forward", dict(n, state_init_col=0,
+                                                                                 state_update_col=0, forward=1))
+    spec16 = spec_from_config(get_config("nrx_large"), 16)
+    assert pick(dispatch_model(spec16, 4, 2, 1584, 8, 4 | 8 | 16 | 64, 0, 256)[1]) == \
+        z(norm=1, state_init=1, state_update_col=8)
