@@ -314,6 +314,64 @@ typedef struct nrx_lmmse_io {
 
 int nrx_lmmse_detect(const nrx_lmmse_io* io, void* stream);
 
+/* ---------------------------------------------------------------- K-best detector
+ * Near-ML MIMO detection: the detector of the reference's baseline_lmmse_kbest /
+ * baseline_perf_csi_kbest systems (utils/baseline_rx.py:242-254, KBestDetector with k = 64).  The
+ * reference takes it from Sionna and holds no source of it, so the detector is defined here, and
+ * pinned by the exhaustive max-log ML detector where the two must coincide (tests/kbest_ref.py).
+ * Stated departures from Sionna's KBestDetector: a real-valued tree (2U levels of PAM) instead of
+ * a complex one, a scalar err_var, a Gram-Cholesky instead of a QR, and the ordering and clipping
+ * rules below.  Tensors and the LLR layout are those of nrx_lmmse_detect.
+ *
+ * Per data RE (b, f, t), with s = no + err_var:
+ *  1. streams: the n <= U users with active > 0, in port order.  User u has m_u =
+ *     mcs_bits[mcs[b][u]] bits of the Gray QAM of TS 38.211 5.1 (the generator's): even bits on the
+ *     real axis, odd bits on the imaginary axis, each axis a PAM of L_u = 2^(m_u / 2) levels.
+ *  2. real model: y_r = [Re y; Im y] in R^2A; user u has the columns [Re h_u; Im h_u] (for Re x_u)
+ *     and [-Im h_u; Re h_u] (for Im x_u).
+ *  3. order: users by |h_u|^2 ascending, ties to the lower u; real streams
+ *     [Re u(1), Im u(1), Re u(2), Im u(2), ...].  Detection runs from the last stream to the first.
+ *  4. G = H_pi^T H_pi (2n x 2n) = R^T R with R upper triangular and a positive diagonal,
+ *     y~ = R^-T H_pi^T y_r; no MMSE regularisation.  If a Cholesky pivot d_i <= 1e-6 G_ii, every
+ *     LLR of the RE is written 0 (the counterpart of the mu < 1e-6 rule of nrx_lmmse_detect).
+ *  5. search: one empty path of metric 0.  At level i = 2n-1 .. 0 every survivor expands into the L
+ *     children of that stream, child metric = parent metric + (y~_i - sum_{j>i} R_ij x_j - R_ii a)^2
+ *     / s; the k children with the smallest metric survive (all of them while there are at most k).
+ *     Children that tie exactly at the k-th place are resolved deterministically.
+ *  6. llr[u][q] = clip(min_{p: b_q(p) = 0} metric_p - min_{p: b_q(p) = 1} metric_p, +-llr_clip) over
+ *     the final list (Sionna sign, log p(1)/p(0)); a side without a path counts as +inf, so the
+ *     result is -+llr_clip.
+ * Entries q >= m_u, inactive users and DMRS symbols are written exactly 0; every element of llr is
+ * written on every call.  f32 arithmetic, no atomics, no allocation, no host synchronisation;
+ * asynchronous on `stream`; bit-identical from call to call and independent of how slots are split
+ * into batches.  The workspace (16-byte aligned, nrx_kbest_workspace_size bytes, monotone in B)
+ * holds the per-RE Gram matrices between the two kernels.  Every argument is checked before the
+ * first HIP call: a NULL io / y / h / active / llr / workspace / bytes, a workspace that is not
+ * 16-byte aligned, no <= 0, err_var < 0, llr_clip <= 0, k outside 1..64 or a bit width outside
+ * {2, 4, 6} is NRX_ERR_INVALID_ARG; T != 14, B outside 1..65535, F outside 1..3300, U < 1, A
+ * outside 1..16, num_mcs outside 1..8 or bits_stride < max(mcs_bits) is NRX_ERR_SHAPE; U > 8 is
+ * NRX_ERR_UNSUPPORTED; a workspace smaller than nrx_kbest_workspace_size is NRX_ERR_WORKSPACE. */
+typedef struct nrx_kbest_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B (1..65535), U (1..8), F (1..3300), T = 14 */
+  int32_t num_rx_ant;          /* A, 1..16 */
+  int32_t bits_stride;         /* last dim of llr, >= max(mcs_bits) */
+  int32_t num_mcs;             /* 1..8 */
+  int32_t mcs_bits[8];         /* 2, 4 or 6 */
+  int32_t dmrs_symbol_mask;    /* bit t set: symbol t carries no data, its LLRs are written 0 */
+  int32_t k;                   /* survivors per level, 1..64 */
+  double  no;                  /* noise variance per complex RE, > 0 */
+  double  err_var;             /* >= 0, added to no: channel-estimation error power (0 for perfect CSI) */
+  double  llr_clip;            /* > 0: LLRs are clipped to +-llr_clip */
+  const float*   y;            /* [B][F][T][2A]      nrx_io.y layout */
+  const float*   h;            /* [B][U][F][T][2A]   h_hat or the true h (nrx_gen_out layouts) */
+  const float*   active;       /* [B][U] */
+  const uint8_t* mcs;          /* [B][U] or NULL (= 0) */
+  float*         llr;          /* [1][B][U][F][T][bits_stride], Sionna sign log p(1)/p(0) */
+} nrx_kbest_io;
+
+int nrx_kbest_workspace_size(const nrx_kbest_io* io, size_t* bytes);
+int nrx_kbest_detect(const nrx_kbest_io* io, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- channel-estimation baselines
  * The estimators of the reference's baseline_lmmse_lmmse / baseline_lslin_lmmse systems
  * (utils/baseline_rx.py:100-229) and the statistics of its scripts/compute_cov_mat.py, for the

@@ -30,7 +30,7 @@ EXPORTS = [
     "nrx_llr_demap", "nrx_gen_workspace_size", "nrx_generate_slots", "nrx_count_errors",
     "nrx_workspace_size_ex", "nrx_forward_ex", "nrx_fused_status", "nrx_fused_config",
     "nrx_build_id", "nrx_update_schedule", "nrx_lmmse_detect", "nrx_cov_workspace_size", "nrx_cov_accumulate",
-    "nrx_chest_lmmse", "nrx_chest_lin",
+    "nrx_chest_lmmse", "nrx_chest_lin", "nrx_kbest_workspace_size", "nrx_kbest_detect",
 ]
 # enum nrx_y_layout
 Y_LAYOUTS = {"cgnn": 0, "sionna": 1, "split": 2}
@@ -193,6 +193,29 @@ class nrx_lmmse_io(ctypes.Structure):
     ]
 
 
+class nrx_kbest_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_rx_ant", ctypes.c_int32),
+        ("bits_stride", ctypes.c_int32),
+        ("num_mcs", ctypes.c_int32),
+        ("mcs_bits", ctypes.c_int32 * 8),
+        ("dmrs_symbol_mask", ctypes.c_int32),
+        ("k", ctypes.c_int32),
+        ("no", ctypes.c_double),
+        ("err_var", ctypes.c_double),
+        ("llr_clip", ctypes.c_double),
+        ("y", ctypes.c_void_p),
+        ("h", ctypes.c_void_p),
+        ("active", ctypes.c_void_p),
+        ("mcs", ctypes.c_void_p),
+        ("llr", ctypes.c_void_p),
+    ]
+
+
 class nrx_cov_io(ctypes.Structure):
     _fields_ = [
         ("batch", ctypes.c_int32),
@@ -297,6 +320,10 @@ def load(path: str = LIB_PATH):
     lib.nrx_count_errors.restype = c.c_int
     lib.nrx_lmmse_detect.argtypes = [P(nrx_lmmse_io), c.c_void_p]
     lib.nrx_lmmse_detect.restype = c.c_int
+    lib.nrx_kbest_workspace_size.argtypes = [P(nrx_kbest_io), P(c.c_size_t)]
+    lib.nrx_kbest_workspace_size.restype = c.c_int
+    lib.nrx_kbest_detect.argtypes = [P(nrx_kbest_io), c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.nrx_kbest_detect.restype = c.c_int
     lib.nrx_cov_workspace_size.argtypes = [P(nrx_cov_io), P(c.c_size_t)]
     lib.nrx_cov_workspace_size.restype = c.c_int
     lib.nrx_cov_accumulate.argtypes = [P(nrx_cov_io), c.c_void_p, c.c_size_t, c.c_void_p]

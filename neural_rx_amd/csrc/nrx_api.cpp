@@ -905,6 +905,51 @@ int nrx_lmmse_detect(const nrx_lmmse_io* io, void* stream) {
   return NRX_OK;
 }
 
+static int check_kbest(const nrx_kbest_io* io) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->y || !io->h || !io->active || !io->llr) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
+  if (!(io->err_var >= 0.0) || !std::isfinite(io->err_var))
+    return fail(NRX_ERR_INVALID_ARG, "err_var must be finite and >= 0");
+  if (!(io->llr_clip > 0.0) || !std::isfinite(io->llr_clip))
+    return fail(NRX_ERR_INVALID_ARG, "llr_clip must be finite and > 0");
+  if (io->k < 1 || io->k > 64) return fail(NRX_ERR_INVALID_ARG, "k must be 1..64");
+  if (io->num_mcs < 1 || io->num_mcs > 8) return fail(NRX_ERR_SHAPE, "num_mcs must be 1..8");
+  int bmax = 0;
+  for (int m = 0; m < io->num_mcs; ++m) {
+    if (io->mcs_bits[m] != 2 && io->mcs_bits[m] != 4 && io->mcs_bits[m] != 6)
+      return fail(NRX_ERR_INVALID_ARG, "mcs_bits must be 2, 4 or 6");
+    bmax = io->mcs_bits[m] > bmax ? io->mcs_bits[m] : bmax;
+  }
+  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
+  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
+  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
+  if (io->num_tx < 1) return fail(NRX_ERR_SHAPE, "num_tx must be >= 1");
+  if (io->num_tx > 8) return fail(NRX_ERR_UNSUPPORTED, "the K-best kernels are built for num_tx <= 8");
+  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
+  if (io->bits_stride < bmax) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
+  return NRX_OK;
+}
+
+int nrx_kbest_workspace_size(const nrx_kbest_io* io, size_t* bytes) {
+  if (int rc = check_kbest(io)) return rc;
+  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
+  *bytes = kbest_workspace_bytes(*io);
+  return NRX_OK;
+}
+
+int nrx_kbest_detect(const nrx_kbest_io* io, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_kbest(io)) return rc;
+  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
+  if ((uintptr_t)workspace & 15) return fail(NRX_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+  const size_t need = kbest_workspace_bytes(*io);
+  if (workspace_bytes < need)
+    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  hipError_t e = launch_kbest(*io, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "k-best detector launch");
+  return NRX_OK;
+}
+
 static int check_cov(const nrx_cov_io* io) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
   if (!io->h || !io->acc) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");

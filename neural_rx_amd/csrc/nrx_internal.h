@@ -173,6 +173,10 @@ hipError_t launch_count_errors(const nrx_count_io& c, hipStream_t st);
 // LMMSE + max-log baseline detector (nrx_lmmse.hip); io validated by nrx_lmmse_detect
 hipError_t launch_lmmse(const nrx_lmmse_io& io, hipStream_t st);
 
+// K-best detector (nrx_kbest.hip); io validated by the nrx_kbest_* entry points
+size_t kbest_workspace_bytes(const nrx_kbest_io& io);
+hipError_t launch_kbest(const nrx_kbest_io& io, void* ws, hipStream_t st);
+
 // Channel-estimation baselines (nrx_chest.hip); io validated by the nrx_cov_* / nrx_chest_* entry points
 size_t cov_workspace_bytes(const nrx_cov_io& io);
 hipError_t launch_cov_accumulate(const nrx_cov_io& io, void* ws, hipStream_t st);

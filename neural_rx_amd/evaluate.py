@@ -33,6 +33,7 @@ from .config import dmrs_symbols, get_config
 from .generator import GenParams, SlotGenerator, count_errors, ebno_to_no
 from .baseline import BaselineReceiver
 from .chest import COV_SLOT_OFFSET, EstimatorBaselineReceiver, estimate_covariance
+from .kbest import KBestBaselineReceiver
 from .receiver import CGNNEngine, compute_pe, spec_for
 
 
@@ -154,11 +155,12 @@ def sim_ber_baseline(receiver, gen: SlotGenerator, ebno_dbs: Sequence[float], ba
                      max_mc_iter: int = 100, num_target_block_errors: int = 100,
                      target_bler: Optional[float] = None, early_stop: bool = True, verbose: bool = False,
                      sync_every: int = 8, label: Optional[str] = None) -> SimResult:
-    """``sim_ber`` with a classical baseline (``baseline.BaselineReceiver``) in place of the
-    engine: the same loop on the same slots (``_mc_loop``), so a baseline curve and the NRX curve
-    of one generator are paired.  ``baseline_perf_csi_lmmse`` needs ``SlotGenerator(want_h=True)``."""
+    """``sim_ber`` with a classical baseline (``baseline.BaselineReceiver``,
+    ``chest.EstimatorBaselineReceiver``, ``kbest.KBestBaselineReceiver``) in place of the engine:
+    the same loop on the same slots (``_mc_loop``), so a baseline curve and the NRX curve of one
+    generator are paired.  The perfect-CSI systems need ``SlotGenerator(want_h=True)``."""
     if receiver.perfect_csi and not gen.want_h:
-        raise ValueError("baseline_perf_csi_lmmse needs SlotGenerator(want_h=True)")
+        raise ValueError("a perfect-CSI baseline needs SlotGenerator(want_h=True)")
     return _mc_loop(receiver, lambda: None, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors,
                     target_bler, early_stop, verbose, sync_every, label)
 
@@ -189,11 +191,14 @@ def main(argv=None):
     ap.add_argument("-gpu", type=int, default=None)
     ap.add_argument("-out", default=None, help="write the result JSON here")
     ap.add_argument("-baselines", nargs="*", default=[],
-                    choices=["lsnn_lmmse", "lslin_lmmse", "lmmse_lmmse", "perf_csi_lmmse"],
+                    choices=["lsnn_lmmse", "lslin_lmmse", "lmmse_lmmse", "perf_csi_lmmse", "lmmse_kbest",
+                             "perf_csi_kbest"],
                     help="classical baselines run on the same slots (baseline.BaselineReceiver, "
-                         "chest.EstimatorBaselineReceiver); the JSON gains \"baselines\": {name: result}")
+                         "chest.EstimatorBaselineReceiver, kbest.KBestBaselineReceiver); the JSON gains "
+                         "\"baselines\": {name: result}")
+    ap.add_argument("-kbest_k", type=int, default=64, help="survivors per level of the K-best baselines (1..64)")
     ap.add_argument("-num_cov_slots", type=int, default=2048,
-                    help="slots the covariance of lmmse_lmmse is estimated from (drawn at slot offset 2^40, "
+                    help="slots the covariance of lmmse_lmmse / lmmse_kbest is estimated from (drawn at slot offset 2^40, "
                          "disjoint from every Monte-Carlo slot)")
     a = ap.parse_args(argv)
 
@@ -214,20 +219,25 @@ def main(argv=None):
     params = GenParams.from_config(cfg, num_tx=u, num_prbs=a.num_prbs, var_mcs=a.var_mcs, seed=a.seed)
     params.num_active = a.num_tx_eval or u
     systems = {n: "baseline_" + n for n in a.baselines}
-    gen = SlotGenerator(params, device=device, want_h=bool({"perf_csi_lmmse", "lmmse_lmmse"} & set(systems)))
+    needs_h = {"perf_csi_lmmse", "lmmse_lmmse", "perf_csi_kbest", "lmmse_kbest"}
+    gen = SlotGenerator(params, device=device, want_h=bool(needs_h & set(systems)))
     ebno = a.ebno_db if a.ebno_db is not None else list(np.arange(-2.0, 8.0, 1.0))
     res = _sim_ber_nrx(engine, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors, a.target_bler,
                        True, cfg.num_nrx_iter_eval, a.precision, True, a.sync_every, "nrx" if systems else None)
     base = {}
     cov = None
-    if "lmmse_lmmse" in systems:
+    if {"lmmse_lmmse", "lmmse_kbest"} & set(systems):
         # the counterpart of compute_cov_mat.py before evaluate (scripts/evaluate.py:159); every rank
         # estimates the same matrices from the same slots
         if a.num_cov_slots < 1 or COV_SLOT_OFFSET <= len(ebno) * a.max_mc_iter * world * a.batch_size:
             raise ValueError("-num_cov_slots must be >= 1 and the Monte-Carlo slots must end below 2^40")
         cov = estimate_covariance(gen, a.num_cov_slots, a.batch_size).matrices()
     for name, system in systems.items():
-        if system in EstimatorBaselineReceiver.SYSTEMS:
+        if system in KBestBaselineReceiver.SYSTEMS:
+            rx = KBestBaselineReceiver(system, params, device=device, k=a.kbest_k)
+            if cov is not None:
+                rx.set_covariance(*cov)
+        elif system in EstimatorBaselineReceiver.SYSTEMS:
             # the filter is designed again at every Eb/N0 point (ChannelEstimator.prepare)
             rx = EstimatorBaselineReceiver(system, params, device=device)
             if cov is not None:
