@@ -448,6 +448,96 @@ typedef struct nrx_chest_io {
 int nrx_chest_lmmse(const nrx_chest_io* io, void* stream);
 int nrx_chest_lin(const nrx_chest_io* io, void* stream);
 
+/* ---------------------------------------------------------------- soft-output metrics
+ * What a decoder would see of the LLRs, and how good a channel estimate is: the sums behind the
+ * bitwise mutual information (BMI; Sionna's BitwiseMutualInformation, 1 - the binary cross-entropy
+ * the reference trains on, neural_rx.py:687, in bits) and behind the NMSE of a channel estimate (the
+ * reference's second loss, neural_rx.py:688).  There is no LDPC decoder here, so the BMI -- the rate
+ * a BICM decoder achieves with exactly these LLRs -- stands where the reference reports coded BLER.
+ *
+ * Contributing set: the one the error counters above count over -- (slot b, user u) with
+ * active[b][u] > 0, symbols t whose bit is not set in dmrs_symbol_mask, every subcarrier f, bit
+ * positions k < m with m = mcs_bits[mcs[b][u]] (MCS 0 when mcs == NULL; an index >= num_mcs is read as
+ * num_mcs - 1); the head is mcs[b][u] when num_heads > 1, else 0.  LLR sign: L = log p(1)/p(0).  An LLR
+ * equal to 0 in the set counts like any other: exclusion is by the masks, never by value.
+ *
+ * Loss of a contributing LLR L (f32) with sent bit c under scale s = scales[j]:
+ *   z = (2c - 1) s L                         formed in float64
+ *   loss_j = (max(-z, 0) + log1p(exp(-|z|))) / ln 2        bits
+ * The unbounded linear term max(-z, 0) is computed and summed in float64, so the accuracy of a mean
+ * does not depend on the size of the LLRs; the bounded term, in (0, ln 2], is the f32
+ * log1pf(expf(.)) of the f32-rounded -|z|, summed in float64.  An LLR that is NaN or +-inf adds 1 to
+ * nonfinite[u][mcs][k] and enters neither cnt nor any loss sum.
+ *
+ * Accumulators (device, owned and zeroed by the caller, only ever added to), M = num_mcs, S = num_scales:
+ *   loss      f64 [U][M][8][S]     sum of loss_j over the contributing finite LLRs of (u, mcs, k)
+ *   cnt       i64 [U][M][8]        their number
+ *   nonfinite i64 [U][M][8]
+ * On the host: bmi[m][k][j] = 1 - sum_u loss / sum_u cnt (it may be negative); the generalised mutual
+ * information is its maximum over j (neural_rx_amd/softmetrics.py).
+ *
+ * Two launches: a work item is (slot, user, strip of at most NRX_SOFT_STRIP subcarriers) -- the
+ * partition depends on the shape only -- and writes one partial record ([8][S] f64, two [8] i64) to the
+ * workspace after a fixed-order reduction (across the wave, then across the waves); items of inactive
+ * (slot, user) pairs exit after one load of active.  The second launch adds the partials of the active
+ * items into the accumulators in ascending (b, strip) order, one thread per (u, k, j).  No atomics: the
+ * same inputs give the same bits on every call.  No allocation, no host synchronisation; asynchronous on
+ * `stream`, capturable into a hipGraph.  Every argument is checked before the first HIP call: a NULL io /
+ * llr / bits / active / loss / cnt / nonfinite / workspace / bytes (mcs may be NULL), a workspace that is
+ * not 8-byte aligned, num_scales outside 1..16, a scale that is not finite or <= 0, a bit width outside
+ * 1..8 or a dmrs_symbol_mask outside 0..2^14 - 1 is NRX_ERR_INVALID_ARG; T != 14, B outside 1..65535,
+ * F outside 1..3300, U outside 1..16, num_mcs outside 1..8, num_heads not in {1, num_mcs} or bits_stride <
+ * max(mcs_bits) is NRX_ERR_SHAPE; a workspace smaller than nrx_llr_stats_workspace_size is
+ * NRX_ERR_WORKSPACE. */
+#define NRX_SOFT_STRIP 16
+typedef struct nrx_llr_stats_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B (1..65535), U (1..16), F (1..3300), T = 14 */
+  int32_t num_heads;           /* H heads in llr; head = mcs if H > 1 else 0 */
+  int32_t bits_stride;         /* last dim of llr and bits */
+  int32_t num_mcs;             /* M, 1..8 */
+  int32_t mcs_bits[8];         /* 1..8 */
+  int32_t dmrs_symbol_mask;
+  int32_t num_scales;          /* S, 1..16 */
+  int32_t pad_;
+  double  scales[16];          /* each finite and > 0 */
+  const float*   llr;          /* [H][B][U][F][T][bits_stride] (nrx_io.llr) */
+  const uint8_t* bits;         /* [B][U][F][T][bits_stride] */
+  const uint8_t* mcs;          /* [B][U] or NULL (= 0) */
+  const float*   active;       /* [B][U] */
+  double*  loss;               /* [U][M][8][S] accumulated */
+  int64_t* cnt;                /* [U][M][8] accumulated */
+  int64_t* nonfinite;          /* [U][M][8] accumulated */
+} nrx_llr_stats_io;
+
+int nrx_llr_stats_workspace_size(const nrx_llr_stats_io* io, size_t* bytes);
+int nrx_llr_stats(const nrx_llr_stats_io* io, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Squared-error sums of a channel estimate h_est against the true channel h_true, both
+ * [B][U][F][T][2A] f32 (nrx_gen_out.h_hat / .h layouts, nrx_io.h_ref): over the active (b, u), the
+ * symbols whose bit is set in symbol_mask (0: all 14), every f and all 2A components,
+ *   err[u] += sum (h_est - h_true)^2      (the difference formed in float64)
+ *   ref[u] += sum h_true^2
+ *   items[u] += 1 per active (b, u);      NMSE = sum_u err / sum_u ref.
+ * The same two launches, partition, workspace discipline and determinism as nrx_llr_stats.  A NULL io /
+ * h_est / h_true / active / err / ref / items / workspace / bytes, a workspace that is not 8-byte
+ * aligned or a symbol_mask outside 0..2^14 - 1 is NRX_ERR_INVALID_ARG; T != 14, B outside 1..65535, F
+ * outside 1..3300, U outside 1..16 or A outside 1..16 is NRX_ERR_SHAPE; a workspace smaller than
+ * nrx_nmse_workspace_size is NRX_ERR_WORKSPACE. */
+typedef struct nrx_nmse_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B, U (1..16), F (1..3300), T = 14 */
+  int32_t num_rx_ant;          /* A, 1..16 */
+  int32_t symbol_mask;         /* bit t set: symbol t is scored; 0 = all */
+  const float* h_est;          /* [B][U][F][T][2A] */
+  const float* h_true;         /* [B][U][F][T][2A] */
+  const float* active;         /* [B][U] */
+  double*  err;                /* [U] accumulated */
+  double*  ref;                /* [U] accumulated */
+  int64_t* items;              /* [U] accumulated */
+} nrx_nmse_io;
+
+int nrx_nmse_workspace_size(const nrx_nmse_io* io, size_t* bytes);
+int nrx_chest_nmse(const nrx_nmse_io* io, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Host helper: nearest-pilot positional encoding pe[U][F][T][2] for DMRS
  * configuration type 1 (restates onnx_utils.py:172-260 for the product path).
  * dmrs_symbols: the DMRS OFDM symbol indices; cdm_group[u] in {0,1}. */

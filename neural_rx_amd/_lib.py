@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("NRX_LIB_PATH") or os.path.join(LIB_DIR, "libnrx.so")
 
 NRX_OK = 0
 NRX_ERR_INVALID_ARG = -1
+NRX_ERR_WORKSPACE = -6
 NRX_ERR_BUSY = -7
 NRX_ERR_FUSED = -8
 NRX_PREC_F16 = 0
@@ -31,6 +32,7 @@ EXPORTS = [
     "nrx_workspace_size_ex", "nrx_forward_ex", "nrx_fused_status", "nrx_fused_config",
     "nrx_build_id", "nrx_update_schedule", "nrx_lmmse_detect", "nrx_cov_workspace_size", "nrx_cov_accumulate",
     "nrx_chest_lmmse", "nrx_chest_lin", "nrx_kbest_workspace_size", "nrx_kbest_detect",
+    "nrx_llr_stats_workspace_size", "nrx_llr_stats", "nrx_nmse_workspace_size", "nrx_chest_nmse",
 ]
 # enum nrx_y_layout
 Y_LAYOUTS = {"cgnn": 0, "sionna": 1, "split": 2}
@@ -249,6 +251,50 @@ class nrx_chest_io(ctypes.Structure):
     ]
 
 
+class nrx_llr_stats_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_heads", ctypes.c_int32),
+        ("bits_stride", ctypes.c_int32),
+        ("num_mcs", ctypes.c_int32),
+        ("mcs_bits", ctypes.c_int32 * 8),
+        ("dmrs_symbol_mask", ctypes.c_int32),
+        ("num_scales", ctypes.c_int32),
+        ("pad_", ctypes.c_int32),
+        ("scales", ctypes.c_double * 16),
+        ("llr", ctypes.c_void_p),
+        ("bits", ctypes.c_void_p),
+        ("mcs", ctypes.c_void_p),
+        ("active", ctypes.c_void_p),
+        ("loss", ctypes.c_void_p),
+        ("cnt", ctypes.c_void_p),
+        ("nonfinite", ctypes.c_void_p),
+    ]
+
+
+class nrx_nmse_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_rx_ant", ctypes.c_int32),
+        ("symbol_mask", ctypes.c_int32),
+        ("h_est", ctypes.c_void_p),
+        ("h_true", ctypes.c_void_p),
+        ("active", ctypes.c_void_p),
+        ("err", ctypes.c_void_p),
+        ("ref", ctypes.c_void_p),
+        ("items", ctypes.c_void_p),
+    ]
+
+
+# subcarriers per work item of nrx_llr_stats / nrx_chest_nmse (NRX_SOFT_STRIP of include/nrx.h)
+SOFT_STRIP = 16
+
 _lib = None
 
 
@@ -332,6 +378,14 @@ def load(path: str = LIB_PATH):
     lib.nrx_chest_lmmse.restype = c.c_int
     lib.nrx_chest_lin.argtypes = [P(nrx_chest_io), c.c_void_p]
     lib.nrx_chest_lin.restype = c.c_int
+    lib.nrx_llr_stats_workspace_size.argtypes = [P(nrx_llr_stats_io), P(c.c_size_t)]
+    lib.nrx_llr_stats_workspace_size.restype = c.c_int
+    lib.nrx_llr_stats.argtypes = [P(nrx_llr_stats_io), c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.nrx_llr_stats.restype = c.c_int
+    lib.nrx_nmse_workspace_size.argtypes = [P(nrx_nmse_io), P(c.c_size_t)]
+    lib.nrx_nmse_workspace_size.restype = c.c_int
+    lib.nrx_chest_nmse.argtypes = [P(nrx_nmse_io), c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.nrx_chest_nmse.restype = c.c_int
     lib.nrx_api_version.argtypes = []
     lib.nrx_api_version.restype = c.c_int32
     lib.nrx_update_schedule.argtypes = [c.c_void_p, c.c_int32]

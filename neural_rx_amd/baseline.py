@@ -107,6 +107,8 @@ class BaselineReceiver:
         self.perfect_csi = system == "baseline_perf_csi_lmmse"
         self.detector = LMMSEDetector(device)
         self._out = None
+        # the channel estimate the last call detected with (sb.h_hat); None with perfect CSI
+        self.last_h = None
 
     @property
     def contaminated(self) -> bool:
@@ -128,6 +130,7 @@ class BaselineReceiver:
         if h is None:
             raise ValueError("baseline_perf_csi_lmmse needs the true channel: SlotGenerator(want_h=True)"
                              if self.perfect_csi else "the slot batch has no h_hat")
+        self.last_h = None if self.perfect_csi else h
         if out is None:
             B = h.shape[0]
             if self._out is None or self._out.shape[1] != B:

@@ -297,6 +297,7 @@ class EstimatorBaselineReceiver:
                                           R_f=R_f, R_t=R_t)
         self.detector = LMMSEDetector(device)
         self._out = None
+        self.last_h = None      # the estimate the last call detected with
 
     def set_covariance(self, R_f, R_t) -> None:
         self.estimator.set_covariance(R_f, R_t)
@@ -322,7 +323,7 @@ class EstimatorBaselineReceiver:
     def __call__(self, sb: SlotBatch, no: float, out=None, stream=None):
         p = self.p
         ev = self.err_var(no)
-        h = self.estimator(sb, no, stream=stream)
+        h = self.last_h = self.estimator(sb, no, stream=stream)
         if out is None:
             B = h.shape[0]
             if self._out is None or self._out.shape[1] != B:

@@ -1015,6 +1015,83 @@ int nrx_chest_lin(const nrx_chest_io* io, void* stream) {
   return NRX_OK;
 }
 
+static int check_llr_stats(const nrx_llr_stats_io* io) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->llr || !io->bits || !io->active || !io->loss || !io->cnt || !io->nonfinite)
+    return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (io->num_scales < 1 || io->num_scales > 16) return fail(NRX_ERR_INVALID_ARG, "num_scales must be 1..16");
+  for (int s = 0; s < io->num_scales; ++s)
+    if (!(io->scales[s] > 0.0) || !std::isfinite(io->scales[s]))
+      return fail(NRX_ERR_INVALID_ARG, "scales must be finite and > 0");
+  if (io->dmrs_symbol_mask < 0 || io->dmrs_symbol_mask >= (1 << kT))
+    return fail(NRX_ERR_INVALID_ARG, "dmrs_symbol_mask must be a mask of the 14 symbols");
+  if (io->num_mcs < 1 || io->num_mcs > 8) return fail(NRX_ERR_SHAPE, "num_mcs must be 1..8");
+  int bmax = 0;
+  for (int m = 0; m < io->num_mcs; ++m) {
+    if (io->mcs_bits[m] < 1 || io->mcs_bits[m] > 8) return fail(NRX_ERR_INVALID_ARG, "mcs_bits must be 1..8");
+    bmax = io->mcs_bits[m] > bmax ? io->mcs_bits[m] : bmax;
+  }
+  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
+  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
+  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
+  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
+  if (io->num_heads != 1 && io->num_heads != io->num_mcs) return fail(NRX_ERR_SHAPE, "num_heads must be 1 or num_mcs");
+  if (io->bits_stride < bmax) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
+  return NRX_OK;
+}
+
+int nrx_llr_stats_workspace_size(const nrx_llr_stats_io* io, size_t* bytes) {
+  if (int rc = check_llr_stats(io)) return rc;
+  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
+  *bytes = llr_stats_workspace_bytes(*io);
+  return NRX_OK;
+}
+
+int nrx_llr_stats(const nrx_llr_stats_io* io, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_llr_stats(io)) return rc;
+  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
+  if ((uintptr_t)workspace & 7) return fail(NRX_ERR_INVALID_ARG, "workspace must be 8-byte aligned");
+  const size_t need = llr_stats_workspace_bytes(*io);
+  if (workspace_bytes < need)
+    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  hipError_t e = launch_llr_stats(*io, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "llr statistics launch");
+  return NRX_OK;
+}
+
+static int check_nmse(const nrx_nmse_io* io) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->h_est || !io->h_true || !io->active || !io->err || !io->ref || !io->items)
+    return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (io->symbol_mask < 0 || io->symbol_mask >= (1 << kT))
+    return fail(NRX_ERR_INVALID_ARG, "symbol_mask must be a mask of the 14 symbols");
+  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
+  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
+  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
+  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
+  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
+  return NRX_OK;
+}
+
+int nrx_nmse_workspace_size(const nrx_nmse_io* io, size_t* bytes) {
+  if (int rc = check_nmse(io)) return rc;
+  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
+  *bytes = nmse_workspace_bytes(*io);
+  return NRX_OK;
+}
+
+int nrx_chest_nmse(const nrx_nmse_io* io, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_nmse(io)) return rc;
+  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
+  if ((uintptr_t)workspace & 7) return fail(NRX_ERR_INVALID_ARG, "workspace must be 8-byte aligned");
+  const size_t need = nmse_workspace_bytes(*io);
+  if (workspace_bytes < need)
+    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  hipError_t e = launch_chest_nmse(*io, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "channel nmse launch");
+  return NRX_OK;
+}
+
 int nrx_profile_enable(nrx_handle* h, int32_t enable) {
   if (!h) return fail(NRX_ERR_INVALID_ARG, "null handle");
   if (enable) {

@@ -183,6 +183,13 @@ hipError_t launch_cov_accumulate(const nrx_cov_io& io, void* ws, hipStream_t st)
 hipError_t launch_chest_lmmse(const nrx_chest_io& io, hipStream_t st);
 hipError_t launch_chest_lin(const nrx_chest_io& io, hipStream_t st);
 
+// Soft-output metrics (nrx_softmetrics.hip); io validated by the nrx_llr_stats* / nrx_nmse* entry points
+constexpr int kSoftFS = NRX_SOFT_STRIP;   // subcarriers per work item
+size_t llr_stats_workspace_bytes(const nrx_llr_stats_io& io);
+hipError_t launch_llr_stats(const nrx_llr_stats_io& io, void* ws, hipStream_t st);
+size_t nmse_workspace_bytes(const nrx_nmse_io& io);
+hipError_t launch_chest_nmse(const nrx_nmse_io& io, void* ws, hipStream_t st);
+
 hipError_t launch_llr_demap(const float* llr, int B, int U, int F, int T, int bits_stride, int bits,
                             const int32_t* data_re, int n_data, float* out, hipStream_t st);
 

@@ -58,12 +58,20 @@ def _dist():
 
 def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int, max_mc_iter: int,
              num_target_block_errors: int, target_bler: Optional[float], early_stop: bool, verbose: bool,
-             sync_every: int, label: Optional[str] = None) -> SimResult:
+             sync_every: int, label: Optional[str] = None, soft: Optional[list] = None, soft_h=None,
+             soft_scales: Optional[Sequence[float]] = None) -> SimResult:
     """The Monte-Carlo loop shared by every system: ``step(sb, no) -> llr`` turns a generated batch
     into LLRs in the engine's layout, ``check()`` runs before every counter reduction.  Slot
     offsets, reductions and stopping rules do not depend on the system, so point k, iteration i
-    is the same slot for every receiver and their curves are paired."""
+    is the same slot for every receiver and their curves are paired.
+
+    ``soft``: a list that gains one ``softmetrics.SoftResult`` per Eb/N0 point -- the LLR statistics of
+    every batch and, when ``soft_h() -> h_est`` returns the channel estimate of the batch just
+    processed, its squared error against ``sb.h`` -- accumulated on the device and reduced over ranks
+    at the same windows as the counters.  Without it the loop does what it did before."""
     import torch
+    if soft is not None:
+        from .softmetrics import DEFAULT_SCALES, SoftAccumulator
     dist = _dist()
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
     # gloo (CPU tests, or ranks sharing one device) reduces host tensors; nccl = RCCL
@@ -78,12 +86,20 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
         no = ebno_to_no(float(ebno), len(p.dmrs_symbols))
         counts = torch.zeros((p.num_tx, 4), dtype=torch.int64, device=dev)
         total = np.zeros(4, np.int64)
+        acc = None
+        if soft is not None:
+            acc = SoftAccumulator(p.num_tx, p.mcs_bits, soft_scales or DEFAULT_SCALES, device=gen.device)
         it = 0
         while it < max_mc_iter:
             off = ((point_seed * max_mc_iter + it) * world + rank) * batch_size
             sb = gen(batch_size, no, slot_offset=off)
             llr = step(sb, no)
             count_errors(llr, sb.bits, sb.active, sb.mcs, p.mcs_bits, p.dmrs_symbols, counts=counts)
+            if acc is not None:
+                acc.add_llr(llr, sb.bits, sb.active, sb.mcs, p.dmrs_symbols)
+                h_est = soft_h() if soft_h is not None else None
+                if h_est is not None:
+                    acc.add_channel(h_est, sb.h, sb.active)
             it += 1
             if it % sync_every and it < max_mc_iter:
                 continue
@@ -94,6 +110,8 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
             if dist:
                 dist.all_reduce(tot)
             total = tot.cpu().numpy()
+            if acc is not None:
+                acc.reduce(dist)
             if total[2] >= num_target_block_errors:
                 break
         ber = total[0] / total[1] if total[1] else float("nan")
@@ -104,9 +122,14 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
         res.counts.append([int(v) for v in total])
         res.mc_iters.append(it)
         res.slots += it * batch_size * world
+        soft_txt = ""
+        if acc is not None:
+            sr = acc.result()
+            soft.append(sr)
+            soft_txt = "  " + soft_line(sr)
         if verbose and rank == 0:
             print(f"{label + '  ' if label else ''}EbNo {ebno:6.2f} dB  BER {ber:.4e}  BLER(uncoded) {bler:.4e}  "
-                  f"bit errors {total[0]}  blocks {total[3]}  iters {it}", flush=True)
+                  f"bit errors {total[0]}  blocks {total[3]}  iters {it}{soft_txt}", flush=True)
         point_seed += 1
         if early_stop and total[0] == 0:
             break
@@ -117,52 +140,99 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
     return res
 
 
+def soft_line(sr) -> str:
+    """``BMI .. GMI .. (x scale) NMSE ..`` of a ``SoftResult``, one BMI / GMI per MCS"""
+    f = lambda v: "-" if v is None or v != v else f"{v:.4f}"  # noqa: E731
+    txt = "BMI " + "/".join(f(v) for v in sr.bmi) + "  GMI " + "/".join(
+        f"{f(g)} (x{s:g})" if s == s else f(g) for g, s in zip(sr.gmi, sr.gmi_scale))
+    txt += "  NMSE " + ("-" if sr.nmse is None else f"{sr.nmse:.4e}")
+    if sr.nonfinite:
+        txt += f"  non-finite LLRs {sr.nonfinite}"
+    return txt
+
+
 def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int,
             max_mc_iter: int = 100, num_target_block_errors: int = 100, target_bler: Optional[float] = None,
             early_stop: bool = True, num_it: Optional[int] = None, precision: str = "f16",
-            verbose: bool = False, sync_every: int = 8) -> SimResult:
+            verbose: bool = False, sync_every: int = 8, soft: Optional[list] = None,
+            soft_scales: Optional[Sequence[float]] = None) -> SimResult:
     """Sionna ``sim_ber`` loop on the GPU (this rank's shard of every Monte-Carlo batch:
     global slot ``(it * world + rank) * batch_size + b``).  The counters are reduced
     over ranks (and copied to the host) every ``sync_every`` batches and at the end of a
-    point; every rank runs the same number of batches, so the collectives pair up."""
+    point; every rank runs the same number of batches, so the collectives pair up.
+
+    ``soft``: a list that gains one ``softmetrics.SoftResult`` per Eb/N0 point (BMI / GMI of the LLRs
+    at ``soft_scales``, NMSE of the refined estimate ``h_ref``).  The forward then also runs the ChEst
+    readout, and the generator needs ``want_h=True`` for the true channel.  The returned
+    ``SimResult`` is the one of a call without ``soft``."""
     return _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors, target_bler,
-                        early_stop, num_it, precision, verbose, sync_every, None)
+                        early_stop, num_it, precision, verbose, sync_every, None, soft, soft_scales)
 
 
 def _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors, target_bler,
-                 early_stop, num_it, precision, verbose, sync_every, label) -> SimResult:
+                 early_stop, num_it, precision, verbose, sync_every, label, soft=None, soft_scales=None) -> SimResult:
     """sim_ber; ``label`` prefixes the verbose lines (the CLI's runs with baselines)"""
     import torch
     p = gen.p
     dev = torch.device(f"cuda:{gen.device}")
+    want_h = soft is not None
+    if want_h and not gen.want_h:
+        raise ValueError("the NMSE of the soft metrics needs the true channel: SlotGenerator(want_h=True)")
     pe = torch.from_numpy(compute_pe(p.num_tx, p.num_subcarriers, p.dmrs_symbols, p.cdm_group)).to(dev)
     spec = engine.spec
-    llr_out = engine.alloc_outputs(batch_size, p.num_tx, p.num_subcarriers, want_h=False)
+    llr_out = engine.alloc_outputs(batch_size, p.num_tx, p.num_subcarriers, want_h=want_h)
+    last = {}
 
     def step(sb, no):
         mcs_mask = sb.mcs_mask if spec.num_mcs > 1 else None
-        llr, _ = engine.forward(sb.y, pe, sb.h_hat, sb.active, mcs_mask=mcs_mask, num_it=num_it,
-                                precision=precision, out=llr_out, want_h=False)
+        llr, last["h"] = engine.forward(sb.y, pe, sb.h_hat, sb.active, mcs_mask=mcs_mask, num_it=num_it,
+                                        precision=precision, out=llr_out, want_h=want_h)
         return llr
 
     # engine.check: the one-launch forward's error word -- a timed-out or incomplete forward raises
     # at the reduction instead of entering the counts (include/nrx.h nrx_fused_status)
     return _mc_loop(step, engine.check, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors,
-                    target_bler, early_stop, verbose, sync_every, label)
+                    target_bler, early_stop, verbose, sync_every, label, soft, lambda: last["h"], soft_scales)
 
 
 def sim_ber_baseline(receiver, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int,
                      max_mc_iter: int = 100, num_target_block_errors: int = 100,
                      target_bler: Optional[float] = None, early_stop: bool = True, verbose: bool = False,
-                     sync_every: int = 8, label: Optional[str] = None) -> SimResult:
+                     sync_every: int = 8, label: Optional[str] = None, soft: Optional[list] = None,
+                     soft_scales: Optional[Sequence[float]] = None) -> SimResult:
     """``sim_ber`` with a classical baseline (``baseline.BaselineReceiver``,
     ``chest.EstimatorBaselineReceiver``, ``kbest.KBestBaselineReceiver``) in place of the engine:
     the same loop on the same slots (``_mc_loop``), so a baseline curve and the NRX curve of one
-    generator are paired.  The perfect-CSI systems need ``SlotGenerator(want_h=True)``."""
+    generator are paired.  The perfect-CSI systems need ``SlotGenerator(want_h=True)``.
+
+    ``soft``: as in ``sim_ber``; the NMSE is the one of the estimate the receiver detected with
+    (``receiver.last_h``: ``sb.h_hat`` for the lsnn systems, the estimator's output for lslin / lmmse)
+    and None for the perfect-CSI systems.  With an estimate to score, the generator needs
+    ``want_h=True``."""
     if receiver.perfect_csi and not gen.want_h:
         raise ValueError("a perfect-CSI baseline needs SlotGenerator(want_h=True)")
+    soft_h = None
+    if soft is not None and not receiver.perfect_csi:
+        if not gen.want_h:
+            raise ValueError("the NMSE of the soft metrics needs the true channel: SlotGenerator(want_h=True)")
+        soft_h = lambda: receiver.last_h  # noqa: E731
     return _mc_loop(receiver, lambda: None, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors,
-                    target_bler, early_stop, verbose, sync_every, label)
+                    target_bler, early_stop, verbose, sync_every, label, soft, soft_h, soft_scales)
+
+
+def soft_dict(points, ebno_dbs: Sequence[float], code_rate: Optional[float] = None) -> dict:
+    """The CLI's ``"soft"`` entry of one system: its ``SoftResult`` per Eb/N0 point and, with a code
+    rate, the Eb/N0 at which the BMI and the GMI of each MCS reach it (``softmetrics.ebno_at_rate``;
+    None where they do not)."""
+    from .softmetrics import ebno_at_rate
+    d = {"points": [sr.as_dict() for sr in points]}
+    if code_rate is not None:
+        d["code_rate"] = code_rate
+        num_mcs = len(points[0].bmi) if points else 0
+        d["ebno_at_rate"] = {
+            key: [ebno_at_rate([(e, getattr(sr, key)[m]) for e, sr in zip(ebno_dbs, points)], code_rate)
+                  for m in range(num_mcs)] for key in ("bmi", "gmi")}
+    return d
 
 
 def baseline_note(name: str, receiver) -> Optional[str]:
@@ -200,6 +270,14 @@ def main(argv=None):
     ap.add_argument("-num_cov_slots", type=int, default=2048,
                     help="slots the covariance of lmmse_lmmse / lmmse_kbest is estimated from (drawn at slot offset 2^40, "
                          "disjoint from every Monte-Carlo slot)")
+    ap.add_argument("-soft_metrics", action="store_true",
+                    help="also accumulate the soft-output metrics (softmetrics.py): BMI / GMI of every system's "
+                         "LLRs and the NMSE of its channel estimate; the JSON gains \"soft\" (per point) next to "
+                         "every result")
+    ap.add_argument("-llr_scales", type=float, nargs="+", default=None,
+                    help="LLR scale factors the GMI is searched over (1..16 positive numbers)")
+    ap.add_argument("-code_rate", type=float, default=None,
+                    help="with -soft_metrics: report the Eb/N0 at which BMI and GMI reach this rate")
     a = ap.parse_args(argv)
 
     import torch
@@ -220,10 +298,12 @@ def main(argv=None):
     params.num_active = a.num_tx_eval or u
     systems = {n: "baseline_" + n for n in a.baselines}
     needs_h = {"perf_csi_lmmse", "lmmse_lmmse", "perf_csi_kbest", "lmmse_kbest"}
-    gen = SlotGenerator(params, device=device, want_h=bool(needs_h & set(systems)))
+    gen = SlotGenerator(params, device=device, want_h=bool(needs_h & set(systems)) or a.soft_metrics)
     ebno = a.ebno_db if a.ebno_db is not None else list(np.arange(-2.0, 8.0, 1.0))
+    soft = {"nrx": []} if a.soft_metrics else {}
     res = _sim_ber_nrx(engine, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors, a.target_bler,
-                       True, cfg.num_nrx_iter_eval, a.precision, True, a.sync_every, "nrx" if systems else None)
+                       True, cfg.num_nrx_iter_eval, a.precision, True, a.sync_every, "nrx" if systems else None,
+                       soft.get("nrx"), a.llr_scales)
     base = {}
     cov = None
     if {"lmmse_lmmse", "lmmse_kbest"} & set(systems):
@@ -247,8 +327,11 @@ def main(argv=None):
         note = baseline_note(name, rx)
         if note and rank == 0:
             print(note, flush=True)
+        if a.soft_metrics:
+            soft[name] = []
         base[name] = sim_ber_baseline(rx, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors,
-                                      a.target_bler, verbose=True, sync_every=a.sync_every, label=name)
+                                      a.target_bler, verbose=True, sync_every=a.sync_every, label=name,
+                                      soft=soft.get(name), soft_scales=a.llr_scales)
     d = None
     if rank == 0:
         d = res.as_dict()
@@ -256,6 +339,12 @@ def main(argv=None):
                  world=world, slots_per_s=res.slots / res.seconds)
         if base:
             d["baselines"] = {name: r.as_dict() for name, r in base.items()}
+        for name, points in soft.items():
+            sd = soft_dict(points, (res if name == "nrx" else base[name]).ebno_db, a.code_rate)
+            if rank == 0 and a.code_rate is not None:
+                print(f"{name}  Eb/N0 at rate {a.code_rate:g}: BMI {sd['ebno_at_rate']['bmi']}  "
+                      f"GMI {sd['ebno_at_rate']['gmi']}", flush=True)
+            (d if name == "nrx" else d["baselines"][name])["soft"] = sd
         if cov is not None:
             d["num_cov_slots"] = a.num_cov_slots
         print(json.dumps(d))

@@ -117,6 +117,7 @@ class KBestBaselineReceiver:
             EstimatorBaselineReceiver("baseline_lmmse_lmmse", params, device, R_f=R_f, R_t=R_t)
         self.detector = KBestDetector(device)
         self._out = None
+        self.last_h = None      # the estimate the last call detected with; None with perfect CSI
 
     def set_covariance(self, R_f, R_t) -> None:
         if self._est is not None:
@@ -138,7 +139,7 @@ class KBestBaselineReceiver:
                 raise ValueError("baseline_perf_csi_kbest needs the true channel: SlotGenerator(want_h=True)")
         else:
             ev = self._est.err_var(no)
-            h = self._est.estimator(sb, no, stream=stream)
+            h = self.last_h = self._est.estimator(sb, no, stream=stream)
         if out is None:
             B = h.shape[0]
             if self._out is None or self._out.shape[1] != B:
