@@ -255,6 +255,33 @@ int nrx_gen_workspace_size(const nrx_gen_desc* desc, size_t* bytes);
 int nrx_generate_slots(const nrx_gen_desc* desc, const nrx_gen_out* out, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* Per-user channel profiles and receive-antenna correlation: the parts of the reference's
+ * evaluation channel that its own text defines (utils/channel_models.py:39-161, "DoubleTDL":
+ * every user its own delay spread and Doppler; gnb_correlation_matrix, 20-33).  The 3GPP tap
+ * tables are not reconstructed: the taps stay the generator's random ones.
+ *   - port u draws its delays and its PDP constant from max_delay_s[u] and its Doppler
+ *     frequencies from max_doppler_hz[u]; the scalars of nrx_gen_desc are not read.  The Philox
+ *     streams and counters are those of nrx_generate_slots.
+ *   - rx_mix = M mixes the finished taps (PDP scaling included) over the antennas,
+ *     g'[a] = sum_a' M[a][a'] g[a'] in complex f64 with a' ascending, in place in the workspace
+ *     (nrx_gen_workspace_size is unchanged), so the taps have the spatial covariance M M^H and
+ *     h, y, h_hat and the Aerial outputs all follow from the mixed taps.  The host side
+ *     (neural_rx_amd/generator.py) passes the Hermitian square root of a correlation matrix.
+ * chan == NULL is exactly nrx_generate_slots; a chan whose first U entries equal the desc's
+ * scalars with rx_mix == NULL gives bit-identical outputs to it.  Entries of ports >= U are not
+ * read.  Slot slot_offset + b stays a pure function of the global slot index.  A negative or
+ * non-finite spread of a port < U, or an rx_mix that is not 8-byte aligned, is
+ * NRX_ERR_INVALID_ARG; the other checks are those of
+ * nrx_generate_slots, and all are made before the first HIP call. */
+typedef struct nrx_gen_chan {
+  double max_delay_s[16];      /* per port, >= 0, replaces nrx_gen_desc.max_delay_s for that port */
+  double max_doppler_hz[16];   /* per port, >= 0, replaces nrx_gen_desc.max_doppler_hz */
+  const double* rx_mix;        /* device, [A][A][2] (re, im), row-major M; NULL = identity */
+} nrx_gen_chan;
+
+int nrx_generate_slots_ex(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_out* out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Uncoded error counters of one batch (sim_ber's counting, scripts/evaluate.py:193-202,
  * with the active-port masking of E2E_Model._mask_active_dmrs, e2e_model.py:195-209):
  * counts[u][0..3] += (bit errors, bits, block errors, blocks) over the active (slot, user)
@@ -403,6 +430,27 @@ typedef struct nrx_cov_io {
 int nrx_cov_workspace_size(const nrx_cov_io* io, size_t* bytes);
 int nrx_cov_accumulate(const nrx_cov_io* io, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Spatial covariance sums of the true channel, the third matrix of compute_cov_mat.py, for a
+ * generator with receive-antenna correlation (nrx_gen_chan.rx_mix), over all (b, u) planes:
+ *   acc[a][a'] += sum_{b,u,f,t} h[a] conj(h[a'])
+ * acc is a device array double[A][A][2] (re, im) that the caller zeroes once; every call adds to
+ * it.  The caller divides by B U F 14.  As in the reference there is one R_s (and one R_f, R_t)
+ * for all users: the mixture over the users' profiles.  Same discipline as the lag sums: f64
+ * products and sums, a fixed number of per-workgroup partials in the workspace, then one ordered
+ * reduction, no atomics, the same bits on every call.  Asynchronous on `stream`.  Error codes
+ * and shape limits are those of nrx_cov_accumulate, checked before the first HIP call. */
+typedef struct nrx_cov_space_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B, U (1..16), F (1..3300), T = 14 */
+  int32_t num_rx_ant;          /* A, 1..16 */
+  int32_t pad_;
+  const float* h;              /* [B][U][F][T][2A] */
+  double*      acc;            /* [A][A][2], accumulated */
+} nrx_cov_space_io;
+
+int nrx_cov_space_workspace_size(const nrx_cov_space_io* io, size_t* bytes);
+int nrx_cov_space_accumulate(const nrx_cov_space_io* io, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* Channel estimators on the LS estimates at the own pilots.  Both read only the own-pilot REs of
  * h_hat (subcarriers f with f mod 2 = cdm_group[u] on the DMRS symbols; the generator's
  * nearest-neighbour h_hat holds the LS estimate there) and write every element of h_out
@@ -447,6 +495,54 @@ typedef struct nrx_chest_io {
 
 int nrx_chest_lmmse(const nrx_chest_io* io, void* stream);
 int nrx_chest_lin(const nrx_chest_io* io, void* stream);
+
+/* nrx_chest_lmmse3: the exact Wiener filter under the covariance R_s (x) R_t (x) R_f with white LS
+ * noise sigma^2 = no / 2 -- the "s" stage of the reference's order "s-f-t" (utils/baseline_rx.py:
+ * 160-195) included, for a generator with receive-antenna correlation.  It is diagonal in the three
+ * eigenbases.  Host design, once per covariance (chest.lmmse3_design):
+ *   R_s = V_s diag(mu) V_s^H (trace A),  R_t[D, D] = V_t diag(lambda) V_t^H (R_t of unit diagonal),
+ *   R_f[P_g, P_g] = Q_g diag(nu_g) Q_g^H per CDM group g,  G_g = R_f[:, P_g] Q_g,
+ *   tcoef[k][t] = (R_t[:, D] v_k)[t]   (not divided by lambda_k, unlike nrx_chest_lmmse's)
+ * and per (b, u), g = cdm_group[u]:
+ *   w[j,k,q] = sum_a conj(V_s[a][j]) sum_d conj(V_t[d][k]) sum_p conj(Q_g[p][q]) h_ls[a, P_p, D_d]
+ *   c[j,k,q] = mu_j / (mu_j lambda_k nu_q + sigma^2) w[j,k,q]
+ *   h^[a,f,t] = sum_j V_s[a][j] sum_k tcoef[k][t] sum_q G_g[f][q] c[j,k,q]
+ * No eigenvalue is inverted, so nothing is dropped or ill-conditioned, and the tables do not depend
+ * on no.  With R_s = I the estimate equals nrx_chest_lmmse's.  Tables, f32 device arrays with
+ * Pmax = (F + 1) / 2, zero-padded where a group has fewer than Pmax pilots:
+ *   qh [2][Pmax][Pmax][2]  rows of Q_g^H: qh[g][q][p] = conj(Q_g[p][q]);   gf [2][F][Pmax][2] = G_g
+ *   nu [2][Pmax];  tcoef [nd][14][2];  vconj [nd][nd][2] = conj(v_k[d]);  lam [nd]
+ *   vs [A][A][2] = V_s[a][j];  mu [A]
+ * qh and gf 8-byte aligned.  Both matrix products run on the exact-f32 MFMA
+ * (v_mfma_f32_16x16x4_f32); the workspace (nrx_chest3_workspace_size bytes, monotone in B) holds c,
+ * rotated back to antennas, between the two kernels.  Guarantees and error codes are those of
+ * nrx_chest_lmmse (every element of h_out written, zeros for inactive users and users without a
+ * pilot, f32, no atomics, independent of the batch split, asynchronous on `stream`, every argument
+ * checked before the first HIP call), and a NULL or not 4-byte aligned workspace or a NULL bytes is
+ * NRX_ERR_INVALID_ARG, a workspace smaller than nrx_chest3_workspace_size NRX_ERR_WORKSPACE.
+ * nrx_chest3_workspace_size reads only the shape fields. */
+typedef struct nrx_chest3_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B, U (1..16), F (1..3300), T = 14 */
+  int32_t num_rx_ant;          /* A, 1..16 */
+  int32_t num_dmrs_symbols;    /* nd, 1..4 */
+  int32_t dmrs_symbols[4];     /* ascending */
+  int32_t cdm_group[16];       /* per port, 0/1 */
+  double  no;                  /* noise variance per complex RE the estimate is made at, > 0 */
+  const float* h_hat;          /* [B][U][F][T][2A], read at the own pilots only */
+  const float* active;         /* [B][U] */
+  const float* qh;             /* [2][Pmax][Pmax][2] */
+  const float* gf;             /* [2][F][Pmax][2] */
+  const float* nu;             /* [2][Pmax] */
+  const float* tcoef;          /* [nd][14][2] */
+  const float* vconj;          /* [nd][nd][2] */
+  const float* lam;            /* [nd] */
+  const float* vs;             /* [A][A][2] */
+  const float* mu;             /* [A] */
+  float*       h_out;          /* [B][U][F][T][2A] */
+} nrx_chest3_io;
+
+int nrx_chest3_workspace_size(const nrx_chest3_io* io, size_t* bytes);
+int nrx_chest_lmmse3(const nrx_chest3_io* io, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- soft-output metrics
  * What a decoder would see of the LLRs, and how good a channel estimate is: the sums behind the

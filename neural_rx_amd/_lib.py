@@ -33,6 +33,8 @@ EXPORTS = [
     "nrx_build_id", "nrx_update_schedule", "nrx_lmmse_detect", "nrx_cov_workspace_size", "nrx_cov_accumulate",
     "nrx_chest_lmmse", "nrx_chest_lin", "nrx_kbest_workspace_size", "nrx_kbest_detect",
     "nrx_llr_stats_workspace_size", "nrx_llr_stats", "nrx_nmse_workspace_size", "nrx_chest_nmse",
+    "nrx_generate_slots_ex", "nrx_cov_space_workspace_size", "nrx_cov_space_accumulate",
+    "nrx_chest3_workspace_size", "nrx_chest_lmmse3",
 ]
 # enum nrx_y_layout
 Y_LAYOUTS = {"cgnn": 0, "sionna": 1, "split": 2}
@@ -154,6 +156,14 @@ class nrx_gen_out(ctypes.Structure):
     ]
 
 
+class nrx_gen_chan(ctypes.Structure):
+    _fields_ = [
+        ("max_delay_s", ctypes.c_double * 16),
+        ("max_doppler_hz", ctypes.c_double * 16),
+        ("rx_mix", ctypes.c_void_p),
+    ]
+
+
 class nrx_count_io(ctypes.Structure):
     _fields_ = [
         ("batch", ctypes.c_int32),
@@ -231,6 +241,19 @@ class nrx_cov_io(ctypes.Structure):
     ]
 
 
+class nrx_cov_space_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_rx_ant", ctypes.c_int32),
+        ("pad_", ctypes.c_int32),
+        ("h", ctypes.c_void_p),
+        ("acc", ctypes.c_void_p),
+    ]
+
+
 class nrx_chest_io(ctypes.Structure):
     _fields_ = [
         ("batch", ctypes.c_int32),
@@ -247,6 +270,31 @@ class nrx_chest_io(ctypes.Structure):
         ("filt", ctypes.c_void_p),
         ("tcoef", ctypes.c_void_p),
         ("vconj", ctypes.c_void_p),
+        ("h_out", ctypes.c_void_p),
+    ]
+
+
+class nrx_chest3_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_rx_ant", ctypes.c_int32),
+        ("num_dmrs_symbols", ctypes.c_int32),
+        ("dmrs_symbols", ctypes.c_int32 * 4),
+        ("cdm_group", ctypes.c_int32 * 16),
+        ("no", ctypes.c_double),
+        ("h_hat", ctypes.c_void_p),
+        ("active", ctypes.c_void_p),
+        ("qh", ctypes.c_void_p),
+        ("gf", ctypes.c_void_p),
+        ("nu", ctypes.c_void_p),
+        ("tcoef", ctypes.c_void_p),
+        ("vconj", ctypes.c_void_p),
+        ("lam", ctypes.c_void_p),
+        ("vs", ctypes.c_void_p),
+        ("mu", ctypes.c_void_p),
         ("h_out", ctypes.c_void_p),
     ]
 
@@ -362,6 +410,13 @@ def load(path: str = LIB_PATH):
     lib.nrx_gen_workspace_size.restype = c.c_int
     lib.nrx_generate_slots.argtypes = [P(nrx_gen_desc), P(nrx_gen_out), c.c_void_p, c.c_size_t, c.c_void_p]
     lib.nrx_generate_slots.restype = c.c_int
+    lib.nrx_generate_slots_ex.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_out), c.c_void_p, c.c_size_t,
+                                          c.c_void_p]
+    lib.nrx_generate_slots_ex.restype = c.c_int
+    lib.nrx_cov_space_workspace_size.argtypes = [P(nrx_cov_space_io), P(c.c_size_t)]
+    lib.nrx_cov_space_workspace_size.restype = c.c_int
+    lib.nrx_cov_space_accumulate.argtypes = [P(nrx_cov_space_io), c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.nrx_cov_space_accumulate.restype = c.c_int
     lib.nrx_count_errors.argtypes = [P(nrx_count_io), c.c_void_p]
     lib.nrx_count_errors.restype = c.c_int
     lib.nrx_lmmse_detect.argtypes = [P(nrx_lmmse_io), c.c_void_p]
@@ -378,6 +433,10 @@ def load(path: str = LIB_PATH):
     lib.nrx_chest_lmmse.restype = c.c_int
     lib.nrx_chest_lin.argtypes = [P(nrx_chest_io), c.c_void_p]
     lib.nrx_chest_lin.restype = c.c_int
+    lib.nrx_chest3_workspace_size.argtypes = [P(nrx_chest3_io), P(c.c_size_t)]
+    lib.nrx_chest3_workspace_size.restype = c.c_int
+    lib.nrx_chest_lmmse3.argtypes = [P(nrx_chest3_io), c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.nrx_chest_lmmse3.restype = c.c_int
     lib.nrx_llr_stats_workspace_size.argtypes = [P(nrx_llr_stats_io), P(c.c_size_t)]
     lib.nrx_llr_stats_workspace_size.restype = c.c_int
     lib.nrx_llr_stats.argtypes = [P(nrx_llr_stats_io), c.c_void_p, c.c_size_t, c.c_void_p]

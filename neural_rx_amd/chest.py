@@ -3,8 +3,8 @@
 The counterpart of the estimators of the reference's ``BaselineReceiver`` (utils/baseline_rx.py:
 100-229) for ``baseline_lmmse_lmmse`` and ``baseline_lslin_lmmse``, and of its
 ``scripts/compute_cov_mat.py`` (which ``scripts/evaluate.py:159`` runs before every baseline
-evaluation).  The device work is in ``libnrx.so`` (``nrx_cov_accumulate``, ``nrx_chest_lmmse``,
-``nrx_chest_lin``: include/nrx.h, csrc/nrx_chest.hip); torch tensors are only device containers and
+evaluation).  The device work is in ``libnrx.so`` (``nrx_cov_accumulate``, ``nrx_cov_space_accumulate``,
+``nrx_chest_lmmse``, ``nrx_chest_lmmse3``, ``nrx_chest_lin``: include/nrx.h, csrc/nrx_chest.hip); torch tensors are only device containers and
 a missing library is an error, never a host fallback.  The filter design is host numpy float64, run
 once per noise level: it is not hot.
 
@@ -13,9 +13,15 @@ Three stated departures from the reference (Sionna):
 * **Toeplitz covariance.**  ``CovarianceEstimator`` estimates lags, not full matrices: the
   generator's channel is stationary in frequency and time by construction (oracle/synth_ref.py:
   206-226), so ``R_f`` and ``R_t`` are Hermitian Toeplitz and the lags estimate the same quantity
-  with less variance and O(F) storage.  The spatial covariance is the identity -- the taps are drawn
-  i.i.d. per antenna (synth_ref.py:213-217) -- so the ``s`` stage of the reference's order
-  ``"s-f-t"`` is a no-op here and is left out.
+  with less variance and O(F) storage.  On the default channel the spatial covariance is the
+  identity -- the taps are drawn i.i.d. per antenna (synth_ref.py:213-217) -- so the ``s`` stage of
+  the reference's order ``"s-f-t"`` is a no-op there and ``"lmmse"`` leaves it out.  With
+  receive-antenna correlation (``GenParams.rx_corr``, ``generator.scenario``) it is not:
+  ``CovarianceEstimator.space()`` estimates ``R_s`` and ``"lmmse3"`` (``lmmse3_design``,
+  ``nrx_chest_lmmse3``) is the exact filter under ``R_s (x) R_t (x) R_f``, the counterpart of the
+  covariance the reference hands to its estimator (utils/baseline_rx.py:160-195).  As in the
+  reference there is one ``R_f``, ``R_t``, ``R_s`` for all users -- with per-user profiles, the
+  mixture over them; per-user covariances are out of scope.
 * **Exact 2-D filter.**  Sionna's ``LMMSEInterpolator`` filters sequentially ("f-t"), which
   approximates the 2-D Wiener filter.  Here the estimate is the exact filter under the separable
   covariance ``R_t (x) R_f``, in an eigen form of ``R_t[D, D]`` that costs ``nd`` frequency GEMMs
@@ -39,7 +45,7 @@ from .baseline import MAX_TX, LMMSEDetector
 from .generator import NUM_SYMBOLS, GenParams, SlotBatch
 
 SYSTEMS = ("baseline_lslin_lmmse", "baseline_lmmse_lmmse")
-KINDS = ("lin", "lmmse")
+KINDS = ("lin", "lmmse", "lmmse3")
 COV_SLOT_OFFSET = 1 << 40        # covariance slots start here: disjoint from every Monte-Carlo offset
 
 
@@ -64,8 +70,10 @@ class CovarianceEstimator:
     """Frequency and time covariance of the generator's channel from its true ``h``
     (``SlotGenerator(want_h=True)``): ``accumulate(sb)`` adds a batch's lag sums on the device
     (``nrx_cov_accumulate``, float64, deterministic), ``matrices()`` divides by the product counts
-    and returns the Hermitian Toeplitz ``(R_f [F, F], R_t [14, 14])`` as numpy complex128.  The
-    spatial covariance is the identity (module docstring), so there is no ``R_s``."""
+    and returns the Hermitian Toeplitz ``(R_f [F, F], R_t [14, 14])`` as numpy complex128.
+    ``accumulate`` also adds the spatial sums (``nrx_cov_space_accumulate``); ``space()`` returns
+    ``R_s [A, A]``, the identity up to estimation noise unless the generator correlates its
+    antennas (module docstring)."""
 
     def __init__(self, params: GenParams, device: int = 0):
         torch = _torch()
@@ -74,8 +82,11 @@ class CovarianceEstimator:
         self._lib = _lib.load()
         self.acc = torch.zeros((params.num_subcarriers + NUM_SYMBOLS, 2), dtype=torch.float64,
                                device=f"cuda:{device}")
+        self.acc_s = torch.zeros((params.num_rx_ant, params.num_rx_ant, 2), dtype=torch.float64,
+                                 device=f"cuda:{device}")
         self.slots = 0
         self._ws = None
+        self._ws_s = None
 
     def accumulate(self, sb: SlotBatch, stream=None) -> None:
         torch = _torch()
@@ -98,6 +109,15 @@ class CovarianceEstimator:
         if stream is None:
             stream = torch.cuda.current_stream(self.acc.device).cuda_stream
         _lib.check(self._lib.nrx_cov_accumulate(ctypes.byref(io), self._ws.data_ptr(), self._ws.numel(), stream))
+        so = _lib.nrx_cov_space_io()
+        so.batch, so.num_tx, so.num_subcarriers, so.num_symbols = B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS
+        so.num_rx_ant = p.num_rx_ant
+        so.h, so.acc = h.data_ptr(), self.acc_s.data_ptr()
+        _lib.check(self._lib.nrx_cov_space_workspace_size(ctypes.byref(so), ctypes.byref(n)))
+        if self._ws_s is None or self._ws_s.numel() < n.value:
+            self._ws_s = torch.empty(n.value, dtype=torch.uint8, device=self.acc.device)
+        _lib.check(self._lib.nrx_cov_space_accumulate(ctypes.byref(so), self._ws_s.data_ptr(), self._ws_s.numel(),
+                                                      stream))
         self.slots += B
 
     def lags(self):
@@ -114,6 +134,18 @@ class CovarianceEstimator:
     def matrices(self):
         r_f, r_t = self.lags()
         return toeplitz(r_f), toeplitz(r_t)
+
+    def space(self) -> np.ndarray:
+        """``R_s [A, A]`` complex128, scaled to ``trace = A`` and made exactly Hermitian: the
+        spatial covariance ``E h[a] conj(h[a'])`` over every (slot, user, RE).  One matrix for all
+        users, as ``R_f`` and ``R_t`` are -- the mixture over the users' profiles, which is what
+        the reference's compute_cov_mat.py estimates."""
+        if not self.slots:
+            raise ValueError("no slots accumulated")
+        a = self.acc_s.cpu().numpy()
+        R = a[..., 0] + 1j * a[..., 1]
+        R = 0.5 * (R + R.conj().T)
+        return R * (self.p.num_rx_ant / np.trace(R).real)
 
 
 @dataclasses.dataclass
@@ -180,46 +212,154 @@ def lmmse_design(R_f: np.ndarray, R_t: np.ndarray, params: GenParams, no: float,
     return LMMSEDesign(ri(filt), ri(tcoef), ri(vconj), err, float(no))
 
 
+LMMSE3_TABLES = ("qh", "gf", "nu", "tcoef", "vconj", "lam", "vs", "mu")
+
+
+@dataclasses.dataclass
+class LMMSE3Design:
+    """Tables of ``nrx_chest_lmmse3`` (include/nrx.h).  They do not depend on ``no``;
+    ``err_var(no)`` is the theoretical error map."""
+    qh: np.ndarray          # [2, Pmax, Pmax, 2] f32: rows of Q_g^H, qh[g][q][p] = conj(Q_g[p][q])
+    gf: np.ndarray          # [2, F, Pmax, 2] f32: G_g = R_f[:, P_g] Q_g
+    nu: np.ndarray          # [2, Pmax] f32: eigenvalues of R_f[P_g, P_g]
+    tcoef: np.ndarray       # [nd, 14, 2] f32: (R_t[:, D] v_k)[t]
+    vconj: np.ndarray       # [nd, nd, 2] f32: conj(v_k[d])
+    lam: np.ndarray         # [nd] f32: eigenvalues of R_t[D, D]
+    vs: np.ndarray          # [A, A, 2] f32: V_s[a][j]
+    mu: np.ndarray          # [A] f32: eigenvalues of R_s
+    prior: np.ndarray       # [A] f64: prior variance of an RE of antenna a, R_s[a, a] R_f[0, 0]
+    exact: dict             # the unrounded complex128 / float64 tables, for err_var
+
+    def err_var(self, no: float) -> np.ndarray:
+        """``E |h - h^|^2`` [2, A, F, 14] float64 per RE of a user of CDM group 0 / 1 at noise ``no``:
+        ``prior - sum_{j,k,q} |V_s[a][j] tcoef[k][t] G_g[f][q]|^2 mu_j^2 / (mu_j lambda_k nu_q +
+        sigma^2)``, from the unrounded tables (the diagonal of ``C - W C_obs^H`` of the Kronecker
+        form; tests/test_chest3_ref.py)."""
+        if not no > 0:
+            raise ValueError("no must be > 0")
+        x = self.exact
+        sigma2 = float(no) / 2.0
+        vs2, tc2 = np.abs(x["vs"]) ** 2, np.abs(x["tcoef"]) ** 2           # [A, j], [k, T]
+        mu, lam = x["mu"], x["lam"]
+        err = np.empty((2, len(mu), x["gf"].shape[1], NUM_SYMBOLS))
+        for g in (0, 1):
+            g2 = np.abs(x["gf"][g]) ** 2                                    # [F, q]
+            gain = mu[:, None, None] ** 2 / (mu[:, None, None] * lam[None, :, None] * x["nu"][g][None, None, :]
+                                             + sigma2)                      # [j, k, q]
+            err[g] = self.prior[:, None, None] - np.einsum("aj,kt,fq,jkq->aft", vs2, tc2, g2, gain)
+        return err
+
+
+def lmmse3_design(R_f: np.ndarray, R_t: np.ndarray, R_s: np.ndarray, params: GenParams,
+                  dtype=np.float32) -> LMMSE3Design:
+    """The exact Wiener filter under ``R_s (x) R_t (x) R_f`` for LS estimates at the own pilots with
+    white noise ``sigma^2 = no / 2``, in the three eigenbases (include/nrx.h nrx_chest_lmmse3):
+
+        R_s = V_s diag(mu) V_s^H  (scaled to trace A),   R_t[D, D] = V_t diag(lambda) V_t^H  (R_t scaled
+        to a unit diagonal),   R_f[P_g, P_g] = Q_g diag(nu_g) Q_g^H,   G_g = R_f[:, P_g] Q_g,
+        tcoef[k] = R_t[:, D] v_k
+
+        w[j,k,q] = sum_a conj(V_s[a][j]) sum_d conj(V_t[d][k]) sum_p conj(Q_g[p][q]) h_ls[a, P_p, D_d]
+        c[j,k,q] = mu_j / (mu_j lambda_k nu_q + sigma^2) w[j,k,q]
+        h^[a,f,t] = sum_j V_s[a][j] sum_k tcoef[k][t] sum_q G_g[f][q] c[j,k,q]
+
+    The cross-covariance of ``h`` with the pilots in the eigenbasis is ``(V_s mu) (x) tcoef (x) G_g``
+    and the pilots' covariance there is ``diag(mu_j lambda_k nu_q + sigma^2)``, which gives the
+    above; it equals the brute-force Kronecker solve (tests/test_chest3_ref.py).  No eigenvalue is
+    inverted, so no component is dropped, and ``no`` enters only through the gain: one design serves
+    an Eb/N0 sweep.  With ``R_s = I`` the estimate is the 2-D filter of ``lmmse_design``.  Eigenvalues
+    that rounding made negative are set to 0.  The tables are rounded once to float32
+    (``dtype=np.float64`` keeps them unrounded, for checks)."""
+    F, T, A = params.num_subcarriers, NUM_SYMBOLS, params.num_rx_ant
+    D = list(params.dmrs_symbols)
+    nd = len(D)
+    R_f = np.asarray(R_f, np.complex128)
+    R_t = np.asarray(R_t, np.complex128)
+    R_s = np.asarray(R_s, np.complex128)
+    if R_f.shape != (F, F) or R_t.shape != (T, T) or R_s.shape != (A, A):
+        raise ValueError(f"R_f must be {(F, F)}, R_t {(T, T)} and R_s {(A, A)}")
+    R_t = R_t / R_t[0, 0].real
+    R_s = R_s * (A / np.trace(R_s).real)
+    mu, Vs = np.linalg.eigh(0.5 * (R_s + R_s.conj().T))
+    lam, Vt = np.linalg.eigh(R_t[np.ix_(D, D)])
+    mu, lam = np.maximum(mu, 0.0), np.maximum(lam, 0.0)
+    Pmax = (F + 1) // 2
+    qh = np.zeros((2, Pmax, Pmax), np.complex128)
+    gf = np.zeros((2, F, Pmax), np.complex128)
+    nu = np.zeros((2, Pmax))
+    for g in (0, 1):
+        P = pilot_subcarriers(F, g)
+        if not len(P):
+            continue
+        n, Q = np.linalg.eigh(R_f[np.ix_(P, P)])
+        nu[g, :len(P)] = np.maximum(n, 0.0)
+        qh[g, :len(P), :len(P)] = Q.conj().T
+        gf[g, :, :len(P)] = R_f[:, P] @ Q
+    tcoef = (R_t[:, D] @ Vt).T                                              # [k, T]
+    vconj = Vt.conj().T                                                     # [k, d]
+    ri = lambda z: np.ascontiguousarray(np.stack([z.real, z.imag], -1).astype(dtype))  # noqa: E731
+    re = lambda x: np.ascontiguousarray(x.astype(dtype))                    # noqa: E731
+    exact = dict(gf=gf, nu=nu, tcoef=tcoef, lam=lam, vs=Vs, mu=mu)
+    return LMMSE3Design(ri(qh), ri(gf), re(nu), ri(tcoef), ri(vconj), re(lam), ri(Vs), re(mu),
+                        prior=np.real(np.diag(R_s)) * R_f[0, 0].real, exact=exact)
+
+
 class ChannelEstimator:
-    """``est(sb, no) -> h_est [B, U, F, 14, 2A]``: ``"lin"`` (``nrx_chest_lin``) or ``"lmmse"``
-    (``nrx_chest_lmmse``) on the LS estimates that ``sb.h_hat`` holds at the own pilots.
-    ``"lmmse"`` needs the covariance (``R_f``, ``R_t`` here or ``set_covariance``) and designs its
-    filter whenever ``no`` changes (``self.design``); ``tables=`` pins given ``LMMSEDesign`` tables
-    instead.  Every element of the output is written; inactive users are 0."""
+    """``est(sb, no) -> h_est [B, U, F, 14, 2A]``: ``"lin"`` (``nrx_chest_lin``), ``"lmmse"``
+    (``nrx_chest_lmmse``) or ``"lmmse3"`` (``nrx_chest_lmmse3``) on the LS estimates that
+    ``sb.h_hat`` holds at the own pilots.  ``"lmmse"`` needs the covariance (``R_f``, ``R_t`` here or
+    ``set_covariance``) and designs its filter whenever ``no`` changes (``self.design``);
+    ``"lmmse3"`` needs ``R_s`` as well and designs once per covariance.  ``tables=`` pins given
+    ``LMMSEDesign`` / ``LMMSE3Design`` tables instead.  Every element of the output is written;
+    inactive users are 0."""
 
     def __init__(self, kind: str, params: GenParams, device: int = 0, R_f=None, R_t=None,
-                 tables: Optional[LMMSEDesign] = None):
+                 tables=None, R_s=None):
         if kind not in KINDS:
             raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
         self.kind = kind
         self.p = params
         self.device = device
         self._lib = _lib.load()
-        self.R_f, self.R_t = R_f, R_t
-        self.design: Optional[LMMSEDesign] = None
+        self.R_f, self.R_t, self.R_s = R_f, R_t, R_s
+        self.design = None
         self._pinned = tables is not None
         self._dev = None
         self._out = None
+        self._ws = None
         if tables is not None:
             self._set_design(tables)
 
-    def set_covariance(self, R_f, R_t) -> None:
-        self.R_f, self.R_t = R_f, R_t
+    def set_covariance(self, R_f, R_t, R_s=None) -> None:
+        self.R_f, self.R_t, self.R_s = R_f, R_t, R_s
         if not self._pinned:
             self.design = None
 
-    def _set_design(self, d: LMMSEDesign) -> None:
+    def _set_design(self, d) -> None:
         p = self.p
-        nd, F = len(p.dmrs_symbols), p.num_subcarriers
-        if d.filt.shape != (2, nd, F, (F + 1) // 2, 2) or d.tcoef.shape != (nd, NUM_SYMBOLS, 2) \
+        nd, F, A = len(p.dmrs_symbols), p.num_subcarriers, p.num_rx_ant
+        Pmax = (F + 1) // 2
+        if self.kind == "lmmse3":
+            shapes = dict(qh=(2, Pmax, Pmax, 2), gf=(2, F, Pmax, 2), nu=(2, Pmax), tcoef=(nd, NUM_SYMBOLS, 2),
+                          vconj=(nd, nd, 2), lam=(nd,), vs=(A, A, 2), mu=(A,))
+            if not isinstance(d, LMMSE3Design) or any(
+                    getattr(d, k).shape != s or getattr(d, k).dtype != np.float32 for k, s in shapes.items()):
+                raise ValueError("tables do not match the parameters (lmmse3_design)")
+        elif d.filt.shape != (2, nd, F, Pmax, 2) or d.tcoef.shape != (nd, NUM_SYMBOLS, 2) \
                 or d.vconj.shape != (nd, nd, 2) or any(a.dtype != np.float32 for a in (d.filt, d.tcoef, d.vconj)):
             raise ValueError("tables do not match the parameters (lmmse_design)")
         self.design = d
         self._dev = None            # uploaded by the next call
 
-    def prepare(self, no: float) -> Optional[LMMSEDesign]:
+    def prepare(self, no: float):
         """(re-)design the LMMSE filter for ``no``; the design in use"""
-        if self.kind != "lmmse" or self._pinned:
+        if self.kind == "lin" or self._pinned:
+            return self.design
+        if self.kind == "lmmse3":
+            if self.design is None:
+                if self.R_f is None or self.R_t is None or self.R_s is None:
+                    raise ValueError("the 3-D LMMSE estimator needs R_f, R_t and R_s (set_covariance)")
+                self._set_design(lmmse3_design(self.R_f, self.R_t, self.R_s, self.p))
             return self.design
         if self.design is None or self.design.no != float(no):
             if self.R_f is None or self.R_t is None:
@@ -258,6 +398,8 @@ class ChannelEstimator:
         io.h_hat, io.active, io.h_out = hh.data_ptr(), sb.active.data_ptr(), out.data_ptr()
         if stream is None:
             stream = torch.cuda.current_stream(hh.device).cuda_stream
+        if self.kind == "lmmse3":
+            return self._lmmse3(io, no, out, stream)
         if self.kind == "lmmse":
             d = self.prepare(no)
             if self._dev is None:
@@ -267,6 +409,30 @@ class ChannelEstimator:
             _lib.check(self._lib.nrx_chest_lmmse(ctypes.byref(io), stream))
         else:
             _lib.check(self._lib.nrx_chest_lin(ctypes.byref(io), stream))
+        return out
+
+
+    def _lmmse3(self, io2, no, out, stream):
+        torch = _torch()
+        d = self.prepare(no)
+        if self._dev is None:
+            self._dev = {k: torch.from_numpy(np.ascontiguousarray(getattr(d, k))).to(out.device)
+                         for k in LMMSE3_TABLES}
+        io = _lib.nrx_chest3_io()
+        for f in ("batch", "num_tx", "num_subcarriers", "num_symbols", "num_rx_ant", "num_dmrs_symbols", "no",
+                  "h_hat", "active", "h_out"):
+            setattr(io, f, getattr(io2, f))
+        for k in range(4):
+            io.dmrs_symbols[k] = io2.dmrs_symbols[k]
+        for u in range(16):
+            io.cdm_group[u] = io2.cdm_group[u]
+        for k in LMMSE3_TABLES:
+            setattr(io, k, self._dev[k].data_ptr())
+        n = ctypes.c_size_t()
+        _lib.check(self._lib.nrx_chest3_workspace_size(ctypes.byref(io), ctypes.byref(n)))
+        if self._ws is None or self._ws.numel() < n.value:
+            self._ws = torch.empty(n.value, dtype=torch.uint8, device=out.device)
+        _lib.check(self._lib.nrx_chest_lmmse3(ctypes.byref(io), self._ws.data_ptr(), self._ws.numel(), stream))
         return out
 
 
@@ -286,21 +452,30 @@ class EstimatorBaselineReceiver:
     perfect_csi = False
     SYSTEMS = SYSTEMS
 
-    def __init__(self, system: str, params: GenParams, device: int = 0, R_f=None, R_t=None):
+    def __init__(self, system: str, params: GenParams, device: int = 0, R_f=None, R_t=None, R_s=None):
         if system not in SYSTEMS:
             raise ValueError(f"system must be one of {SYSTEMS}, got {system!r}")
         if params.num_tx > MAX_TX:
             raise ValueError(f"the LMMSE kernel is built for at most {MAX_TX} users, got {params.num_tx}")
         self.system = system
         self.p = params
-        self.estimator = ChannelEstimator("lmmse" if system == "baseline_lmmse_lmmse" else "lin", params, device,
-                                          R_f=R_f, R_t=R_t)
+        self._device = device
         self.detector = LMMSEDetector(device)
         self._out = None
         self.last_h = None      # the estimate the last call detected with
+        self.estimator = None
+        self._ev3 = None
+        self.set_covariance(R_f, R_t, R_s)
 
-    def set_covariance(self, R_f, R_t) -> None:
-        self.estimator.set_covariance(R_f, R_t)
+    def set_covariance(self, R_f, R_t, R_s=None) -> None:
+        """``R_s=None`` keeps the 2-D filter; a matrix selects the 3-D one (``baseline_lmmse_lmmse`` only)"""
+        kind = "lin" if self.system != "baseline_lmmse_lmmse" else "lmmse" if R_s is None else "lmmse3"
+        if self.estimator is None or self.estimator.kind != kind:
+            self.estimator = ChannelEstimator(kind, self.p, self._device)
+        if kind == "lmmse3":
+            self.estimator.set_covariance(R_f, R_t, R_s)
+        else:
+            self.estimator.set_covariance(R_f, R_t)
 
     @property
     def _num_active(self) -> int:
@@ -318,6 +493,11 @@ class EstimatorBaselineReceiver:
         d = self.estimator.prepare(no)
         data = [t for t in range(NUM_SYMBOLS) if t not in self.p.dmrs_symbols]
         groups = list(self.p.cdm_group[:self.p.num_tx])
+        if self.estimator.kind == "lmmse3":     # the design does not depend on no: the map is cached per no
+            if self._ev3 is None or self._ev3[0] is not d or self._ev3[1] != float(no):
+                ev = d.err_var(no)              # [2, A, F, 14]: also the mean over the antennas
+                self._ev3 = (d, float(no), self._num_active * float(np.mean([ev[g][:, :, data].mean() for g in groups])))
+            return self._ev3[2]
         return self._num_active * float(np.mean([d.err_var[g][:, data].mean() for g in groups]))
 
     def __call__(self, sb: SlotBatch, no: float, out=None, stream=None):

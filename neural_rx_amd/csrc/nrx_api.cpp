@@ -849,7 +849,29 @@ int nrx_gen_workspace_size(const nrx_gen_desc* desc, size_t* bytes) {
 
 int nrx_generate_slots(const nrx_gen_desc* desc, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
                        void* stream) {
+  return nrx_generate_slots_ex(desc, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+int nrx_generate_slots_ex(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_out* out, void* workspace,
+                          size_t workspace_bytes, void* stream) {
   if (int rc = check_gen(desc)) return rc;
+  nrx_gen_chan c{};                          // NULL chan: every port has the desc's scalars, no mixing
+  if (chan) {
+    for (int u = 0; u < desc->num_tx; ++u) {
+      if (!(chan->max_delay_s[u] >= 0.0) || !std::isfinite(chan->max_delay_s[u]) ||
+          !(chan->max_doppler_hz[u] >= 0.0) || !std::isfinite(chan->max_doppler_hz[u]))
+        return fail(NRX_ERR_INVALID_ARG, "per-port delay and Doppler spreads must be finite and non-negative");
+      c.max_delay_s[u] = chan->max_delay_s[u];
+      c.max_doppler_hz[u] = chan->max_doppler_hz[u];
+    }
+    if ((uintptr_t)chan->rx_mix & 7) return fail(NRX_ERR_INVALID_ARG, "rx_mix must be 8-byte aligned");
+    c.rx_mix = chan->rx_mix;
+  } else {
+    for (int u = 0; u < desc->num_tx; ++u) {
+      c.max_delay_s[u] = desc->max_delay_s;
+      c.max_doppler_hz[u] = desc->max_doppler_hz;
+    }
+  }
   if (!out || !out->y || !workspace) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   int bmax = 0;
   for (int m = 0; m < desc->num_mcs; ++m) bmax = desc->mcs_bits[m] > bmax ? desc->mcs_bits[m] : bmax;
@@ -861,7 +883,7 @@ int nrx_generate_slots(const nrx_gen_desc* desc, const nrx_gen_out* out, void* w
   const size_t need = gen_workspace_bytes(*desc, nullptr, nullptr);
   if (workspace_bytes < need)
     return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  hipError_t e = launch_generate(*desc, *out, workspace, (hipStream_t)stream);
+  hipError_t e = launch_generate(*desc, c, *out, workspace, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "slot generator launch");
   return NRX_OK;
 }
@@ -950,7 +972,10 @@ int nrx_kbest_detect(const nrx_kbest_io* io, void* workspace, size_t workspace_b
   return NRX_OK;
 }
 
-static int check_cov(const nrx_cov_io* io) {
+// nrx_cov_io and nrx_cov_space_io carry the same fields
+extern "C++" {
+template <class IO>
+static int check_cov(const IO* io) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
   if (!io->h || !io->acc) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
@@ -960,6 +985,7 @@ static int check_cov(const nrx_cov_io* io) {
   if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
   return NRX_OK;
 }
+}  // extern "C++"
 
 int nrx_cov_workspace_size(const nrx_cov_io* io, size_t* bytes) {
   if (int rc = check_cov(io)) return rc;
@@ -979,12 +1005,28 @@ int nrx_cov_accumulate(const nrx_cov_io* io, void* workspace, size_t workspace_b
   return NRX_OK;
 }
 
-static int check_chest(const nrx_chest_io* io, bool lmmse) {
-  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
-  if (!io->h_hat || !io->active || !io->h_out) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  if (lmmse && (!io->filt || !io->tcoef || !io->vconj)) return fail(NRX_ERR_INVALID_ARG, "null table pointer");
-  if (lmmse && ((uintptr_t)io->filt & 7)) return fail(NRX_ERR_INVALID_ARG, "filt must be 8-byte aligned");
-  if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
+int nrx_cov_space_workspace_size(const nrx_cov_space_io* io, size_t* bytes) {
+  if (int rc = check_cov(io)) return rc;
+  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
+  *bytes = cov_space_workspace_bytes(*io);
+  return NRX_OK;
+}
+
+int nrx_cov_space_accumulate(const nrx_cov_space_io* io, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_cov(io)) return rc;
+  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
+  const size_t need = cov_space_workspace_bytes(*io);
+  if (workspace_bytes < need)
+    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  hipError_t e = launch_cov_space(*io, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "spatial covariance launch");
+  return NRX_OK;
+}
+
+// the shape, DMRS and group fields that nrx_chest_io and nrx_chest3_io share
+extern "C++" {
+template <class IO>
+static int check_chest_shape(const IO* io) {
   if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
   if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
   if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
@@ -1000,6 +1042,16 @@ static int check_chest(const nrx_chest_io* io, bool lmmse) {
     if (io->cdm_group[u] != 0 && io->cdm_group[u] != 1) return fail(NRX_ERR_INVALID_ARG, "cdm_group must be 0/1");
   return NRX_OK;
 }
+}  // extern "C++"
+
+static int check_chest(const nrx_chest_io* io, bool lmmse) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->h_hat || !io->active || !io->h_out) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (lmmse && (!io->filt || !io->tcoef || !io->vconj)) return fail(NRX_ERR_INVALID_ARG, "null table pointer");
+  if (lmmse && ((uintptr_t)io->filt & 7)) return fail(NRX_ERR_INVALID_ARG, "filt must be 8-byte aligned");
+  if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
+  return check_chest_shape(io);
+}
 
 int nrx_chest_lmmse(const nrx_chest_io* io, void* stream) {
   if (int rc = check_chest(io, true)) return rc;
@@ -1012,6 +1064,37 @@ int nrx_chest_lin(const nrx_chest_io* io, void* stream) {
   if (int rc = check_chest(io, false)) return rc;
   hipError_t e = launch_chest_lin(*io, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "linear channel estimator launch");
+  return NRX_OK;
+}
+
+static int check_chest3(const nrx_chest3_io* io, bool tables) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (tables) {
+    if (!io->h_hat || !io->active || !io->h_out) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+    if (!io->qh || !io->gf || !io->nu || !io->tcoef || !io->vconj || !io->lam || !io->vs || !io->mu)
+      return fail(NRX_ERR_INVALID_ARG, "null table pointer");
+    if (((uintptr_t)io->qh | (uintptr_t)io->gf) & 7) return fail(NRX_ERR_INVALID_ARG, "qh and gf must be 8-byte aligned");
+    if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
+  }
+  return check_chest_shape(io);
+}
+
+int nrx_chest3_workspace_size(const nrx_chest3_io* io, size_t* bytes) {
+  if (int rc = check_chest3(io, false)) return rc;
+  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
+  *bytes = chest3_workspace_bytes(*io);
+  return NRX_OK;
+}
+
+int nrx_chest_lmmse3(const nrx_chest3_io* io, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_chest3(io, true)) return rc;
+  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
+  if ((uintptr_t)workspace & 3) return fail(NRX_ERR_INVALID_ARG, "workspace must be 4-byte aligned");
+  const size_t need = chest3_workspace_bytes(*io);
+  if (workspace_bytes < need)
+    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  hipError_t e = launch_chest_lmmse3(*io, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "3-D lmmse channel estimator launch");
   return NRX_OK;
 }
 

@@ -124,6 +124,63 @@ int cov_groups(const nrx_cov_io& io) {
   return (int)(rows < kCovGroups ? rows : kCovGroups);
 }
 
+// ------------------------------------------------------------------ spatial covariance sums
+struct CovSpaceArgs {
+  int A, groups;
+  int64_t rows;         // B * U * F * T resource elements of 2A floats
+  const float* h;
+  double* part;         // [groups][A * A][2]
+  double* acc;          // [A * A][2]
+};
+
+// Thread (s, p) of workgroup g owns the antenna pair p = (a, a') and walks the resource elements
+// r = g * S + s, + groups * S, ... (S = 256 / A^2 walkers per pair): the lanes of a pair group read
+// one 2A-float row together, so every row comes from HBM once.  The S walkers of a pair are summed
+// in ascending s by the pair's first thread: a fixed order, f64 throughout.
+__global__ __launch_bounds__(kCovBlock) void k_cov_space_partial(CovSpaceArgs p) {
+  __shared__ double red[kCovBlock][2];
+  const int tid = threadIdx.x, g = blockIdx.x;
+  const int A = p.A, AA = A * A, S = kCovBlock / AA;
+  const int s = tid / AA, pr = tid - s * AA;
+  const int a = pr / A, a2 = pr - a * A;
+  double sr = 0.0, si = 0.0;
+  if (s < S) {
+    for (int64_t r = (int64_t)g * S + s; r < p.rows; r += (int64_t)p.groups * S) {
+      const float* src = p.h + (size_t)r * 2 * A;
+      const double xr = src[a], xi = src[A + a], yr = src[a2], yi = src[A + a2];   // x conj(y)
+      sr += xr * yr + xi * yi;
+      si += xi * yr - xr * yi;
+    }
+  }
+  red[tid][0] = sr;
+  red[tid][1] = si;
+  __syncthreads();
+  if (tid < AA) {
+    double tr = 0.0, ti = 0.0;
+    for (int k = 0; k < S; ++k) {
+      tr += red[k * AA + tid][0];
+      ti += red[k * AA + tid][1];
+    }
+    p.part[((size_t)g * AA + tid) * 2] = tr;
+    p.part[((size_t)g * AA + tid) * 2 + 1] = ti;
+  }
+}
+
+// acc[i] += sum_g part[g][i], g ascending: one lane per output, no atomics
+__global__ __launch_bounds__(kCovBlock) void k_cov_space_reduce(CovSpaceArgs p) {
+  const int n = p.A * p.A * 2;
+  const int i = blockIdx.x * kCovBlock + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int g = 0; g < p.groups; ++g) s += p.part[(size_t)g * n + i];
+  p.acc[i] += s;
+}
+
+int cov_space_groups(const nrx_cov_space_io& io) {
+  const int64_t rows = (int64_t)io.batch * io.num_tx * io.num_subcarriers * kT;
+  return (int)(rows < kCovGroups ? rows : kCovGroups);
+}
+
 // ------------------------------------------------------------------ the estimators
 constexpr int kChBlock = 256;
 constexpr int kChWaves = kChBlock / 64;
@@ -354,6 +411,301 @@ __global__ __launch_bounds__(kChBlock) void k_chest_lin(ChestArgs p, int64_t nve
 #undef NRX_LIN
 }
 
+// ------------------------------------------------------------------ the 3-D (space-time-frequency) filter
+// nrx_chest_lmmse3 (include/nrx.h): the exact Wiener filter under R_s (x) R_t (x) R_f, diagonal in the
+// three eigenbases.  Two launches around a workspace c' [B U][Pmax][nd][2A]:
+//   k_chest3_pilot   w = Q_g^H . z on the MFMA (M = eigen-component q, K = pilot p, N = spatial
+//                    component j), z = (V_s^H (x) V_t^H) h_ls applied while staging; then the gain
+//                    mu_j / (mu_j lambda_k nu_q + sigma^2) and the rotation back to antennas
+//                    c'[a] = sum_j V_s[a][j] c[j] in the epilogue.  The rotation commutes with the
+//                    frequency product of the second stage, so it is done here, on |P| rows, and not
+//                    there, on F rows.
+//   k_chest3_expand  Y_k = G_g . c'_k on the MFMA (M = subcarrier, K = q, N = antenna) and the
+//                    14-symbol expansion by tcoef: k_chest_lmmse with one A operand for all k.
+// Both read the A operand (rows of qh / gf) once for all nd components.
+struct Chest3Args {
+  int B, U, F, A, nd;
+  int dm[4];
+  unsigned grp_mask;                // bit u: cdm_group[u]
+  float sigma2;                     // no / 2
+  const float* hh;
+  const float* active;
+  const float* qh;                  // [2][Pmax][Pmax][2]
+  const float* gf;                  // [2][F][Pmax][2]
+  const float* nu;                  // [2][Pmax]
+  const float* tcoef;               // [nd][14][2]
+  const float* vconj;               // [nd][nd][2]
+  const float* lam;                 // [nd]
+  const float* vs;                  // [A][A][2]
+  const float* mu;                  // [A]
+  float* cw;                        // [B U][Pmax][nd][2A]
+  float* out;
+};
+
+template <int ND>
+__global__ __launch_bounds__(kChBlock) void k_chest3_pilot(Chest3Args p) {
+  __shared__ float zs[ND][2][kPC / 4 * kZG];        // z chunk [k][re / im][z_at(pilot, component j)]
+  __shared__ float ys[kChWaves][ND][2][16][16];     // per wave: c tile [k][re / im][row q][component j]
+  __shared__ float vc[ND * ND * 2];
+  __shared__ float vsr[16 * 16], vsi[16 * 16];      // V_s[a][j] at [a * 16 + j], zero beyond A
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bu = blockIdx.x, u = bu % p.U;
+  if (!(p.active[bu] > 0.0f)) return;               // uniform; k_chest3_expand writes the zeros and reads no c'
+  const int F = p.F, A = p.A, A2 = 2 * A;
+  const int g = (p.grp_mask >> u) & 1;
+  const int P = (F - g + 1) >> 1;
+  const int Pmax = (F + 1) >> 1;
+  const int q0 = (blockIdx.y * kChWaves + wave) * 16;
+  const int nrow = P - q0 < 16 ? P - q0 : 16;       // <= 0: no tile for this wave
+  if (tid < ND * ND * 2) vc[tid] = p.vconj[tid];
+  {
+    const int a = tid >> 4, j = tid & 15;
+    const bool ok = a < A && j < A;
+    vsr[tid] = ok ? p.vs[(a * A + j) * 2] : 0.0f;
+    vsi[tid] = ok ? p.vs[(a * A + j) * 2 + 1] : 0.0f;
+  }
+  f32x4 accr[ND], acci[ND];
+#pragma unroll
+  for (int k = 0; k < ND; ++k) accr[k] = acci[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int col = lane & 15, kk = lane >> 4;
+  int qrow = q0 + col < P ? q0 + col : P - 1;       // rows past P are computed on row P - 1 and dropped
+  qrow = qrow < 0 ? 0 : qrow;
+  const float* hb = p.hh + (size_t)bu * F * kT * A2;
+  const float2* wrow = reinterpret_cast<const float2*>(p.qh) + ((size_t)g * Pmax + qrow) * Pmax;
+
+  for (int pc = 0; pc < P; pc += kPC) {
+    float2 wv[kPC / 4];
+#pragma unroll
+    for (int i = 0; i < kPC / 4; ++i) {
+      const int pp = pc + 16 * (i >> 2) + 4 * kk + (i & 3);
+      wv[i] = nrow > 0 && pp < P ? wrow[pp] : make_float2(0.f, 0.f);
+    }
+    __syncthreads();                                // the tables are there; the previous chunk has been read
+    for (int e = tid; e < kPC * 16; e += kChBlock) {
+      const int pp = e >> 4, j = e & 15;
+      float zr[ND], zi[ND];
+#pragma unroll
+      for (int k = 0; k < ND; ++k) zr[k] = zi[k] = 0.0f;
+      if (pc + pp < P && j < A) {
+        const float* src = hb + (size_t)(g + 2 * (pc + pp)) * kT * A2;
+        for (int a = 0; a < A; ++a) {
+          float yr[ND], yi[ND];
+#pragma unroll
+          for (int k = 0; k < ND; ++k) yr[k] = yi[k] = 0.0f;
+#pragma unroll
+          for (int d = 0; d < ND; ++d) {
+            const float xr = src[p.dm[d] * A2 + a], xi = src[p.dm[d] * A2 + A + a];
+#pragma unroll
+            for (int k = 0; k < ND; ++k) {
+              const float cr = vc[(k * ND + d) * 2], ci = vc[(k * ND + d) * 2 + 1];
+              yr[k] += cr * xr - ci * xi;
+              yi[k] += cr * xi + ci * xr;
+            }
+          }
+          const float sr = vsr[a * 16 + j], si = -vsi[a * 16 + j];      // conj(V_s[a][j])
+#pragma unroll
+          for (int k = 0; k < ND; ++k) {
+            zr[k] += sr * yr[k] - si * yi[k];
+            zi[k] += sr * yi[k] + si * yr[k];
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < ND; ++k) {
+        zs[k][0][z_at(pp, j)] = zr[k];
+        zs[k][1][z_at(pp, j)] = zi[k];
+      }
+    }
+    __syncthreads();
+    if (nrow > 0) {
+#pragma unroll
+      for (int i = 0; i < kPC / 4; ++i) {
+        if (pc + 16 * (i >> 2) < P) {               // uniform
+          const int pp = 16 * (i >> 2) + 4 * kk + (i & 3);
+          const float2 w = wv[i];
+#pragma unroll
+          for (int k = 0; k < ND; ++k) {
+            const float zr = zs[k][0][z_at(pp, col)], zi = zs[k][1][z_at(pp, col)];
+            accr[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, zr, accr[k], 0, 0, 0);
+            acci[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, zi, acci[k], 0, 0, 0);
+            accr[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, -zi, accr[k], 0, 0, 0);
+            acci[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, zr, acci[k], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+  // C / D layout: column = lane & 15 (component j), row = 4 (lane >> 4) + register (component q); the
+  // gain is element-wise there
+  const float muj = col < A ? p.mu[col] : 0.0f;
+#pragma unroll
+  for (int k = 0; k < ND; ++k) {
+    const float lk = p.lam[k];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int q = q0 + kk * 4 + r;
+      const float nq = q < P ? p.nu[g * Pmax + q] : 0.0f;
+      const float gain = muj / (muj * lk * nq + p.sigma2);
+      ys[wave][k][0][kk * 4 + r][col] = accr[k][r] * gain;
+      ys[wave][k][1][kk * 4 + r][col] = acci[k][r] * gain;
+    }
+  }
+  __syncthreads();
+  if (nrow <= 0) return;
+  // back to antennas, c'[a] = sum_j V_s[a][j] c[j]; the wave's rows are one contiguous run of c'
+  const int n = nrow * ND * A2;
+  float* dst = p.cw + ((size_t)bu * Pmax + q0) * ND * A2;
+  for (int e = lane; e < n; e += 64) {
+    const int row = e / (ND * A2), rem = e - row * (ND * A2);
+    const int k = rem / A2, c = rem - k * A2;
+    const bool im = c >= A;
+    const int a = im ? c - A : c;
+    float o = 0.0f;
+    for (int j = 0; j < A; ++j) {
+      const float vr = vsr[a * 16 + j], vi = vsi[a * 16 + j];
+      const float yr = ys[wave][k][0][row][j], yi = ys[wave][k][1][row][j];
+      o += im ? vr * yi + vi * yr : vr * yr - vi * yi;
+    }
+    dst[e] = o;
+  }
+}
+
+template <int ND, bool VEC>
+__global__ __launch_bounds__(kChBlock) void k_chest3_expand(Chest3Args p) {
+  __shared__ float zs[ND][2][kPC / 4 * kZG];        // c' chunk [k][re / im][z_at(component q, antenna)]
+  __shared__ float ys[kChWaves][ND][2][16][16];     // per wave: Y_k tile [k][re / im][row][antenna]
+  __shared__ float tc[ND * kT * 2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bu = blockIdx.x, u = bu % p.U;
+  const int F = p.F, A = p.A, A2 = 2 * A;
+  const int f0 = (blockIdx.y * kChWaves + wave) * 16;
+  const int nrow = F - f0 < 16 ? F - f0 : 16;       // <= 0: no tile for this wave
+  const int n = nrow * kT * A2;                     // this wave's output floats, one contiguous run
+  float* dst = p.out + ((size_t)bu * F + (nrow > 0 ? f0 : 0)) * kT * A2;
+  if (!(p.active[bu] > 0.0f)) {                     // uniform over the workgroup
+    if (VEC) {
+      for (int e = lane * 4; e < n; e += 256) *reinterpret_cast<float4*>(dst + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      for (int e = lane; e < n; e += 64) dst[e] = 0.0f;
+    }
+    return;
+  }
+  const int g = (p.grp_mask >> u) & 1;
+  const int P = (F - g + 1) >> 1;
+  const int Pmax = (F + 1) >> 1;
+  if (tid < ND * kT * 2) tc[tid] = p.tcoef[tid];
+  f32x4 accr[ND], acci[ND];
+#pragma unroll
+  for (int k = 0; k < ND; ++k) accr[k] = acci[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int col = lane & 15, kk = lane >> 4;
+  const int frow = f0 + col < F ? f0 + col : F - 1; // rows past F are computed on row F - 1 and dropped
+  const float* cb = p.cw + (size_t)bu * Pmax * ND * A2;
+  const float2* wrow = reinterpret_cast<const float2*>(p.gf) + ((size_t)g * F + frow) * Pmax;
+
+  for (int pc = 0; pc < P; pc += kPC) {
+    float2 wv[kPC / 4];
+#pragma unroll
+    for (int i = 0; i < kPC / 4; ++i) {
+      const int pp = pc + 16 * (i >> 2) + 4 * kk + (i & 3);
+      wv[i] = nrow > 0 && pp < P ? wrow[pp] : make_float2(0.f, 0.f);
+    }
+    __syncthreads();                                // the previous chunk has been read
+    for (int e = tid; e < kPC * 16; e += kChBlock) {
+      const int pp = e >> 4, a = e & 15;
+      float zr[ND], zi[ND];
+#pragma unroll
+      for (int k = 0; k < ND; ++k) zr[k] = zi[k] = 0.0f;
+      if (pc + pp < P && a < A) {
+        const float* src = cb + (size_t)(pc + pp) * ND * A2 + a;
+#pragma unroll
+        for (int k = 0; k < ND; ++k) {
+          zr[k] = src[k * A2];
+          zi[k] = src[k * A2 + A];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < ND; ++k) {
+        zs[k][0][z_at(pp, a)] = zr[k];
+        zs[k][1][z_at(pp, a)] = zi[k];
+      }
+    }
+    __syncthreads();
+    if (nrow > 0) {
+#pragma unroll
+      for (int i = 0; i < kPC / 4; ++i) {
+        if (pc + 16 * (i >> 2) < P) {               // uniform
+          const int pp = 16 * (i >> 2) + 4 * kk + (i & 3);
+          const float2 w = wv[i];
+#pragma unroll
+          for (int k = 0; k < ND; ++k) {
+            const float zr = zs[k][0][z_at(pp, col)], zi = zs[k][1][z_at(pp, col)];
+            accr[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, zr, accr[k], 0, 0, 0);
+            acci[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, zi, acci[k], 0, 0, 0);
+            accr[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, -zi, accr[k], 0, 0, 0);
+            acci[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, zr, acci[k], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < ND; ++k) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      ys[wave][k][0][kk * 4 + r][col] = accr[k][r];
+      ys[wave][k][1][kk * 4 + r][col] = acci[k][r];
+    }
+  }
+  __syncthreads();
+  const int rowlen = kT * A2;
+  if (VEC) {
+    for (int e = lane * 4; e < n; e += 256) {
+      const int fr = e / rowlen, rem = e - fr * rowlen;
+      const int t = rem / A2, c = rem - t * A2;
+      const bool im = c >= A;
+      const int a = im ? c - A : c;
+      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int k = 0; k < ND; ++k) {
+        const float ar = tc[(k * kT + t) * 2], ai = tc[(k * kT + t) * 2 + 1];
+        const float4 yr = *reinterpret_cast<const float4*>(&ys[wave][k][0][fr][a]);
+        const float4 yi = *reinterpret_cast<const float4*>(&ys[wave][k][1][fr][a]);
+        const float c0 = im ? ai : ar, c1 = im ? ar : -ai;       // re: ar yr - ai yi, im: ai yr + ar yi
+        o.x += c0 * yr.x + c1 * yi.x;
+        o.y += c0 * yr.y + c1 * yi.y;
+        o.z += c0 * yr.z + c1 * yi.z;
+        o.w += c0 * yr.w + c1 * yi.w;
+      }
+      *reinterpret_cast<float4*>(dst + e) = o;
+    }
+  } else {
+    for (int e = lane; e < n; e += 64) {
+      const int fr = e / rowlen, rem = e - fr * rowlen;
+      const int t = rem / A2, c = rem - t * A2;
+      const bool im = c >= A;
+      const int a = im ? c - A : c;
+      float o = 0.0f;
+#pragma unroll
+      for (int k = 0; k < ND; ++k) {
+        const float ar = tc[(k * kT + t) * 2], ai = tc[(k * kT + t) * 2 + 1];
+        const float c0 = im ? ai : ar, c1 = im ? ar : -ai;
+        o += c0 * ys[wave][k][0][fr][a] + c1 * ys[wave][k][1][fr][a];
+      }
+      dst[e] = o;
+    }
+  }
+}
+
+template <int ND>
+void launch3_nd(const Chest3Args& a, bool vec, hipStream_t st) {
+  const int Pmax = (a.F + 1) / 2;
+  const int qtiles = (Pmax + 15) / 16, ftiles = (a.F + 15) / 16;
+  k_chest3_pilot<ND><<<dim3(a.B * a.U, (qtiles + kChWaves - 1) / kChWaves), kChBlock, 0, st>>>(a);
+  const dim3 grid(a.B * a.U, (ftiles + kChWaves - 1) / kChWaves);
+  if (vec) k_chest3_expand<ND, true><<<grid, kChBlock, 0, st>>>(a);
+  else k_chest3_expand<ND, false><<<grid, kChBlock, 0, st>>>(a);
+}
+
 ChestArgs chest_args(const nrx_chest_io& io) {
   ChestArgs a;
   a.B = io.batch;
@@ -403,6 +755,24 @@ hipError_t launch_cov_accumulate(const nrx_cov_io& io, void* ws, hipStream_t st)
   return hipGetLastError();
 }
 
+size_t cov_space_workspace_bytes(const nrx_cov_space_io& io) {
+  return (size_t)cov_space_groups(io) * io.num_rx_ant * io.num_rx_ant * 2 * sizeof(double);
+}
+
+hipError_t launch_cov_space(const nrx_cov_space_io& io, void* ws, hipStream_t st) {
+  CovSpaceArgs a;
+  a.A = io.num_rx_ant;
+  a.groups = cov_space_groups(io);
+  a.rows = (int64_t)io.batch * io.num_tx * io.num_subcarriers * kT;
+  a.h = io.h;
+  a.part = (double*)ws;
+  a.acc = io.acc;
+  k_cov_space_partial<<<a.groups, kCovBlock, 0, st>>>(a);
+  const int n = a.A * a.A * 2;
+  k_cov_space_reduce<<<(n + kCovBlock - 1) / kCovBlock, kCovBlock, 0, st>>>(a);
+  return hipGetLastError();
+}
+
 hipError_t launch_chest_lmmse(const nrx_chest_io& io, hipStream_t st) {
   const ChestArgs a = chest_args(io);
   // dwordx4 stores need A % 4 == 0 and a 16-byte aligned h_out (tiles start at multiples of 8A floats)
@@ -412,6 +782,45 @@ hipError_t launch_chest_lmmse(const nrx_chest_io& io, hipStream_t st) {
     case 2: launch_nd<2>(a, vec, st); break;
     case 3: launch_nd<3>(a, vec, st); break;
     case 4: launch_nd<4>(a, vec, st); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+size_t chest3_workspace_bytes(const nrx_chest3_io& io) {
+  const size_t Pmax = ((size_t)io.num_subcarriers + 1) / 2;
+  return (size_t)io.batch * io.num_tx * Pmax * io.num_dmrs_symbols * 2 * io.num_rx_ant * sizeof(float);
+}
+
+hipError_t launch_chest_lmmse3(const nrx_chest3_io& io, void* ws, hipStream_t st) {
+  Chest3Args a;
+  a.B = io.batch;
+  a.U = io.num_tx;
+  a.F = io.num_subcarriers;
+  a.A = io.num_rx_ant;
+  a.nd = io.num_dmrs_symbols;
+  for (int k = 0; k < 4; ++k) a.dm[k] = k < a.nd ? io.dmrs_symbols[k] : io.dmrs_symbols[0];
+  a.grp_mask = 0;
+  for (int u = 0; u < io.num_tx; ++u) a.grp_mask |= (unsigned)(io.cdm_group[u] & 1) << u;
+  a.sigma2 = (float)(io.no / 2.0);
+  a.hh = io.h_hat;
+  a.active = io.active;
+  a.qh = io.qh;
+  a.gf = io.gf;
+  a.nu = io.nu;
+  a.tcoef = io.tcoef;
+  a.vconj = io.vconj;
+  a.lam = io.lam;
+  a.vs = io.vs;
+  a.mu = io.mu;
+  a.cw = (float*)ws;
+  a.out = io.h_out;
+  const bool vec = io.num_rx_ant % 4 == 0 && ((uintptr_t)io.h_out & 15) == 0;
+  switch (a.nd) {
+    case 1: launch3_nd<1>(a, vec, st); break;
+    case 2: launch3_nd<2>(a, vec, st); break;
+    case 3: launch3_nd<3>(a, vec, st); break;
+    case 4: launch3_nd<4>(a, vec, st); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

@@ -167,7 +167,8 @@ hipError_t launch_aerial_llr(const float* llr, int B, int U, int F, int T, int b
 // gen_workspace_bytes(d, nullptr, nullptr) = workspace size.
 struct GenWs;
 size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base);
-hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_out& o, void* ws, hipStream_t st);
+hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
+                           hipStream_t st);
 hipError_t launch_count_errors(const nrx_count_io& c, hipStream_t st);
 
 // LMMSE + max-log baseline detector (nrx_lmmse.hip); io validated by nrx_lmmse_detect
@@ -180,8 +181,12 @@ hipError_t launch_kbest(const nrx_kbest_io& io, void* ws, hipStream_t st);
 // Channel-estimation baselines (nrx_chest.hip); io validated by the nrx_cov_* / nrx_chest_* entry points
 size_t cov_workspace_bytes(const nrx_cov_io& io);
 hipError_t launch_cov_accumulate(const nrx_cov_io& io, void* ws, hipStream_t st);
+size_t cov_space_workspace_bytes(const nrx_cov_space_io& io);
+hipError_t launch_cov_space(const nrx_cov_space_io& io, void* ws, hipStream_t st);
 hipError_t launch_chest_lmmse(const nrx_chest_io& io, hipStream_t st);
 hipError_t launch_chest_lin(const nrx_chest_io& io, hipStream_t st);
+size_t chest3_workspace_bytes(const nrx_chest3_io& io);
+hipError_t launch_chest_lmmse3(const nrx_chest3_io& io, void* ws, hipStream_t st);
 
 // Soft-output metrics (nrx_softmetrics.hip); io validated by the nrx_llr_stats* / nrx_nmse* entry points
 constexpr int kSoftFS = NRX_SOFT_STRIP;   // subcarriers per work item

@@ -8,6 +8,8 @@
 //   k_gen_params   per slot: active ports (Fisher-Yates, e2e_model.py:187-193), MCS per
 //                  user, TDL delays (sorted, first = 0) and the exponential PDP
 //   k_gen_taps     per (slot, user, antenna, tap, symbol): sum-of-sinusoids tap gain g(t)
+//   k_gen_mix      per (slot, user, tap, symbol): receive-antenna mixing of the finished taps
+//                  (nrx_generate_slots_ex with rx_mix; tests/synth_chan_ref.py states it)
 //   k_gen_tx       per (slot, user, RE): Philox bits, Gray QAM / DMRS QPSK x sqrt(2), x *= active
 //   k_gen_rx       per (slot, subcarrier): the user/tap phasors of that subcarrier in LDS,
 //                  then y[a][t] = sum_u H_u x_u + AWGN (and the true channel, optional)
@@ -92,7 +94,8 @@ __device__ __forceinline__ double2 qam(uint32_t w, int m) {
                       s(1) * (4.0 - s(3) * (2.0 - s(5))) / sqrt(42.0));
 }
 
-__global__ __launch_bounds__(64) void k_gen_params(nrx_gen_desc d, GenWs w, float* __restrict__ active_out,
+__global__ __launch_bounds__(64) void k_gen_params(nrx_gen_desc d, nrx_gen_chan ch, GenWs w,
+                                                    float* __restrict__ active_out,
                                                     float* __restrict__ mcs_mask, uint8_t* __restrict__ mcs_out) {
   const int b = blockIdx.x;
   const int U = d.num_tx, L = d.num_taps, M = d.num_mcs;
@@ -132,7 +135,7 @@ __global__ __launch_bounds__(64) void k_gen_params(nrx_gen_desc d, GenWs w, floa
   // (ties by index, as a stable sort), the smallest set to 0; PDP normalised per user
   __shared__ double tau[kMaxUsers * 8];
   __shared__ double pw[kMaxUsers * 8];
-  for (int j = i; j < U * L; j += 64) tau[j] = uni(draw(d, b, ST_DELAY, j).x) * d.max_delay_s;
+  for (int j = i; j < U * L; j += 64) tau[j] = uni(draw(d, b, ST_DELAY, j).x) * ch.max_delay_s[j / L];
   __syncthreads();
   double tr[2], pr[2];
   int rk[2];
@@ -147,7 +150,7 @@ __global__ __launch_bounds__(64) void k_gen_params(nrx_gen_desc d, GenWs w, floa
     }
     rk[q] = r;
     tr[q] = r == 0 ? 0.0 : tau[j];
-    pr[q] = exp(-tr[q] / (d.max_delay_s / kPDP + 1e-12));
+    pr[q] = exp(-tr[q] / (ch.max_delay_s[u] / kPDP + 1e-12));
   }
   __syncthreads();
   for (int q = 0; q < 2; ++q) {
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(64) void k_gen_params(nrx_gen_desc d, GenWs w, floa
 constexpr int kTapGroups = 16;
 constexpr int kMaxSinusoids = 16;   // nrx_generate_slots validates num_sinusoids <= 16
 
-__global__ __launch_bounds__(kTapGroups * kT) void k_gen_taps(nrx_gen_desc d, GenWs w) {
+__global__ __launch_bounds__(kTapGroups * kT) void k_gen_taps(nrx_gen_desc d, nrx_gen_chan ch, GenWs w) {
   __shared__ double sg[kTapGroups * kMaxSinusoids][3];
   const int U = d.num_tx, A = d.num_rx_ant, L = d.num_taps, NS = d.num_sinusoids;
   const int64_t ngrp = (int64_t)d.batch * U * A * L;
@@ -196,7 +199,7 @@ __global__ __launch_bounds__(kTapGroups * kT) void k_gen_taps(nrx_gen_desc d, Ge
     const double2 z = box_muller(r.x, r.y);
     sg[j][0] = z.x * sc;
     sg[j][1] = z.y * sc;
-    sg[j][2] = d.max_doppler_hz * cos(2.0 * kPi * uni(r.z));
+    sg[j][2] = ch.max_doppler_hz[u] * cos(2.0 * kPi * uni(r.z));
   }
   __syncthreads();
   const int gl = threadIdx.x / kT, t = threadIdx.x % kT;
@@ -214,6 +217,36 @@ __global__ __launch_bounds__(kTapGroups * kT) void k_gen_taps(nrx_gen_desc d, Ge
   const int64_t bu = g / ((int64_t)L * A);
   const double sp = w.spdp[bu * L + l];
   w.gt[g * kT + t] = make_double2(ar * sp, ai * sp);
+}
+
+// Receive-antenna mixing g'[a] = sum_a' M[a][a'] g[a'] (nrx_gen_chan.rx_mix), in place: one thread
+// per (b, u, l, t) holds the A taps of its column in registers, so no thread reads what another
+// writes; complex f64, a' ascending.  The taps of one antenna lie L * T apart, so a wave's loads and
+// stores of one antenna are contiguous.
+__global__ __launch_bounds__(256) void k_gen_mix(GenWs w, const double* __restrict__ mix, int A, int LT, int64_t n) {
+  __shared__ double2 m[16 * 16];
+  for (int j = threadIdx.x; j < A * A; j += 256) m[j] = make_double2(mix[2 * j], mix[2 * j + 1]);
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t bu = i / LT;
+  double2* g = w.gt + bu * A * LT + (i - bu * LT);
+  double2 v[16];
+#pragma unroll
+  for (int a = 0; a < 16; ++a)
+    if (a < A) v[a] = g[(size_t)a * LT];
+  for (int a = 0; a < A; ++a) {
+    double sr = 0.0, si = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      if (k < A) {
+        const double2 mm = m[a * A + k];
+        sr += mm.x * v[k].x - mm.y * v[k].y;
+        si += mm.x * v[k].y + mm.y * v[k].x;
+      }
+    }
+    g[(size_t)a * LT] = make_double2(sr, si);
+  }
 }
 
 // one thread per (b, u, f, t)
@@ -544,14 +577,16 @@ size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base) {
   return o;
 }
 
-hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_out& o, void* ws, hipStream_t st) {
+hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
+                           hipStream_t st) {
   GenWs w;
   gen_workspace_bytes(d, &w, (char*)ws);
   const int64_t B = d.batch, U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols, A = d.num_rx_ant,
                 L = d.num_taps;
   auto blocks = [](int64_t n) { return (unsigned)((n + 255) / 256); };
-  k_gen_params<<<(unsigned)B, 64, 0, st>>>(d, w, o.active, o.mcs_mask, o.mcs);
-  k_gen_taps<<<(unsigned)((B * U * A * L + kTapGroups - 1) / kTapGroups), kTapGroups * kT, 0, st>>>(d, w);
+  k_gen_params<<<(unsigned)B, 64, 0, st>>>(d, c, w, o.active, o.mcs_mask, o.mcs);
+  k_gen_taps<<<(unsigned)((B * U * A * L + kTapGroups - 1) / kTapGroups), kTapGroups * kT, 0, st>>>(d, c, w);
+  if (c.rx_mix) k_gen_mix<<<blocks(B * U * L * kT), 256, 0, st>>>(w, c.rx_mix, (int)A, (int)(L * kT), B * U * L * kT);
   k_gen_tx<<<blocks(B * U * F * T), 256, 0, st>>>(d, w, o.bits, o.bits_stride);
   const int at = (int)(A * T);
   int FB = 256 / at;

@@ -30,7 +30,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .config import dmrs_symbols, get_config
-from .generator import GenParams, SlotGenerator, count_errors, ebno_to_no
+from .generator import SCENARIOS, GenParams, SlotGenerator, count_errors, ebno_to_no, rx_correlation, scenario
 from .baseline import BaselineReceiver
 from .chest import COV_SLOT_OFFSET, EstimatorBaselineReceiver, estimate_covariance
 from .kbest import KBestBaselineReceiver
@@ -278,6 +278,16 @@ def main(argv=None):
                     help="LLR scale factors the GMI is searched over (1..16 positive numbers)")
     ap.add_argument("-code_rate", type=float, default=None,
                     help="with -soft_metrics: report the Eb/N0 at which BMI and GMI reach this rate")
+    ap.add_argument("-channel", default="iid", choices=["iid"] + list(SCENARIOS),
+                    help="iid: one delay / Doppler profile for every user and uncorrelated receive antennas; "
+                         "double_tdl_low / double_tdl_high: the two-user profiles of the reference's evaluation "
+                         "channel with gNB antenna correlation alpha = 0 / 0.9 (generator.scenario; needs a "
+                         "two-port config)")
+    ap.add_argument("-rx_corr", type=float, default=None, metavar="ALPHA",
+                    help="receive-antenna correlation rx_correlation(A, ALPHA), replacing the channel's own")
+    ap.add_argument("-chest_2d", action="store_true",
+                    help="on a correlated channel lmmse_lmmse uses the spatial covariance (nrx_chest_lmmse3); this "
+                         "keeps the 2-D filter that ignores it, so that both can be tabulated")
     a = ap.parse_args(argv)
 
     import torch
@@ -296,6 +306,12 @@ def main(argv=None):
     u = cfg.max_num_tx
     params = GenParams.from_config(cfg, num_tx=u, num_prbs=a.num_prbs, var_mcs=a.var_mcs, seed=a.seed)
     params.num_active = a.num_tx_eval or u
+    if a.channel != "iid":
+        params = scenario(a.channel, params)
+    if a.rx_corr is not None:
+        params = dataclasses.replace(params, rx_corr=rx_correlation(params.num_rx_ant, a.rx_corr))
+    # a correlated channel: the LMMSE estimator takes the spatial covariance unless -chest_2d keeps it out
+    chest3 = params.rx_corr is not None and not a.chest_2d
     systems = {n: "baseline_" + n for n in a.baselines}
     needs_h = {"perf_csi_lmmse", "lmmse_lmmse", "perf_csi_kbest", "lmmse_kbest"}
     gen = SlotGenerator(params, device=device, want_h=bool(needs_h & set(systems)) or a.soft_metrics)
@@ -311,7 +327,9 @@ def main(argv=None):
         # estimates the same matrices from the same slots
         if a.num_cov_slots < 1 or COV_SLOT_OFFSET <= len(ebno) * a.max_mc_iter * world * a.batch_size:
             raise ValueError("-num_cov_slots must be >= 1 and the Monte-Carlo slots must end below 2^40")
-        cov = estimate_covariance(gen, a.num_cov_slots, a.batch_size).matrices()
+        est = estimate_covariance(gen, a.num_cov_slots, a.batch_size)
+        cov = est.matrices()
+        R_s = est.space() if chest3 else None
     for name, system in systems.items():
         if system in KBestBaselineReceiver.SYSTEMS:
             rx = KBestBaselineReceiver(system, params, device=device, k=a.kbest_k)
@@ -321,7 +339,7 @@ def main(argv=None):
             # the filter is designed again at every Eb/N0 point (ChannelEstimator.prepare)
             rx = EstimatorBaselineReceiver(system, params, device=device)
             if cov is not None:
-                rx.set_covariance(*cov)
+                rx.set_covariance(*cov, R_s=R_s)
         else:
             rx = BaselineReceiver(system, params, device=device)
         note = baseline_note(name, rx)
@@ -337,6 +355,10 @@ def main(argv=None):
         d = res.as_dict()
         d.update(config=cfg.label, num_tx_eval=params.num_active, dmrs_symbols=list(dmrs_symbols(cfg)),
                  world=world, slots_per_s=res.slots / res.seconds)
+        if params.correlated:       # the iid run keeps the keys it always had
+            d.update(channel=a.channel, user_profiles=[list(x) for x in params.profiles()],
+                     rx_corr=a.rx_corr if a.rx_corr is not None else SCENARIOS.get(a.channel),
+                     chest="lmmse3" if chest3 else "lmmse")
         if base:
             d["baselines"] = {name: r.as_dict() for name, r in base.items()}
         for name, points in soft.items():

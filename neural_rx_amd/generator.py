@@ -8,8 +8,12 @@ variance (323-332), LS channel estimate -> the CGNN's inputs; and the counting s
 are not available here; the generator's channel is the seeded tapped-delay line stated in
 ``oracle/synth_ref.py`` and the counters are uncoded (hard decisions on the LLRs).
 
-Everything runs through ``libnrx.so`` (``nrx_generate_slots`` / ``nrx_count_errors``,
-include/nrx.h); torch tensors are only device containers.
+``GenParams.user_profiles`` / ``rx_corr`` (and ``scenario``) add what the reference's evaluation
+channel ``DoubleTDL`` defines in its own text: a delay and Doppler spread per user and gNB antenna
+correlation (utils/channel_models.py:20-161), through ``nrx_generate_slots_ex``.
+
+Everything runs through ``libnrx.so`` (``nrx_generate_slots`` / ``nrx_generate_slots_ex`` /
+``nrx_count_errors``, include/nrx.h); torch tensors are only device containers.
 """
 from __future__ import annotations
 
@@ -55,6 +59,10 @@ class GenParams:
     max_doppler_hz: float = 400.0
     subcarrier_spacing: float = 30e3
     seed: int = 1234
+    # per port (max_delay_s, max_doppler_hz), replacing the two scalars above; None = the scalars
+    user_profiles: Optional[Sequence] = None
+    # receive-antenna correlation, A x A Hermitian PSD (rx_correlation); None = i.i.d. antennas
+    rx_corr: Optional[np.ndarray] = None
 
     @classmethod
     def from_config(cls, cfg: NRXConfig | str, num_tx: Optional[int] = None, num_prbs: Optional[int] = None,
@@ -98,6 +106,83 @@ class GenParams:
         d.seed, d.slot_offset = self.seed, slot_offset
         return d
 
+    @property
+    def correlated(self) -> bool:
+        """the slots need ``nrx_generate_slots_ex``"""
+        return self.user_profiles is not None or self.rx_corr is not None
+
+    def profiles(self) -> list:
+        """(max_delay_s, max_doppler_hz) of every port"""
+        if self.user_profiles is None:
+            return [(float(self.max_delay_s), float(self.max_doppler_hz))] * self.num_tx
+        prof = [(float(a), float(b)) for a, b in self.user_profiles]
+        if len(prof) != self.num_tx:
+            raise ValueError(f"user_profiles needs one (max_delay_s, max_doppler_hz) per port: "
+                             f"{self.num_tx}, got {len(prof)}")
+        return prof
+
+    def rx_mix(self) -> Optional[np.ndarray]:
+        """``M = V diag(sqrt(mu)) V^H``, the Hermitian square root of ``rx_corr`` (complex128
+        [A, A], ``M M^H = rx_corr``), or None.  Eigenvalues below zero by rounding count as 0."""
+        if self.rx_corr is None:
+            return None
+        A = self.num_rx_ant
+        R = np.asarray(self.rx_corr, np.complex128)
+        if R.shape != (A, A) or not np.allclose(R, R.conj().T, rtol=0, atol=1e-12 * max(1.0, np.abs(R).max())):
+            raise ValueError(f"rx_corr must be a Hermitian {(A, A)} matrix")
+        mu, V = np.linalg.eigh(R)
+        if mu[0] < -1e-9 * max(mu[-1], 1e-300):
+            raise ValueError("rx_corr must be positive semi-definite")
+        return (V * np.sqrt(np.maximum(mu, 0.0))) @ V.conj().T
+
+
+def rx_correlation(num_rx_ant: int, alpha: float) -> np.ndarray:
+    """Receive-antenna correlation ``R[i][j] = alpha^((|i - j| / (A - 1))^2)`` (A = 1: ``[[1]]``),
+    float64 [A, A].  For A in {2, 4, 8} these are the exponent tables of the reference's
+    ``gnb_correlation_matrix`` (utils/channel_models.py:20-33; alpha = 0 / 0.9 for low / high
+    correlation, 96-107); the closed form extends them to any A.  It is a Gaussian kernel in the antenna index, hence positive semi-definite."""
+    A = int(num_rx_ant)
+    if A < 1:
+        raise ValueError("num_rx_ant must be >= 1")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("alpha must be in [0, 1]")
+    if A == 1:
+        return np.ones((1, 1))
+    i = np.arange(A)
+    e = (np.abs(i[:, None] - i[None, :]) / (A - 1.0)) ** 2
+    return np.where(e == 0, 1.0, float(alpha) ** e)
+
+
+# rms delay spread of the generator's delay profile over its max_delay_s (scenario docstring)
+RMS_OVER_MAX_DELAY = 0.23658
+SCENARIOS = {"double_tdl_low": 0.0, "double_tdl_high": 0.9}
+DOUBLE_TDL_USERS = ((100e-9, 400.0), (300e-9, 100.0))     # (rms delay spread, max Doppler) of port 0 / 1
+
+
+def scenario(name: str, params: GenParams) -> GenParams:
+    """``params`` on the reference's evaluation channel ``DoubleTDL`` (utils/channel_models.py:
+    39-161, ``channel_type_eval = "DoubleTDLlow"``): two users with different profiles -- port 0
+    delay spread 100 ns / 400 Hz Doppler, port 1 300 ns / 100 Hz -- and gNB antenna correlation
+    ``rx_correlation(A, alpha)``, alpha = 0 (``"double_tdl_low"``) or 0.9 (``"double_tdl_high"``).
+    It needs exactly two ports, as the reference's scripts/evaluate.py:177-180 does.
+
+    Delay spread.  The generator draws delays uniformly on [0, max] and weighs them by
+    exp(-3 tau / max), so its continuous PDP is p(x) ~ exp(-3 x) on x = tau / max in [0, 1]:
+    m0 = (1 - e^-3) / 3, E x = (1/9 - 4/9 e^-3) / m0 = 0.280936, E x^2 = (2/27 - 17/27 e^-3) / m0 =
+    0.134897, so the rms delay spread is sqrt(E x^2 - (E x)^2) max = 0.23658 max and
+    ``max_delay_s = DS / 0.23658``.
+
+    Two stated departures: the taps are still the generator's random ones (uniform delays,
+    sum-of-sinusoids Doppler), not the 3GPP TDL-B / TDL-C tables; and the reference's "medium"
+    correlation differs from "high" only on the UE side, which has one antenna here, so there is no
+    separate preset."""
+    if name not in SCENARIOS:
+        raise ValueError(f"scenario must be one of {tuple(SCENARIOS)}, got {name!r}")
+    if params.num_tx != 2:
+        raise ValueError(f"the DoubleTDL scenarios are defined for exactly two ports, got {params.num_tx}")
+    prof = [(ds / RMS_OVER_MAX_DELAY, fd) for ds, fd in DOUBLE_TDL_USERS]
+    return dataclasses.replace(params, user_profiles=prof, rx_corr=rx_correlation(params.num_rx_ant, SCENARIOS[name]))
+
 
 @dataclasses.dataclass
 class SlotBatch:
@@ -127,6 +212,19 @@ class SlotGenerator:
         self._lib = _lib.load()
         self._ws = None
         self._bufs = {}
+        self._chan = None
+        self._mix = None        # device copy of rx_mix(), uploaded once
+        if params.correlated:
+            c = _lib.nrx_gen_chan()
+            for u, (delay, doppler) in enumerate(params.profiles()):
+                c.max_delay_s[u], c.max_doppler_hz[u] = delay, doppler
+            M = params.rx_mix()
+            if M is not None:
+                torch = _torch()
+                m = np.ascontiguousarray(np.stack([M.real, M.imag], -1))
+                self._mix = torch.from_numpy(m).to(f"cuda:{device}")
+                c.rx_mix = self._mix.data_ptr()
+            self._chan = c
 
     def workspace_bytes(self, batch: int) -> int:
         n = ctypes.c_size_t()
@@ -175,8 +273,12 @@ class SlotGenerator:
         o.h_ls_real, o.h_ls_imag = ptr(sb.h_ls_real), ptr(sb.h_ls_imag)
         if stream is None:
             stream = torch.cuda.current_stream(sb.y.device).cuda_stream
-        _lib.check(self._lib.nrx_generate_slots(ctypes.byref(d), ctypes.byref(o), self._ws.data_ptr(),
-                                                self._ws.numel(), stream))
+        if self._chan is not None:
+            _lib.check(self._lib.nrx_generate_slots_ex(ctypes.byref(d), ctypes.byref(self._chan), ctypes.byref(o),
+                                                       self._ws.data_ptr(), self._ws.numel(), stream))
+        else:
+            _lib.check(self._lib.nrx_generate_slots(ctypes.byref(d), ctypes.byref(o), self._ws.data_ptr(),
+                                                    self._ws.numel(), stream))
         return sb
 
 
