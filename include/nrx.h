@@ -164,6 +164,10 @@ int nrx_forward_ex(nrx_handle* h, const nrx_io* io, int32_t y_layout, const floa
  *   dmrs_subcarrier_pos   [U][npil]               i32   pilot subcarriers within a PRB (device)
  *   llr                   [B][bits][U][F][T]      f32   out, LLR = log p(b=0)/p(b=1)
  *   h_hat                 [B][U][F][T][2A]        f32   out, refined estimate (NULL: skip)
+ * The contents of dmrs_ofdm_pos / dmrs_subcarrier_pos are device data the host never reads
+ * and are not validated: the caller keeps every entry inside 0..13 / 0..11 (any order,
+ * per user).  Entries outside that range are not a memory hazard (they only enter
+ * distances) but give a preprocessing the reference does not define.
  */
 typedef struct nrx_aerial_io {
   nrx_shape shape;           /* B, U = num_tx, F (multiple of 12), T = 14 */
@@ -190,6 +194,15 @@ int nrx_aerial_workspace_size(const nrx_handle* h, const nrx_aerial_io* io, size
  * host synchronisation. */
 int nrx_forward_aerial(nrx_handle* h, const nrx_aerial_io* io, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* The preprocessing of nrx_forward_aerial alone (the same two launches, through the same
+ * internal helper), into caller buffers:
+ * y [B][F][T][2A], h_hat [B][U][F][T][2A], pe [U][F][T][2], nn [U][T][12] (index into the
+ * per-PRB pilot list, i = k * npil + j); reads io->shape, num_dmrs_*, y_*, h_ls_*, dmrs_*_pos;
+ * ignores llr, h_hat, dmrs_port_mask, num_it, precision.  No workspace.  Asynchronous on
+ * `stream`. */
+int nrx_aerial_preprocess(const nrx_handle* h, const nrx_aerial_io* io, float* y, float* h_hat,
+                          float* pe, int32_t* nn, void* stream);
 
 /* Coded-bit layout of one LLR head (Sionna sign): out[B][U][n_data * bits] with
  * out[b][u][i * bits + k] = llr[b][u][f][t][k] for the i-th data RE, data_re[i] = t * F + f

@@ -34,7 +34,7 @@ EXPORTS = [
     "nrx_chest_lmmse", "nrx_chest_lin", "nrx_kbest_workspace_size", "nrx_kbest_detect",
     "nrx_llr_stats_workspace_size", "nrx_llr_stats", "nrx_nmse_workspace_size", "nrx_chest_nmse",
     "nrx_generate_slots_ex", "nrx_cov_space_workspace_size", "nrx_cov_space_accumulate",
-    "nrx_chest3_workspace_size", "nrx_chest_lmmse3",
+    "nrx_chest3_workspace_size", "nrx_chest_lmmse3", "nrx_aerial_preprocess",
 ]
 # enum nrx_y_layout
 Y_LAYOUTS = {"cgnn": 0, "sionna": 1, "split": 2}
@@ -403,6 +403,9 @@ def load(path: str = LIB_PATH):
     lib.nrx_aerial_workspace_size.restype = c.c_int
     lib.nrx_forward_aerial.argtypes = [c.c_void_p, P(nrx_aerial_io), c.c_void_p, c.c_size_t, c.c_void_p]
     lib.nrx_forward_aerial.restype = c.c_int
+    lib.nrx_aerial_preprocess.argtypes = [c.c_void_p, P(nrx_aerial_io), c.c_void_p, c.c_void_p, c.c_void_p,
+                                          c.c_void_p, c.c_void_p]
+    lib.nrx_aerial_preprocess.restype = c.c_int
     lib.nrx_llr_demap.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.c_int32,
                                   c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p]
     lib.nrx_llr_demap.restype = c.c_int

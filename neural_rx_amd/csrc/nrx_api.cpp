@@ -729,7 +729,35 @@ int check_aerial(const nrx_handle* h, const nrx_aerial_io* io) {
     return fail(NRX_ERR_SHAPE, "num_dmrs_subcarriers must be even and 2..12 (FOCC pairs)");
   return NRX_OK;
 }
+
+// The two preprocessing launches of the Aerial contract (NN table + PE, then y and h_hat), shared
+// by nrx_forward_aerial and nrx_aerial_preprocess so that both run the same code on the same
+// arguments.
+hipError_t aerial_prepare(const nrx_handle* h, const nrx_aerial_io* io, float* y, float* h_hat, float* pe,
+                          int32_t* nn, hipStream_t st) {
+  const nrx_shape& s = io->shape;
+  hipError_t e = launch_aerial_tables(io->dmrs_ofdm_pos, io->dmrs_subcarrier_pos, s.num_tx, io->num_dmrs_symbols,
+                                      io->num_dmrs_subcarriers, s.num_symbols, s.num_subcarriers, nn, pe, st);
+  if (e == hipSuccess)
+    e = launch_aerial_inputs(io->y_real, io->y_imag, io->h_ls_real, io->h_ls_imag, nn, s.batch, s.num_tx,
+                             s.num_subcarriers, s.num_symbols, h->desc.num_rx_ant, io->num_dmrs_symbols,
+                             io->num_dmrs_subcarriers, y, h_hat, st);
+  return e;
+}
 }  // namespace
+
+int nrx_aerial_preprocess(const nrx_handle* h, const nrx_aerial_io* io, float* y, float* h_hat, float* pe,
+                          int32_t* nn, void* stream) {
+  int rc = check_aerial(h, io);
+  if (rc) return rc;
+  if (!io->y_real || !io->y_imag || !io->h_ls_real || !io->h_ls_imag || !io->dmrs_ofdm_pos ||
+      !io->dmrs_subcarrier_pos)
+    return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (!y || !h_hat || !pe || !nn) return fail(NRX_ERR_INVALID_ARG, "null output pointer");
+  hipError_t e = aerial_prepare(h, io, y, h_hat, pe, nn, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "aerial preprocessing launch");
+  return NRX_OK;
+}
 
 int nrx_aerial_workspace_size(const nrx_handle* h, const nrx_aerial_io* io, size_t* bytes) {
   int rc = check_aerial(h, io);
@@ -756,7 +784,6 @@ int nrx_forward_aerial(nrx_handle* h, const nrx_aerial_io* io, void* workspace, 
   if (!workspace || workspace_bytes < w.total)
     return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(w.total) + " bytes");
   const nrx_shape& s = io->shape;
-  const int A = h->desc.num_rx_ant;
   hipStream_t st = (hipStream_t)stream;
   {
     nrx_io q{};
@@ -766,12 +793,7 @@ int nrx_forward_aerial(nrx_handle* h, const nrx_aerial_io* io, void* workspace, 
     bool takes = false;
     if ((rc = fused_busy(h, &q, st, &takes))) return rc;
   }
-  hipError_t e = launch_aerial_tables(io->dmrs_ofdm_pos, io->dmrs_subcarrier_pos, s.num_tx, io->num_dmrs_symbols,
-                                      io->num_dmrs_subcarriers, s.num_symbols, s.num_subcarriers, w.nn, w.pe, st);
-  if (e == hipSuccess)
-    e = launch_aerial_inputs(io->y_real, io->y_imag, io->h_ls_real, io->h_ls_imag, w.nn, s.batch, s.num_tx,
-                             s.num_subcarriers, s.num_symbols, A, io->num_dmrs_symbols, io->num_dmrs_subcarriers,
-                             w.y, w.h, st);
+  hipError_t e = aerial_prepare(h, io, w.y, w.h, w.pe, w.nn, st);
   if (e != hipSuccess) return hip_fail(e, "aerial preprocessing launch");
   nrx_io cio{};
   cio.shape = s;

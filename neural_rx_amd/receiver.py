@@ -264,6 +264,64 @@ class CGNNEngine:
         return out
 
     # -------------------------------------------------------------- Aerial contract
+    def _aerial_io(self, y_real, y_imag, h_ls_real, h_ls_imag, dmrs_ofdm_pos, dmrs_subcarrier_pos, U):
+        """The input half of an ``nrx_aerial_io`` for U users: shapes and types checked, ``h_ls``
+        and the DMRS positions narrowed to the first U users (``h_hat[:, 0, :, :num_tx]``,
+        neural_rx.py:1709), everything contiguous.  Returns ``(io, tensors)``; the caller keeps
+        ``tensors`` alive until the stream consumed them."""
+        torch = _torch()
+        sp = self.spec
+        B, F, T, A = y_real.shape
+        if T != NUM_SYMBOLS or A != sp.num_rx_ant:
+            raise ValueError(f"y must be [B,F,14,{sp.num_rx_ant}], got {tuple(y_real.shape)}")
+        nsym, npil = dmrs_ofdm_pos.shape[1], dmrs_subcarrier_pos.shape[1]
+        if h_ls_real.shape[1] != nsym * (F // 12) * npil or h_ls_real.shape[3] != A:
+            raise ValueError(f"h_ls must be [B,{nsym * (F // 12) * npil},U,{A}], got {tuple(h_ls_real.shape)}")
+        if tuple(y_imag.shape) != tuple(y_real.shape) or tuple(h_ls_imag.shape) != tuple(h_ls_real.shape) or \
+                h_ls_real.shape[0] != B:
+            raise ValueError("y_imag / h_ls_imag must have the shapes of y_real / h_ls_real, h_ls the batch of y")
+        if h_ls_real.shape[2] < U or dmrs_ofdm_pos.shape[0] < U or dmrs_subcarrier_pos.shape[0] < U:
+            raise ValueError(f"h_ls and the dmrs positions must hold at least {U} users")
+        if h_ls_real.shape[2] != U:
+            h_ls_real, h_ls_imag = h_ls_real[:, :, :U], h_ls_imag[:, :, :U]
+        f32 = [y_real, y_imag, h_ls_real, h_ls_imag]
+        for t in f32:
+            if not t.is_cuda or t.dtype != torch.float32:
+                raise ValueError("y / h_ls / dmrs_port_mask must be float32 CUDA tensors")
+        pos = [dmrs_ofdm_pos[:U], dmrs_subcarrier_pos[:U]]
+        for t in pos:
+            if not t.is_cuda or t.dtype != torch.int32:
+                raise ValueError("dmrs positions must be int32 CUDA tensors")
+        kept = [t.contiguous() for t in f32 + pos]
+        io = _lib.nrx_aerial_io()
+        io.shape = _lib.nrx_shape(B, U, F, NUM_SYMBOLS)
+        io.num_dmrs_symbols, io.num_dmrs_subcarriers = nsym, npil
+        io.y_real, io.y_imag = kept[0].data_ptr(), kept[1].data_ptr()
+        io.h_ls_real, io.h_ls_imag = kept[2].data_ptr(), kept[3].data_ptr()
+        io.dmrs_ofdm_pos, io.dmrs_subcarrier_pos = kept[4].data_ptr(), kept[5].data_ptr()
+        return io, kept
+
+    def aerial_preprocess(self, y_real, y_imag, h_ls_real, h_ls_imag, dmrs_ofdm_pos, dmrs_subcarrier_pos,
+                          num_tx=None, stream=None):
+        """The preprocessing of ``forward_aerial`` alone (include/nrx.h nrx_aerial_preprocess; the
+        same two launches): ``(y [B,F,T,2A], h_hat [B,U,F,T,2A], pe [U,F,T,2], nn [U,T,12] int32)``
+        for the first ``num_tx`` users (default: every row of ``dmrs_ofdm_pos``)."""
+        torch = _torch()
+        U = dmrs_ofdm_pos.shape[0] if num_tx is None else int(num_tx)
+        io, kept = self._aerial_io(y_real, y_imag, h_ls_real, h_ls_imag, dmrs_ofdm_pos, dmrs_subcarrier_pos, U)
+        B, F, A = kept[0].shape[0], kept[0].shape[1], self.spec.num_rx_ant
+        dev = kept[0].device
+        y = torch.empty((B, F, NUM_SYMBOLS, 2 * A), dtype=torch.float32, device=dev)
+        h = torch.empty((B, U, F, NUM_SYMBOLS, 2 * A), dtype=torch.float32, device=dev)
+        pe = torch.empty((U, F, NUM_SYMBOLS, 2), dtype=torch.float32, device=dev)
+        nn = torch.empty((U, NUM_SYMBOLS, 12), dtype=torch.int32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self._lib.nrx_aerial_preprocess(self._h, ctypes.byref(io), y.data_ptr(), h.data_ptr(),
+                                                   pe.data_ptr(), nn.data_ptr(), stream))
+        self._last_inputs = kept
+        return y, h, pe, nn
+
     def forward_aerial(self, y_real, y_imag, h_ls_real, h_ls_imag, dmrs_port_mask, dmrs_ofdm_pos,
                        dmrs_subcarrier_pos, num_it=None, precision="f16", want_h=True, stream=None):
         """NeuralReceiverONNX I/O on the GPU (include/nrx.h, nrx_forward_aerial).
@@ -274,38 +332,20 @@ class CGNNEngine:
         Returns ``(llr [B,bits,U,F,T], h_hat [B,U,F,T,2A] or None)`` with the Aerial sign."""
         torch = _torch()
         sp = self.spec
-        B, F, T, A = y_real.shape
         U = dmrs_port_mask.shape[1]
-        if T != NUM_SYMBOLS or A != sp.num_rx_ant:
-            raise ValueError(f"y must be [B,F,14,{sp.num_rx_ant}], got {tuple(y_real.shape)}")
-        nsym, npil = dmrs_ofdm_pos.shape[1], dmrs_subcarrier_pos.shape[1]
-        if h_ls_real.shape[1] != nsym * (F // 12) * npil or h_ls_real.shape[3] != A:
-            raise ValueError(f"h_ls must be [B,{nsym * (F // 12) * npil},U,{A}], got {tuple(h_ls_real.shape)}")
-        if h_ls_real.shape[2] != U:        # h_hat[:, 0, :, :num_tx] (neural_rx.py:1709)
-            h_ls_real, h_ls_imag = h_ls_real[:, :, :U], h_ls_imag[:, :, :U]
-        f32 = [y_real, y_imag, h_ls_real, h_ls_imag, dmrs_port_mask]
-        for t in f32:
-            if not t.is_cuda or t.dtype != torch.float32:
-                raise ValueError("y / h_ls / dmrs_port_mask must be float32 CUDA tensors")
-        pos = [dmrs_ofdm_pos[:U], dmrs_subcarrier_pos[:U]]
-        for t in pos:
-            if not t.is_cuda or t.dtype != torch.int32:
-                raise ValueError("dmrs positions must be int32 CUDA tensors")
-        y_real, y_imag, h_ls_real, h_ls_imag, mask = [t.contiguous() for t in f32]
-        ofdm, scp = [t.contiguous() for t in pos]
+        if not dmrs_port_mask.is_cuda or dmrs_port_mask.dtype != torch.float32:
+            raise ValueError("y / h_ls / dmrs_port_mask must be float32 CUDA tensors")
+        io, kept = self._aerial_io(y_real, y_imag, h_ls_real, h_ls_imag, dmrs_ofdm_pos, dmrs_subcarrier_pos, U)
+        y_real, y_imag, h_ls_real, h_ls_imag, ofdm, scp = kept
+        B, F, A = y_real.shape[0], y_real.shape[1], sp.num_rx_ant
+        mask = dmrs_port_mask.contiguous()
         bits = sp.bits_max if sp.masking else sp.bits[0]
         llr = torch.empty((B, bits, U, F, NUM_SYMBOLS), dtype=torch.float32, device=y_real.device)
         h = (torch.empty((B, U, F, NUM_SYMBOLS, 2 * A), dtype=torch.float32, device=y_real.device)
              if want_h else None)
-        io = _lib.nrx_aerial_io()
-        io.shape = _lib.nrx_shape(B, U, F, NUM_SYMBOLS)
         io.num_it = sp.num_it if num_it is None else num_it
         io.precision = _lib.PRECISIONS[precision]
-        io.num_dmrs_symbols, io.num_dmrs_subcarriers = nsym, npil
-        io.y_real, io.y_imag = y_real.data_ptr(), y_imag.data_ptr()
-        io.h_ls_real, io.h_ls_imag = h_ls_real.data_ptr(), h_ls_imag.data_ptr()
         io.dmrs_port_mask = mask.data_ptr()
-        io.dmrs_ofdm_pos, io.dmrs_subcarrier_pos = ofdm.data_ptr(), scp.data_ptr()
         io.llr = llr.data_ptr()
         io.h_hat = h.data_ptr() if h is not None else None
         nbytes = ctypes.c_size_t()

@@ -11,6 +11,10 @@ reference's golden FOCC vector; GPU tests compare nrx_forward_aerial with it:
 * end to end against the fp64 oracle: f32x LLR max-abs < 1e-3, h_hat < 1e-4; f16 within the
   gates of tests/test_gpu_parity.py;
 * shapes of the reference's TRT engine at 132 PRB (real_time_nrx.ipynb:776-777).
+
+This file runs the nrx_rt layout (symbols (2, 11), six type-1 pilots, A = 4) with the trained
+weights; the other DMRS layouts, sizes and LLR heads the contract accepts are in
+tests/test_aerial_layouts.py (oracle) and tests/test_gpu_aerial_contract.py (GPU).
 """
 import numpy as np
 import pytest
