@@ -73,7 +73,9 @@ class CovarianceEstimator:
     and returns the Hermitian Toeplitz ``(R_f [F, F], R_t [14, 14])`` as numpy complex128.
     ``accumulate`` also adds the spatial sums (``nrx_cov_space_accumulate``); ``space()`` returns
     ``R_s [A, A]``, the identity up to estimation noise unless the generator correlates its
-    antennas (module docstring)."""
+    antennas (module docstring).  ``accumulate(..., workspace=(ws, ws_space))`` runs the two launches
+    in the caller's uint8 device tensors (any content) instead of the estimator's own;
+    ``last_workspace_bytes`` is the pair of sizes the ``*_workspace_size`` calls asked for."""
 
     def __init__(self, params: GenParams, device: int = 0):
         torch = _torch()
@@ -87,9 +89,14 @@ class CovarianceEstimator:
         self.slots = 0
         self._ws = None
         self._ws_s = None
+        self.last_workspace_bytes = (0, 0)
 
-    def accumulate(self, sb: SlotBatch, stream=None) -> None:
+    def accumulate(self, sb: SlotBatch, stream=None, workspace=None) -> None:
         torch = _torch()
+        if workspace is not None:
+            for w in workspace:
+                if w.device != self.acc.device or w.dtype != torch.uint8 or not w.is_contiguous():
+                    raise ValueError(f"workspace must be two contiguous uint8 tensors on {self.acc.device}")
         h = sb.h
         if h is None:
             raise ValueError("the covariance needs the true channel: SlotGenerator(want_h=True)")
@@ -104,20 +111,29 @@ class CovarianceEstimator:
         io.h, io.acc = h.data_ptr(), self.acc.data_ptr()
         n = ctypes.c_size_t()
         _lib.check(self._lib.nrx_cov_workspace_size(ctypes.byref(io), ctypes.byref(n)))
-        if self._ws is None or self._ws.numel() < n.value:
-            self._ws = torch.empty(n.value, dtype=torch.uint8, device=self.acc.device)
+        need = n.value
+        if workspace is not None:
+            ws = workspace[0]
+        else:
+            if self._ws is None or self._ws.numel() < n.value:
+                self._ws = torch.empty(n.value, dtype=torch.uint8, device=self.acc.device)
+            ws = self._ws
         if stream is None:
             stream = torch.cuda.current_stream(self.acc.device).cuda_stream
-        _lib.check(self._lib.nrx_cov_accumulate(ctypes.byref(io), self._ws.data_ptr(), self._ws.numel(), stream))
+        _lib.check(self._lib.nrx_cov_accumulate(ctypes.byref(io), ws.data_ptr(), ws.numel(), stream))
         so = _lib.nrx_cov_space_io()
         so.batch, so.num_tx, so.num_subcarriers, so.num_symbols = B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS
         so.num_rx_ant = p.num_rx_ant
         so.h, so.acc = h.data_ptr(), self.acc_s.data_ptr()
         _lib.check(self._lib.nrx_cov_space_workspace_size(ctypes.byref(so), ctypes.byref(n)))
-        if self._ws_s is None or self._ws_s.numel() < n.value:
-            self._ws_s = torch.empty(n.value, dtype=torch.uint8, device=self.acc.device)
-        _lib.check(self._lib.nrx_cov_space_accumulate(ctypes.byref(so), self._ws_s.data_ptr(), self._ws_s.numel(),
-                                                      stream))
+        self.last_workspace_bytes = (need, n.value)
+        if workspace is not None:
+            ws = workspace[1]
+        else:
+            if self._ws_s is None or self._ws_s.numel() < n.value:
+                self._ws_s = torch.empty(n.value, dtype=torch.uint8, device=self.acc.device)
+            ws = self._ws_s
+        _lib.check(self._lib.nrx_cov_space_accumulate(ctypes.byref(so), ws.data_ptr(), ws.numel(), stream))
         self.slots += B
 
     def lags(self):
@@ -327,6 +343,7 @@ class ChannelEstimator:
         self._dev = None
         self._out = None
         self._ws = None
+        self.last_workspace_bytes = 0      # what nrx_chest3_workspace_size asked for the last call
         if tables is not None:
             self._set_design(tables)
 
@@ -367,7 +384,10 @@ class ChannelEstimator:
             self._set_design(lmmse_design(self.R_f, self.R_t, self.p, no))
         return self.design
 
-    def __call__(self, sb: SlotBatch, no: float, out=None, stream=None):
+    def __call__(self, sb: SlotBatch, no: float, out=None, stream=None, workspace=None):
+        """``workspace`` (lmmse3 only, the one estimator with a workspace): a uint8 device tensor
+        of at least ``nrx_chest3_workspace_size`` bytes (``last_workspace_bytes`` after a call),
+        any content, instead of the estimator's own."""
         torch = _torch()
         p = self.p
         hh = sb.h_hat
@@ -399,7 +419,9 @@ class ChannelEstimator:
         if stream is None:
             stream = torch.cuda.current_stream(hh.device).cuda_stream
         if self.kind == "lmmse3":
-            return self._lmmse3(io, no, out, stream)
+            return self._lmmse3(io, no, out, stream, workspace)
+        if workspace is not None:
+            raise ValueError(f"the {self.kind} estimator takes no workspace")
         if self.kind == "lmmse":
             d = self.prepare(no)
             if self._dev is None:
@@ -412,7 +434,7 @@ class ChannelEstimator:
         return out
 
 
-    def _lmmse3(self, io2, no, out, stream):
+    def _lmmse3(self, io2, no, out, stream, workspace=None):
         torch = _torch()
         d = self.prepare(no)
         if self._dev is None:
@@ -430,9 +452,16 @@ class ChannelEstimator:
             setattr(io, k, self._dev[k].data_ptr())
         n = ctypes.c_size_t()
         _lib.check(self._lib.nrx_chest3_workspace_size(ctypes.byref(io), ctypes.byref(n)))
-        if self._ws is None or self._ws.numel() < n.value:
-            self._ws = torch.empty(n.value, dtype=torch.uint8, device=out.device)
-        _lib.check(self._lib.nrx_chest_lmmse3(ctypes.byref(io), self._ws.data_ptr(), self._ws.numel(), stream))
+        self.last_workspace_bytes = n.value
+        if workspace is not None:
+            if workspace.device != out.device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+                raise ValueError(f"workspace must be a contiguous uint8 tensor on {out.device}")
+            ws = workspace
+        else:
+            if self._ws is None or self._ws.numel() < n.value:
+                self._ws = torch.empty(n.value, dtype=torch.uint8, device=out.device)
+            ws = self._ws
+        _lib.check(self._lib.nrx_chest_lmmse3(ctypes.byref(io), ws.data_ptr(), ws.numel(), stream))
         return out
 
 

@@ -257,13 +257,21 @@ class SlotGenerator:
         self._bufs = {key: sb}
         return sb
 
-    def __call__(self, batch: int, no: float, slot_offset: int = 0, stream=None, out: Optional[SlotBatch] = None
-                 ) -> SlotBatch:
+    def __call__(self, batch: int, no: float, slot_offset: int = 0, stream=None, out: Optional[SlotBatch] = None,
+                 workspace=None) -> SlotBatch:
+        """``workspace``: a uint8 device tensor of at least ``workspace_bytes(batch)`` bytes, any
+        content, to run this call in instead of the generator's own."""
         torch = _torch()
         sb = out if out is not None else self._alloc(batch)
-        nbytes = self.workspace_bytes(batch)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{self.device}")
+        if workspace is not None:
+            if not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+                raise ValueError("workspace must be a contiguous uint8 CUDA tensor")
+            ws = workspace
+        else:
+            nbytes = self.workspace_bytes(batch)
+            if self._ws is None or self._ws.numel() < nbytes:
+                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{self.device}")
+            ws = self._ws
         d = self.p.desc(batch, no, slot_offset)
         o = _lib.nrx_gen_out()
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
@@ -275,10 +283,10 @@ class SlotGenerator:
             stream = torch.cuda.current_stream(sb.y.device).cuda_stream
         if self._chan is not None:
             _lib.check(self._lib.nrx_generate_slots_ex(ctypes.byref(d), ctypes.byref(self._chan), ctypes.byref(o),
-                                                       self._ws.data_ptr(), self._ws.numel(), stream))
+                                                       ws.data_ptr(), ws.numel(), stream))
         else:
-            _lib.check(self._lib.nrx_generate_slots(ctypes.byref(d), ctypes.byref(o), self._ws.data_ptr(),
-                                                    self._ws.numel(), stream))
+            _lib.check(self._lib.nrx_generate_slots(ctypes.byref(d), ctypes.byref(o), ws.data_ptr(), ws.numel(),
+                                                    stream))
         return sb
 
 

@@ -39,15 +39,18 @@ class KBestDetector:
     the true channel), active [B, U] f32, mcs [B, U] u8 or None (= MCS 0), contiguous on the device.
     ``k`` survivors per level (1..64), LLRs clipped to ``+-llr_clip``.  Every element of ``out`` is
     written, so a reused buffer needs no clearing.  The detector owns its workspace and keeps it
-    from call to call (it grows with the batch)."""
+    from call to call (it grows with the batch); ``workspace=`` (a uint8 tensor on the device, at
+    least ``nrx_kbest_workspace_size`` bytes, any content) runs one call in the caller's instead."""
 
     def __init__(self, device: int = 0):
         self.device = device
         self._lib = _lib.load()
         self._ws = None
+        self.last_workspace_bytes = 0      # what nrx_kbest_workspace_size asked for the last call
 
     def __call__(self, y, h, active, mcs, mcs_bits: Sequence[int], no: float, dmrs_symbols: Sequence[int],
-                 err_var: float = 0.0, k: int = MAX_K, llr_clip: float = 20.0, out=None, stream=None):
+                 err_var: float = 0.0, k: int = MAX_K, llr_clip: float = 20.0, out=None, stream=None,
+                 workspace=None):
         torch = _torch()
         B, U, F, T, A2 = h.shape
         if h.device != torch.device(f"cuda:{self.device}"):
@@ -81,11 +84,18 @@ class KBestDetector:
         io.mcs = mcs.data_ptr() if mcs is not None else None
         need = ctypes.c_size_t()
         _lib.check(self._lib.nrx_kbest_workspace_size(ctypes.byref(io), ctypes.byref(need)))
-        if self._ws is None or self._ws.numel() < need.value:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=h.device)
+        self.last_workspace_bytes = need.value
+        if workspace is not None:
+            if workspace.device != h.device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+                raise ValueError(f"workspace must be a contiguous uint8 tensor on {h.device}")
+            ws = workspace
+        else:
+            if self._ws is None or self._ws.numel() < need.value:
+                self._ws = torch.empty(need.value, dtype=torch.uint8, device=h.device)
+            ws = self._ws
         if stream is None:
             stream = torch.cuda.current_stream(h.device).cuda_stream
-        _lib.check(self._lib.nrx_kbest_detect(ctypes.byref(io), self._ws.data_ptr(), self._ws.numel(), stream))
+        _lib.check(self._lib.nrx_kbest_detect(ctypes.byref(io), ws.data_ptr(), ws.numel(), stream))
         return out
 
 

@@ -160,8 +160,25 @@ class CGNNEngine:
                                                    _lib.Y_LAYOUTS[y_layout], ctypes.byref(out)))
         return out.value
 
-    def _workspace(self, nbytes: int):
+    def aerial_workspace_bytes(self, batch, num_tx, num_subcarriers, num_dmrs_symbols=2, num_dmrs_subcarriers=6,
+                               precision="f16") -> int:
+        """What ``forward_aerial`` needs for the shape (include/nrx.h nrx_aerial_workspace_size)."""
+        io = _lib.nrx_aerial_io()
+        io.shape = _lib.nrx_shape(batch, num_tx, num_subcarriers, NUM_SYMBOLS)
+        io.num_dmrs_symbols, io.num_dmrs_subcarriers = num_dmrs_symbols, num_dmrs_subcarriers
+        io.precision = _lib.PRECISIONS[precision]
+        out = ctypes.c_size_t()
+        _lib.check(self._lib.nrx_aerial_workspace_size(self._h, ctypes.byref(io), ctypes.byref(out)))
+        return out.value
+
+    def _workspace(self, nbytes: int, given=None):
+        """The cached buffer, grown to ``nbytes`` -- or the caller's ``workspace=`` tensor, passed
+        on as it is: the C call checks its size (NRX_ERR_WORKSPACE when it is too small)."""
         torch = _torch()
+        if given is not None:
+            if not given.is_cuda or given.dtype != torch.uint8 or not given.is_contiguous():
+                raise ValueError("workspace must be a contiguous uint8 CUDA tensor")
+            return given
         ws = self._ws.get("buf")
         if ws is None or ws.numel() < nbytes:
             ws = torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{self.device}")
@@ -180,13 +197,15 @@ class CGNNEngine:
 
     # -------------------------------------------------------------- forward
     def forward(self, y, pe, h_hat, active, mcs_mask=None, num_it=None, precision="f16",
-                out=None, want_h=True, stream=None, y_layout="cgnn", y_imag=None):
+                out=None, want_h=True, stream=None, y_layout="cgnn", y_imag=None, workspace=None):
         """All inputs are float32 CUDA tensors in the CGNN layout (see include/nrx.h), except
         ``y`` with ``y_layout``: "sionna" = the complex64 resource grid ``[B,1,A,14,F]``
         CGNNOFDM.forward receives, "split" = ``y`` / ``y_imag`` = rx_slot_real / imag
         ``[B,F,14,A]`` (NeuralReceiverONNX); the layout change runs in libnrx
-        (``nrx_forward_ex``).  Returns ``(llr [H,B,U,F,T,bits_max], h_ref [B,U,F,T,2A] or
-        None)``."""
+        (``nrx_forward_ex``).  ``workspace``: a uint8 CUDA tensor of at least
+        ``workspace_bytes(...)`` bytes to run in (its ``numel()`` is the C call's
+        ``workspace_bytes``; its content on entry is irrelevant); default: the engine's cached
+        buffer.  Returns ``(llr [H,B,U,F,T,bits_max], h_ref [B,U,F,T,2A] or None)``."""
         torch = _torch()
         sp = self.spec
         A = sp.num_rx_ant
@@ -229,7 +248,7 @@ class CGNNEngine:
         llr, h_ref = out
         prec = _lib.PRECISIONS[precision]
         nbytes = self.workspace_bytes(B, U, F, precision, y_layout)
-        ws = self._workspace(nbytes)
+        ws = self._workspace(nbytes, workspace)
         io = _lib.nrx_io()
         io.shape = _lib.nrx_shape(B, U, F, NUM_SYMBOLS)
         io.num_it = sp.num_it if num_it is None else num_it
@@ -323,12 +342,15 @@ class CGNNEngine:
         return y, h, pe, nn
 
     def forward_aerial(self, y_real, y_imag, h_ls_real, h_ls_imag, dmrs_port_mask, dmrs_ofdm_pos,
-                       dmrs_subcarrier_pos, num_it=None, precision="f16", want_h=True, stream=None):
+                       dmrs_subcarrier_pos, num_it=None, precision="f16", want_h=True, stream=None,
+                       out=None, workspace=None):
         """NeuralReceiverONNX I/O on the GPU (include/nrx.h, nrx_forward_aerial).
 
         ``y_real/imag [B,F,T,A]``, ``h_ls_real/imag [B,Npil,U,A]`` (LS at the DMRS pilots,
         pilot p = (k * F/12 + prb) * npil + j), ``dmrs_port_mask [B,U]`` float,
         ``dmrs_ofdm_pos [U,nsym]`` / ``dmrs_subcarrier_pos [U,npil]`` int32 CUDA tensors.
+        ``out``: ``(llr, h_hat or None)`` to write instead of fresh tensors; ``workspace``: as in
+        ``forward``, sized by ``aerial_workspace_bytes``.
         Returns ``(llr [B,bits,U,F,T], h_hat [B,U,F,T,2A] or None)`` with the Aerial sign."""
         torch = _torch()
         sp = self.spec
@@ -340,9 +362,11 @@ class CGNNEngine:
         B, F, A = y_real.shape[0], y_real.shape[1], sp.num_rx_ant
         mask = dmrs_port_mask.contiguous()
         bits = sp.bits_max if sp.masking else sp.bits[0]
-        llr = torch.empty((B, bits, U, F, NUM_SYMBOLS), dtype=torch.float32, device=y_real.device)
-        h = (torch.empty((B, U, F, NUM_SYMBOLS, 2 * A), dtype=torch.float32, device=y_real.device)
-             if want_h else None)
+        if out is None:
+            out = (torch.empty((B, bits, U, F, NUM_SYMBOLS), dtype=torch.float32, device=y_real.device),
+                   torch.empty((B, U, F, NUM_SYMBOLS, 2 * A), dtype=torch.float32, device=y_real.device)
+                   if want_h else None)
+        llr, h = out
         io.num_it = sp.num_it if num_it is None else num_it
         io.precision = _lib.PRECISIONS[precision]
         io.dmrs_port_mask = mask.data_ptr()
@@ -350,7 +374,7 @@ class CGNNEngine:
         io.h_hat = h.data_ptr() if h is not None else None
         nbytes = ctypes.c_size_t()
         _lib.check(self._lib.nrx_aerial_workspace_size(self._h, ctypes.byref(io), ctypes.byref(nbytes)))
-        ws = self._workspace(nbytes.value)
+        ws = self._workspace(nbytes.value, workspace)
         if stream is None:
             stream = torch.cuda.current_stream(y_real.device).cuda_stream
         _lib.check(self._lib.nrx_forward_aerial(self._h, ctypes.byref(io), ws.data_ptr(), ws.numel(), stream))

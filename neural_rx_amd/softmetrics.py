@@ -158,20 +158,27 @@ class SoftAccumulator:
         self.ref = self.f64[n * S + U:]
         self._ws = None
         self._ws_bytes = {}
+        self.last_workspace_bytes = 0      # what the *_workspace_size call asked for the last add_*
         self._total = None         # (i64, f64) of the last reduce, dropped by the next add
         self._lib = _lib.load() if device is not None else None
 
-    def _workspace(self, size_fn, io, key):
-        """the workspace, grown to what ``size_fn(io)`` asks for (asked once per shape ``key``)"""
+    def _workspace(self, size_fn, io, key, given=None):
+        """(pointer, bytes) of the workspace, grown to what ``size_fn(io)`` asks for (asked once per
+        shape ``key``) -- or of the caller's ``workspace=`` (a uint8 tensor on the device, any content)"""
         torch = _torch()
         nbytes = self._ws_bytes.get(key)
         if nbytes is None:
             n = ctypes.c_size_t()
             _lib.check(size_fn(ctypes.byref(io), ctypes.byref(n)))
             nbytes = self._ws_bytes[key] = n.value
+        self.last_workspace_bytes = nbytes
+        if given is not None:
+            if given.device != self.i64.device or given.dtype != torch.uint8 or not given.is_contiguous():
+                raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.i64.device}")
+            return given.data_ptr(), given.numel()
         if self._ws is None or self._ws.numel() * 8 < nbytes:
             self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=self.i64.device)
-        return self._ws
+        return self._ws.data_ptr(), self._ws.numel() * 8
 
     def _on_device(self, **tensors):
         if self._lib is None:
@@ -180,7 +187,7 @@ class SoftAccumulator:
             if t is not None and (t.device != self.i64.device or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous tensor on {self.i64.device}")
 
-    def add_llr(self, llr, bits, active, mcs, dmrs_symbols: Sequence[int], stream=None):
+    def add_llr(self, llr, bits, active, mcs, dmrs_symbols: Sequence[int], stream=None, workspace=None):
         """llr [H, B, U, F, T, bits_stride] f32 (head = MCS if H > 1), bits [B, U, F, T, bits_stride] u8,
         active [B, U] f32, mcs [B, U] u8 or None (= MCS 0)."""
         torch = _torch()
@@ -206,13 +213,13 @@ class SoftAccumulator:
         io.llr, io.bits, io.active = llr.data_ptr(), bits.data_ptr(), active.data_ptr()
         io.mcs = mcs.data_ptr() if mcs is not None else None
         io.loss, io.cnt, io.nonfinite = self.loss.data_ptr(), self.cnt.data_ptr(), self.nonfinite.data_ptr()
-        ws = self._workspace(self._lib.nrx_llr_stats_workspace_size, io, ("llr", B, F))
+        ws, ws_bytes = self._workspace(self._lib.nrx_llr_stats_workspace_size, io, ("llr", B, F), workspace)
         if stream is None:
             stream = torch.cuda.current_stream(llr.device).cuda_stream
-        _lib.check(self._lib.nrx_llr_stats(ctypes.byref(io), ws.data_ptr(), ws.numel() * 8, stream))
+        _lib.check(self._lib.nrx_llr_stats(ctypes.byref(io), ws, ws_bytes, stream))
         self._total = None
 
-    def add_channel(self, h_est, h_true, active, symbol_mask: int = 0, stream=None):
+    def add_channel(self, h_est, h_true, active, symbol_mask: int = 0, stream=None, workspace=None):
         """h_est, h_true [B, U, F, T, 2A] f32, active [B, U] f32; ``symbol_mask`` bit t selects symbol t
         (0: all 14)."""
         torch = _torch()
@@ -229,10 +236,10 @@ class SoftAccumulator:
         io.num_rx_ant, io.symbol_mask = A2 // 2, int(symbol_mask)
         io.h_est, io.h_true, io.active = h_est.data_ptr(), h_true.data_ptr(), active.data_ptr()
         io.err, io.ref, io.items = self.err.data_ptr(), self.ref.data_ptr(), self.items.data_ptr()
-        ws = self._workspace(self._lib.nrx_nmse_workspace_size, io, ("nmse", B, F))
+        ws, ws_bytes = self._workspace(self._lib.nrx_nmse_workspace_size, io, ("nmse", B, F), workspace)
         if stream is None:
             stream = torch.cuda.current_stream(h_true.device).cuda_stream
-        _lib.check(self._lib.nrx_chest_nmse(ctypes.byref(io), ws.data_ptr(), ws.numel() * 8, stream))
+        _lib.check(self._lib.nrx_chest_nmse(ctypes.byref(io), ws, ws_bytes, stream))
         self._total = None
 
     def reduce(self, dist=None):

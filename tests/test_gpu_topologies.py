@@ -238,18 +238,28 @@ def dispatch_model(spec, B, U, F, num_it, mask, fused, cus):
     return "strips24", n
 
 
-def run_sched(case, mask, fused=False, want_h=True, mcs_mask="case"):
-    """One f16 forward under a schedule mask; returns (llr_raw, h or None, profile counts)."""
+def upload(case):
+    """The case's input tensors on the device, keyed as run_sched's ``dev`` takes them."""
+    import torch
+    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()  # noqa: E731
+    return {k: t(getattr(case, k)) for k in ("y", "pe", "h_hat", "active", "mcs_mask")}
+
+
+def run_sched(case, mask, fused=False, want_h=True, mcs_mask="case", precision="f16", dev=None, **forward_kw):
+    """One forward (f16 unless ``precision`` says otherwise) under a schedule mask; returns
+    (llr_raw, h or None, profile counts).  ``dev``: the inputs already on the device (``upload``,
+    or tensors placed by the caller), uploaded here otherwise; ``forward_kw`` goes on to
+    ``CGNNEngine.forward`` (workspace=, out=, y_layout=, y_imag=)."""
     import torch
     eng = engine_for(case)
-    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()  # noqa: E731
+    d = dev if dev is not None else upload(case)
     eng.fused_config(enable=fused)
     eng.update_schedule(mask)
     try:
         eng.profile(True)
-        llr, h = eng.forward(t(case.y), t(case.pe), t(case.h_hat), t(case.active),
-                             t(case.mcs_mask) if isinstance(mcs_mask, str) else mcs_mask,
-                             num_it=case.num_it, precision="f16", want_h=want_h)
+        llr, h = eng.forward(d["y"], d["pe"], d["h_hat"], d["active"],
+                             d["mcs_mask"] if isinstance(mcs_mask, str) else mcs_mask,
+                             num_it=case.num_it, precision=precision, want_h=want_h, **forward_kw)
         torch.cuda.synchronize()
         prof = {k: v[0] for k, v in eng.profile_read().items()}
         eng.profile(False)
