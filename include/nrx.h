@@ -561,8 +561,8 @@ int nrx_chest_lmmse3(const nrx_chest3_io* io, void* workspace, size_t workspace_
  * What a decoder would see of the LLRs, and how good a channel estimate is: the sums behind the
  * bitwise mutual information (BMI; Sionna's BitwiseMutualInformation, 1 - the binary cross-entropy
  * the reference trains on, neural_rx.py:687, in bits) and behind the NMSE of a channel estimate (the
- * reference's second loss, neural_rx.py:688).  There is no LDPC decoder here, so the BMI -- the rate
- * a BICM decoder achieves with exactly these LLRs -- stands where the reference reports coded BLER.
+ * reference's second loss, neural_rx.py:688).  The BMI is the rate a BICM decoder achieves with
+ * exactly these LLRs; the coded BLER itself comes from the QC-LDPC decoder below.
  *
  * Contributing set: the one the error counters above count over -- (slot b, user u) with
  * active[b][u] > 0, symbols t whose bit is not set in dmrs_symbol_mask, every subcarrier f, bit
@@ -646,6 +646,151 @@ typedef struct nrx_nmse_io {
 
 int nrx_nmse_workspace_size(const nrx_nmse_io* io, size_t* bytes);
 int nrx_chest_nmse(const nrx_nmse_io* io, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------- QC-LDPC decoder
+ * Layered belief propagation for a quasi-cyclic LDPC code, the decoder the reference puts behind
+ * every receiver (TBDecoder: num_bp_iter = 20, cn_type = 'boxplus'; utils/neural_rx.py:1407-1413).
+ * The code is data: a base matrix of circulant shifts that the caller passes.  The limits admit the
+ * TS 38.212 base graphs, but the project ships and tests only codes it constructs itself
+ * (neural_rx_amd/ldpc.py); a caller-supplied table goes through the same path.  Stated departures
+ * from the reference: the project's own codes; no CRC, no segmentation and no bit interleaver; a
+ * layered schedule where Sionna's is flooding.
+ *
+ * Code: shifts [mb][nb] int16 (host), -1 for no edge, else 0..z-1.  Block (i, j) with shift s
+ * connects check i z + r to variable j z + (r + s) mod z, r = 0..z-1.  N = nb z.  Error counting
+ * covers the information columns v < kb z.
+ *
+ * Decoding of one codeword from its channel LLRs l[v] = log p(0)/p(1) (positive: bit 0), in f32:
+ *   init   APP[v] = clamp(l[v], +-llr_clip), a NaN input counts as 0; every check-to-variable
+ *          message m_e = 0.
+ *   One iteration is the layers i = 0..mb-1 in order.  In layer i every check r takes its edges
+ *   e_0..e_{d-1} in ascending base-column order (2 <= d <= 32):
+ *          t_k = APP[v_k] - m_k
+ *          x_k = the extrinsic of the other edges' t (below)
+ *          m_k <- clamp(x_k, +-llr_clip)
+ *          APP[v_k] <- t_k + m_k
+ *   Only the channel LLRs and the messages are clamped, never t or APP, so APP = l + sum of the
+ *   variable's messages holds exactly and |APP| <= (1 + max column weight) llr_clip.
+ *   boxplus (cn_type 0):  a [+] b = sgn(a) sgn(b) min(|a|, |b|) + (log1p(exp(-|a + b|)) - log1p(exp(-|a - b|)))
+ *          with sgn(0) = 0; the correction is formed first, so a [+] b is exactly odd in a and in b and the
+ *          decoder is exactly sign-symmetric.  P_0 = t_0, P_k = P_{k-1} [+] t_k (left fold); S_{d-1} = t_{d-1},
+ *          S_k = S_{k+1} [+] t_k (right fold);  x_0 = S_1, x_{d-1} = P_{d-2}, else x_k = P_{k-1} [+] S_{k+1}.
+ *   min-sum (cn_type 1):  x_k = ms_scale * (prod_{j != k} sgn(t_j) * min_{j != k} |t_j|) with sgn(0) = +1
+ *          (the sign is the one of the comparison t < 0).
+ *   After each iteration hard[v] = (APP[v] <= 0): a tie decides 1, so an all-erased input can never
+ *   pass as the all-zero word.  parity_ok = every check of hard is satisfied.  With early_stop a
+ *   codeword stops after the first iteration with parity_ok; iters = iterations run.  Without it
+ *   iters = num_iter and parity_ok is the one after the last iteration.
+ *   A codeword with skip[cw] != 0 is not decoded: its hard, app, iters and parity_ok are written 0.
+ *
+ * One launch runs all iterations: a workgroup owns 256 / z codewords (at least one), one thread per
+ * check of a layer, APP in LDS, layers separated by a barrier; the messages live in LDS when they
+ * fit next to APP, else in the workspace (nrx_ldpc_workspace_size, monotone in num_cw).  Early exit
+ * is uniform over the workgroup.  No atomics: the same inputs give the same bits on every call,
+ * independent of how the codewords are split into calls.  No allocation, no host synchronisation;
+ * asynchronous on `stream`, capturable into a hipGraph.
+ *
+ * nrx_ldpc_create validates the host table before the first HIP call: a NULL code / shifts / out is
+ * NRX_ERR_INVALID_ARG; mb outside 1..46, nb outside 2..68, nb <= mb, z outside 2..384 or kb outside
+ * 1..nb-1 is NRX_ERR_SHAPE; a shift outside -1..z-1, a row weight outside 2..32 or an empty column
+ * is NRX_ERR_INVALID_ARG.  device = -1 creates a handle without device tables: it answers
+ * nrx_ldpc_workspace_size and runs every argument check of nrx_ldpc_decode, which then returns
+ * NRX_ERR_INVALID_ARG ("no device").
+ * nrx_ldpc_decode checks every argument before the first HIP call: a NULL io / llr_in / hard / iters
+ * / parity_ok (app and skip may be NULL), num_iter outside 1..100, a cn_type other than 0 / 1,
+ * an early_stop other than 0 / 1, cn_type 1 with ms_scale outside (0, 1], an llr_clip that is not
+ * finite and > 0 is NRX_ERR_INVALID_ARG; num_cw outside 1..2^20 is NRX_ERR_SHAPE; then a NULL handle
+ * or a NULL or not 16-byte aligned workspace is NRX_ERR_INVALID_ARG and a workspace smaller than
+ * nrx_ldpc_workspace_size NRX_ERR_WORKSPACE. */
+typedef struct nrx_ldpc_code {
+  int32_t mb, nb, z, kb;       /* base rows 1..46, base columns 2..68 (> mb), lifting 2..384, 1 <= kb < nb */
+  const int16_t* shifts;       /* host, [mb][nb] */
+} nrx_ldpc_code;
+
+typedef struct nrx_ldpc_io {
+  int32_t num_cw;              /* 1..2^20 */
+  int32_t num_iter;            /* 1..100 */
+  int32_t cn_type;             /* 0 boxplus, 1 scaled min-sum */
+  int32_t early_stop;          /* 0 / 1 */
+  float   ms_scale;            /* cn_type 1: in (0, 1] */
+  float   llr_clip;            /* > 0 */
+  const float*   llr_in;       /* [num_cw][N], log p(0)/p(1) */
+  const uint8_t* skip;         /* [num_cw] or NULL (= none) */
+  uint8_t* hard;               /* [num_cw][N] */
+  float*   app;                /* [num_cw][N] or NULL */
+  int32_t* iters;              /* [num_cw] */
+  uint8_t* parity_ok;          /* [num_cw] */
+} nrx_ldpc_io;
+
+typedef struct nrx_ldpc nrx_ldpc;
+
+int nrx_ldpc_create(const nrx_ldpc_code* code, int32_t device, nrx_ldpc** out);
+void nrx_ldpc_destroy(nrx_ldpc* h);
+int nrx_ldpc_workspace_size(const nrx_ldpc* h, const nrx_ldpc_io* io, size_t* bytes);
+int nrx_ldpc_decode(nrx_ldpc* h, const nrx_ldpc_io* io, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Slot glue of a coded evaluation.  The generator sends i.i.d. uniform bits c; they are read as the
+ * all-zero codeword under the random scrambler c, so the descrambled LLR of a sent bit with engine
+ * LLR L (Sionna sign, log p(1)/p(0)) is (2c - 1) L = log p(0)/p(1) towards the all-zero word.
+ *
+ * nrx_ldpc_gather writes llr_in [(b U + u) C + j][N] and skip [(b U + u) C + j] from the engine's LLR
+ * tensor (contributing set, head and MCS rules of nrx_llr_stats).  Transmitted bit e of a (slot, user)
+ * with m = mcs_bits[mcs[b][u]] is (i-th data RE in symbol-major order, bit k) with e = i m + k, the
+ * order of nrx_llr_demap; n_data = F * (data symbols).  Codeword j takes e = j n_tx + e', e' in
+ * [0, n_tx):   l[tx_col[e']] += (2c - 1) L   in f32, in ascending e', starting from col_prior[v]
+ * (NULL: 0); repeats of a column accumulate, columns never listed stay at col_prior (puncturing and
+ * shortening), an entry of tx_col outside 0..N-1 is dropped.  tx_col == NULL is the identity and
+ * needs n_tx <= N.  A codeword is skipped (skip = 1, its row = col_prior) when the user is inactive
+ * or j >= floor(n_data m / n_tx).  No floating-point atomics: the same bits on every call.
+ * A NULL io / llr / bits / active / llr_in / skip, a bit width outside 1..8 or a dmrs_symbol_mask
+ * outside 0..2^14 - 1 is NRX_ERR_INVALID_ARG; T != 14, B outside 1..65535, F outside 1..3300, U
+ * outside 1..16, num_mcs outside 1..8, num_heads not in {1, num_mcs}, bits_stride < max(mcs_bits),
+ * C outside 1..64, B U C > 2^20, N outside 4..26112, n_tx outside 1..2^20 or tx_col == NULL with
+ * n_tx > N is NRX_ERR_SHAPE.  Checked before the first HIP call; asynchronous on `stream`. */
+typedef struct nrx_ldpc_gather_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B (1..65535), U (1..16), F (1..3300), T = 14 */
+  int32_t num_heads;           /* H heads in llr; head = mcs if H > 1 else 0 */
+  int32_t bits_stride;         /* last dim of llr and bits */
+  int32_t num_mcs;             /* 1..8 */
+  int32_t mcs_bits[8];         /* 1..8 */
+  int32_t dmrs_symbol_mask;
+  int32_t num_cw_per_user;     /* C, 1..64 */
+  int32_t n_tx;                /* transmitted bits per codeword */
+  int32_t n;                   /* N */
+  const float*   llr;          /* [H][B][U][F][T][bits_stride] (nrx_io.llr) */
+  const uint8_t* bits;         /* [B][U][F][T][bits_stride] */
+  const uint8_t* mcs;          /* [B][U] or NULL (= 0) */
+  const float*   active;       /* [B][U] */
+  const int32_t* tx_col;       /* device, [n_tx] or NULL (= identity) */
+  const float*   col_prior;    /* device, [N] or NULL (= 0) */
+  float*   llr_in;             /* [B U C][N] */
+  uint8_t* skip;               /* [B U C] */
+} nrx_ldpc_gather_io;
+
+int nrx_ldpc_gather(const nrx_ldpc_gather_io* io, void* stream);
+
+/* Coded error counters against the all-zero word, over the codewords with skip == 0:
+ *   counts[u][0..3] += (information-bit errors, information bits, block errors, blocks)
+ * where an information bit is a column v < num_info, a block is one (slot, user) with at least one
+ * counted codeword, in error if any of them has hard != 0 in an information column.  counts has the
+ * layout of nrx_count_errors (int64, device, accumulated), so the same all-reduce carries it.  With
+ * iters and iter_counts both non-NULL, iter_counts[u][0..1] += (decoder iterations, codewords).
+ * A NULL io / hard / skip / counts is NRX_ERR_INVALID_ARG; B outside 1..65535, U outside 1..16, C
+ * outside 1..64, N outside 4..26112 or num_info outside 1..N is NRX_ERR_SHAPE. */
+typedef struct nrx_ldpc_count_io {
+  int32_t batch, num_tx;       /* B, U */
+  int32_t num_cw_per_user;     /* C */
+  int32_t n;                   /* N */
+  int32_t num_info;            /* kb z */
+  int32_t pad_;
+  const uint8_t* hard;         /* [B U C][N] */
+  const uint8_t* skip;         /* [B U C] */
+  const int32_t* iters;        /* [B U C] or NULL */
+  int64_t* counts;             /* [U][4] accumulated */
+  int64_t* iter_counts;        /* [U][2] accumulated, or NULL */
+} nrx_ldpc_count_io;
+
+int nrx_ldpc_count(const nrx_ldpc_count_io* io, void* stream);
 
 /* Host helper: nearest-pilot positional encoding pe[U][F][T][2] for DMRS
  * configuration type 1 (restates onnx_utils.py:172-260 for the product path).

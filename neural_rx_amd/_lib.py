@@ -35,6 +35,8 @@ EXPORTS = [
     "nrx_llr_stats_workspace_size", "nrx_llr_stats", "nrx_nmse_workspace_size", "nrx_chest_nmse",
     "nrx_generate_slots_ex", "nrx_cov_space_workspace_size", "nrx_cov_space_accumulate",
     "nrx_chest3_workspace_size", "nrx_chest_lmmse3", "nrx_aerial_preprocess",
+    "nrx_ldpc_create", "nrx_ldpc_destroy", "nrx_ldpc_workspace_size", "nrx_ldpc_decode", "nrx_ldpc_gather",
+    "nrx_ldpc_count",
 ]
 # enum nrx_y_layout
 Y_LAYOUTS = {"cgnn": 0, "sionna": 1, "split": 2}
@@ -340,6 +342,74 @@ class nrx_nmse_io(ctypes.Structure):
     ]
 
 
+class nrx_ldpc_code(ctypes.Structure):
+    _fields_ = [
+        ("mb", ctypes.c_int32),
+        ("nb", ctypes.c_int32),
+        ("z", ctypes.c_int32),
+        ("kb", ctypes.c_int32),
+        ("shifts", ctypes.c_void_p),
+    ]
+
+
+class nrx_ldpc_io(ctypes.Structure):
+    _fields_ = [
+        ("num_cw", ctypes.c_int32),
+        ("num_iter", ctypes.c_int32),
+        ("cn_type", ctypes.c_int32),
+        ("early_stop", ctypes.c_int32),
+        ("ms_scale", ctypes.c_float),
+        ("llr_clip", ctypes.c_float),
+        ("llr_in", ctypes.c_void_p),
+        ("skip", ctypes.c_void_p),
+        ("hard", ctypes.c_void_p),
+        ("app", ctypes.c_void_p),
+        ("iters", ctypes.c_void_p),
+        ("parity_ok", ctypes.c_void_p),
+    ]
+
+
+class nrx_ldpc_gather_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_heads", ctypes.c_int32),
+        ("bits_stride", ctypes.c_int32),
+        ("num_mcs", ctypes.c_int32),
+        ("mcs_bits", ctypes.c_int32 * 8),
+        ("dmrs_symbol_mask", ctypes.c_int32),
+        ("num_cw_per_user", ctypes.c_int32),
+        ("n_tx", ctypes.c_int32),
+        ("n", ctypes.c_int32),
+        ("llr", ctypes.c_void_p),
+        ("bits", ctypes.c_void_p),
+        ("mcs", ctypes.c_void_p),
+        ("active", ctypes.c_void_p),
+        ("tx_col", ctypes.c_void_p),
+        ("col_prior", ctypes.c_void_p),
+        ("llr_in", ctypes.c_void_p),
+        ("skip", ctypes.c_void_p),
+    ]
+
+
+class nrx_ldpc_count_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_cw_per_user", ctypes.c_int32),
+        ("n", ctypes.c_int32),
+        ("num_info", ctypes.c_int32),
+        ("pad_", ctypes.c_int32),
+        ("hard", ctypes.c_void_p),
+        ("skip", ctypes.c_void_p),
+        ("iters", ctypes.c_void_p),
+        ("counts", ctypes.c_void_p),
+        ("iter_counts", ctypes.c_void_p),
+    ]
+
+
 # subcarriers per work item of nrx_llr_stats / nrx_chest_nmse (NRX_SOFT_STRIP of include/nrx.h)
 SOFT_STRIP = 16
 
@@ -448,6 +518,18 @@ def load(path: str = LIB_PATH):
     lib.nrx_nmse_workspace_size.restype = c.c_int
     lib.nrx_chest_nmse.argtypes = [P(nrx_nmse_io), c.c_void_p, c.c_size_t, c.c_void_p]
     lib.nrx_chest_nmse.restype = c.c_int
+    lib.nrx_ldpc_create.argtypes = [P(nrx_ldpc_code), c.c_int32, P(c.c_void_p)]
+    lib.nrx_ldpc_create.restype = c.c_int
+    lib.nrx_ldpc_destroy.argtypes = [c.c_void_p]
+    lib.nrx_ldpc_destroy.restype = None
+    lib.nrx_ldpc_workspace_size.argtypes = [c.c_void_p, P(nrx_ldpc_io), P(c.c_size_t)]
+    lib.nrx_ldpc_workspace_size.restype = c.c_int
+    lib.nrx_ldpc_decode.argtypes = [c.c_void_p, P(nrx_ldpc_io), c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.nrx_ldpc_decode.restype = c.c_int
+    lib.nrx_ldpc_gather.argtypes = [P(nrx_ldpc_gather_io), c.c_void_p]
+    lib.nrx_ldpc_gather.restype = c.c_int
+    lib.nrx_ldpc_count.argtypes = [P(nrx_ldpc_count_io), c.c_void_p]
+    lib.nrx_ldpc_count.restype = c.c_int
     lib.nrx_api_version.argtypes = []
     lib.nrx_api_version.restype = c.c_int32
     lib.nrx_update_schedule.argtypes = [c.c_void_p, c.c_int32]

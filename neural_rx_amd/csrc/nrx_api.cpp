@@ -1197,6 +1197,155 @@ int nrx_chest_nmse(const nrx_nmse_io* io, void* workspace, size_t workspace_byte
   return NRX_OK;
 }
 
+// ---- QC-LDPC decoder: the host table is validated and packed into per-layer edge lists
+struct nrx_ldpc {
+  LdpcDev d;
+  int device;                  // -1: no device tables (sizing and argument checks only)
+  void* tables;                // one device allocation: row_ptr, then edges
+};
+
+constexpr int kLdpcMaxN = 68 * 384;
+
+int nrx_ldpc_create(const nrx_ldpc_code* code, int32_t device, nrx_ldpc** out) {
+  if (!code || !code->shifts || !out) return fail(NRX_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  const int mb = code->mb, nb = code->nb, z = code->z;
+  if (mb < 1 || mb > 46) return fail(NRX_ERR_SHAPE, "mb must be 1..46");
+  if (nb < 2 || nb > 68) return fail(NRX_ERR_SHAPE, "nb must be 2..68");
+  if (nb <= mb) return fail(NRX_ERR_SHAPE, "nb must be > mb");
+  if (z < 2 || z > 384) return fail(NRX_ERR_SHAPE, "z must be 2..384");
+  if (code->kb < 1 || code->kb >= nb) return fail(NRX_ERR_SHAPE, "kb must be 1..nb-1");
+  if (device < -1) return fail(NRX_ERR_INVALID_ARG, "device must be >= 0, or -1 for a handle without device tables");
+  std::vector<int> row_ptr(mb + 1, 0), edges, colw(nb, 0);
+  for (int i = 0; i < mb; ++i) {
+    for (int j = 0; j < nb; ++j) {
+      const int s = code->shifts[i * nb + j];
+      if (s < -1 || s >= z) return fail(NRX_ERR_INVALID_ARG, "shifts must be -1..z-1");
+      if (s < 0) continue;
+      edges.push_back(j * z);
+      edges.push_back(s);
+      colw[j] += 1;
+    }
+    row_ptr[i + 1] = (int)edges.size() / 2;
+    const int w = row_ptr[i + 1] - row_ptr[i];
+    if (w < 2 || w > 32) return fail(NRX_ERR_INVALID_ARG, "row weight must be 2..32");
+  }
+  for (int j = 0; j < nb; ++j)
+    if (!colw[j]) return fail(NRX_ERR_INVALID_ARG, "column weight must be >= 1");
+  nrx_ldpc* h = new nrx_ldpc();
+  h->d.mb = mb, h->d.nb = nb, h->d.z = z, h->d.kb = code->kb, h->d.num_edges = row_ptr[mb];
+  h->d.plan = ldpc_plan(nb, z, h->d.num_edges);
+  h->d.row_ptr = nullptr, h->d.edges = nullptr;
+  h->device = device;
+  h->tables = nullptr;
+  if (device >= 0) {
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = ldpc_setup();
+    const size_t rp = (size_t)(mb + 1) * 4, rpa = (rp + 15) / 16 * 16, eb = edges.size() * 4;
+    if (e == hipSuccess) e = hipMalloc(&h->tables, rpa + eb);
+    if (e == hipSuccess) e = hipMemcpy(h->tables, row_ptr.data(), rp, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char*)h->tables + rpa, edges.data(), eb, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      if (h->tables) (void)hipFree(h->tables);
+      delete h;
+      return hip_fail(e, "ldpc tables");
+    }
+    h->d.row_ptr = (const int*)h->tables;
+    h->d.edges = (const int*)((char*)h->tables + rpa);
+  }
+  *out = h;
+  return NRX_OK;
+}
+
+void nrx_ldpc_destroy(nrx_ldpc* h) {
+  if (!h) return;
+  if (h->tables) (void)hipFree(h->tables);
+  delete h;
+}
+
+static int check_ldpc_io(const nrx_ldpc_io* io) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->llr_in || !io->hard || !io->iters || !io->parity_ok) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (io->num_iter < 1 || io->num_iter > 100) return fail(NRX_ERR_INVALID_ARG, "num_iter must be 1..100");
+  if (io->cn_type != 0 && io->cn_type != 1) return fail(NRX_ERR_INVALID_ARG, "cn_type must be 0 (boxplus) or 1 (min-sum)");
+  if (io->early_stop != 0 && io->early_stop != 1) return fail(NRX_ERR_INVALID_ARG, "early_stop must be 0 or 1");
+  if (io->cn_type == 1 && !(io->ms_scale > 0.0f && io->ms_scale <= 1.0f))
+    return fail(NRX_ERR_INVALID_ARG, "ms_scale must be in (0, 1]");
+  if (!(io->llr_clip > 0.0f) || !std::isfinite(io->llr_clip))
+    return fail(NRX_ERR_INVALID_ARG, "llr_clip must be finite and > 0");
+  if (io->num_cw < 1 || io->num_cw > (1 << 20)) return fail(NRX_ERR_SHAPE, "num_cw must be 1..2^20");
+  return NRX_OK;
+}
+
+static size_t ldpc_workspace_bytes(const nrx_ldpc* h, const nrx_ldpc_io* io) {
+  const size_t msgs = h->d.plan.msg_lds ? 0 : (size_t)io->num_cw * h->d.num_edges * h->d.z * 4;
+  return msgs > 256 ? msgs : 256;
+}
+
+int nrx_ldpc_workspace_size(const nrx_ldpc* h, const nrx_ldpc_io* io, size_t* bytes) {
+  if (int rc = check_ldpc_io(io)) return rc;
+  if (!h) return fail(NRX_ERR_INVALID_ARG, "null handle");
+  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
+  *bytes = ldpc_workspace_bytes(h, io);
+  return NRX_OK;
+}
+
+int nrx_ldpc_decode(nrx_ldpc* h, const nrx_ldpc_io* io, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_ldpc_io(io)) return rc;
+  if (!h) return fail(NRX_ERR_INVALID_ARG, "null handle");
+  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
+  if ((uintptr_t)workspace & 15) return fail(NRX_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+  const size_t need = ldpc_workspace_bytes(h, io);
+  if (workspace_bytes < need)
+    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (h->device < 0) return fail(NRX_ERR_INVALID_ARG, "no device: the handle was created with device = -1");
+  hipError_t e = launch_ldpc_decode(h->d, *io, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "ldpc decode launch");
+  return NRX_OK;
+}
+
+int nrx_ldpc_gather(const nrx_ldpc_gather_io* io, void* stream) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->llr || !io->bits || !io->active || !io->llr_in || !io->skip)
+    return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (io->dmrs_symbol_mask < 0 || io->dmrs_symbol_mask >= (1 << kT))
+    return fail(NRX_ERR_INVALID_ARG, "dmrs_symbol_mask must be a mask of the 14 symbols");
+  if (io->num_mcs < 1 || io->num_mcs > 8) return fail(NRX_ERR_SHAPE, "num_mcs must be 1..8");
+  int bmax = 0;
+  for (int m = 0; m < io->num_mcs; ++m) {
+    if (io->mcs_bits[m] < 1 || io->mcs_bits[m] > 8) return fail(NRX_ERR_INVALID_ARG, "mcs_bits must be 1..8");
+    bmax = io->mcs_bits[m] > bmax ? io->mcs_bits[m] : bmax;
+  }
+  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
+  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
+  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
+  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
+  if (io->num_heads != 1 && io->num_heads != io->num_mcs) return fail(NRX_ERR_SHAPE, "num_heads must be 1 or num_mcs");
+  if (io->bits_stride < bmax) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
+  if (io->num_cw_per_user < 1 || io->num_cw_per_user > 64) return fail(NRX_ERR_SHAPE, "num_cw_per_user must be 1..64");
+  if ((int64_t)io->batch * io->num_tx * io->num_cw_per_user > (1 << 20))
+    return fail(NRX_ERR_SHAPE, "batch * num_tx * num_cw_per_user must be <= 2^20");
+  if (io->n < 4 || io->n > kLdpcMaxN) return fail(NRX_ERR_SHAPE, "n must be 4..26112");
+  if (io->n_tx < 1 || io->n_tx > (1 << 20)) return fail(NRX_ERR_SHAPE, "n_tx must be 1..2^20");
+  if (!io->tx_col && io->n_tx > io->n) return fail(NRX_ERR_SHAPE, "n_tx > n needs a tx_col");
+  hipError_t e = launch_ldpc_gather(*io, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "ldpc gather launch");
+  return NRX_OK;
+}
+
+int nrx_ldpc_count(const nrx_ldpc_count_io* io, void* stream) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->hard || !io->skip || !io->counts) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
+  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
+  if (io->num_cw_per_user < 1 || io->num_cw_per_user > 64) return fail(NRX_ERR_SHAPE, "num_cw_per_user must be 1..64");
+  if (io->n < 4 || io->n > kLdpcMaxN) return fail(NRX_ERR_SHAPE, "n must be 4..26112");
+  if (io->num_info < 1 || io->num_info > io->n) return fail(NRX_ERR_SHAPE, "num_info must be 1..n");
+  hipError_t e = launch_ldpc_count(*io, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "ldpc count launch");
+  return NRX_OK;
+}
+
 int nrx_profile_enable(nrx_handle* h, int32_t enable) {
   if (!h) return fail(NRX_ERR_INVALID_ARG, "null handle");
   if (enable) {

@@ -195,6 +195,25 @@ hipError_t launch_llr_stats(const nrx_llr_stats_io& io, void* ws, hipStream_t st
 size_t nmse_workspace_bytes(const nrx_nmse_io& io);
 hipError_t launch_chest_nmse(const nrx_nmse_io& io, void* ws, hipStream_t st);
 
+// QC-LDPC decoder and slot glue (nrx_ldpc.hip); io validated by the nrx_ldpc_* entry points
+struct LdpcPlan {
+  int G;                             // codewords per workgroup
+  int threads;
+  int lds_bytes;                     // dynamic LDS: APP, and the messages when msg_lds
+  bool msg_lds;                      // else the messages live in the workspace, [num_cw][num_edges][z] f32
+};
+struct LdpcDev {
+  int mb, nb, z, kb, num_edges;
+  LdpcPlan plan;
+  const int* row_ptr;                // device [mb + 1]
+  const int* edges;                  // device [num_edges][2]: (base column * z, shift)
+};
+LdpcPlan ldpc_plan(int nb, int z, int num_edges);
+hipError_t ldpc_setup();
+hipError_t launch_ldpc_decode(const LdpcDev& d, const nrx_ldpc_io& io, void* ws, hipStream_t st);
+hipError_t launch_ldpc_gather(const nrx_ldpc_gather_io& io, hipStream_t st);
+hipError_t launch_ldpc_count(const nrx_ldpc_count_io& io, hipStream_t st);
+
 hipError_t launch_llr_demap(const float* llr, int B, int U, int F, int T, int bits_stride, int bits,
                             const int32_t* data_re, int n_data, float* out, hipStream_t st);
 

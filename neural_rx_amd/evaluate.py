@@ -7,8 +7,10 @@ the CGNN engine, the GPU error counters, and -- across ranks -- one RCCL
 ``all_reduce(SUM)`` of the int64 counters every ``sync_every`` Monte-Carlo iterations
 (the analogue of ``sim_ber(distribute="all")``, evaluate.py:61).  Between those
 reductions nothing leaves the device: the counters accumulate in HBM and the host runs
-ahead, so a sharded run pays one collective + one host sync per window, not per batch.  Counts are uncoded (no LDPC here): BER
-of hard decisions on the LLRs and the fraction of (slot, user) grids with any bit error.
+ahead, so a sharded run pays one collective + one host sync per window, not per batch.  The counts of a
+``SimResult`` are uncoded: BER of hard decisions on the LLRs and the fraction of (slot, user) grids with any
+bit error.  With ``coded`` (CLI: ``-ldpc``) every batch is also decoded by the GPU QC-LDPC decoder (``ldpc.py``)
+and every system gains a coded BER / BLER column on the same slots.
 
 sim_ber semantics kept: per Eb/N0 point iterate until ``max_mc_iter`` or until
 ``num_target_block_errors`` block errors (tested at each reduction, so a point may run
@@ -59,7 +61,8 @@ def _dist():
 def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int, max_mc_iter: int,
              num_target_block_errors: int, target_bler: Optional[float], early_stop: bool, verbose: bool,
              sync_every: int, label: Optional[str] = None, soft: Optional[list] = None, soft_h=None,
-             soft_scales: Optional[Sequence[float]] = None) -> SimResult:
+             soft_scales: Optional[Sequence[float]] = None, coded: Optional[list] = None,
+             coded_spec=None) -> SimResult:
     """The Monte-Carlo loop shared by every system: ``step(sb, no) -> llr`` turns a generated batch
     into LLRs in the engine's layout, ``check()`` runs before every counter reduction.  Slot
     offsets, reductions and stopping rules do not depend on the system, so point k, iteration i
@@ -68,7 +71,13 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
     ``soft``: a list that gains one ``softmetrics.SoftResult`` per Eb/N0 point -- the LLR statistics of
     every batch and, when ``soft_h() -> h_est`` returns the channel estimate of the batch just
     processed, its squared error against ``sb.h`` -- accumulated on the device and reduced over ranks
-    at the same windows as the counters.  Without it the loop does what it did before."""
+    at the same windows as the counters.  Without it the loop does what it did before.
+
+    ``coded``: a list that gains one ``ldpc.CodedResult`` per Eb/N0 point -- the LLRs of every batch,
+    descrambled by the sent bits, decoded towards the all-zero word with ``coded_spec``
+    (``ldpc.DecoderSpec``) and counted on the device, reduced at the same windows.  ``no`` stays the one
+    of ``ebno_to_no``: it is not re-adjusted by the code's rate.  The stopping rules keep looking at the
+    uncoded counters, so the ``SimResult`` is the one of a call without ``coded``."""
     import torch
     if soft is not None:
         from .softmetrics import DEFAULT_SCALES, SoftAccumulator
@@ -80,6 +89,11 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
     p = gen.p
     dev = torch.device(f"cuda:{gen.device}")
     res = SimResult([], [], [], [], [], 0.0, 0)
+    cacc = None
+    if coded is not None:
+        from .ldpc import CodedAccumulator, DecoderSpec
+        cacc = CodedAccumulator(coded_spec or DecoderSpec(), p.num_tx, p.mcs_bits,
+                                p.num_subcarriers * (14 - len(p.dmrs_symbols)), device=gen.device)
     t0 = time.perf_counter()
     point_seed = 0
     for ebno in ebno_dbs:
@@ -89,6 +103,8 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
         acc = None
         if soft is not None:
             acc = SoftAccumulator(p.num_tx, p.mcs_bits, soft_scales or DEFAULT_SCALES, device=gen.device)
+        if cacc is not None:
+            cacc.reset()
         it = 0
         while it < max_mc_iter:
             off = ((point_seed * max_mc_iter + it) * world + rank) * batch_size
@@ -100,6 +116,8 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
                 h_est = soft_h() if soft_h is not None else None
                 if h_est is not None:
                     acc.add_channel(h_est, sb.h, sb.active)
+            if cacc is not None:
+                cacc.add(llr, sb.bits, sb.active, sb.mcs, p.dmrs_symbols)
             it += 1
             if it % sync_every and it < max_mc_iter:
                 continue
@@ -112,6 +130,8 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
             total = tot.cpu().numpy()
             if acc is not None:
                 acc.reduce(dist)
+            if cacc is not None:
+                cacc.reduce(dist)
             if total[2] >= num_target_block_errors:
                 break
         ber = total[0] / total[1] if total[1] else float("nan")
@@ -127,6 +147,10 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
             sr = acc.result()
             soft.append(sr)
             soft_txt = "  " + soft_line(sr)
+        if cacc is not None:
+            cr = cacc.result()
+            coded.append(cr)
+            soft_txt += f"  coded[{cr.code} z{cr.z} x{cr.cw_per_block}] BER {cr.ber:.4e} BLER {cr.bler:.4e} it {cr.mean_iters:.2f}"
         if verbose and rank == 0:
             print(f"{label + '  ' if label else ''}EbNo {ebno:6.2f} dB  BER {ber:.4e}  BLER(uncoded) {bler:.4e}  "
                   f"bit errors {total[0]}  blocks {total[3]}  iters {it}{soft_txt}", flush=True)
@@ -155,7 +179,8 @@ def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], b
             max_mc_iter: int = 100, num_target_block_errors: int = 100, target_bler: Optional[float] = None,
             early_stop: bool = True, num_it: Optional[int] = None, precision: str = "f16",
             verbose: bool = False, sync_every: int = 8, soft: Optional[list] = None,
-            soft_scales: Optional[Sequence[float]] = None) -> SimResult:
+            soft_scales: Optional[Sequence[float]] = None, coded: Optional[list] = None,
+            coded_spec=None) -> SimResult:
     """Sionna ``sim_ber`` loop on the GPU (this rank's shard of every Monte-Carlo batch:
     global slot ``(it * world + rank) * batch_size + b``).  The counters are reduced
     over ranks (and copied to the host) every ``sync_every`` batches and at the end of a
@@ -164,13 +189,18 @@ def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], b
     ``soft``: a list that gains one ``softmetrics.SoftResult`` per Eb/N0 point (BMI / GMI of the LLRs
     at ``soft_scales``, NMSE of the refined estimate ``h_ref``).  The forward then also runs the ChEst
     readout, and the generator needs ``want_h=True`` for the true channel.  The returned
-    ``SimResult`` is the one of a call without ``soft``."""
+    ``SimResult`` is the one of a call without ``soft``.
+
+    ``coded``: a list that gains one ``ldpc.CodedResult`` per Eb/N0 point (coded BER / BLER, mean decoder
+    iterations, code name, rate, N, C), decoded with ``coded_spec`` (``ldpc.DecoderSpec``; default r12, 20
+    boxplus iterations).  ``no`` is not re-adjusted by the code's rate.  The ``SimResult`` is unchanged."""
     return _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors, target_bler,
-                        early_stop, num_it, precision, verbose, sync_every, None, soft, soft_scales)
+                        early_stop, num_it, precision, verbose, sync_every, None, soft, soft_scales, coded, coded_spec)
 
 
 def _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors, target_bler,
-                 early_stop, num_it, precision, verbose, sync_every, label, soft=None, soft_scales=None) -> SimResult:
+                 early_stop, num_it, precision, verbose, sync_every, label, soft=None, soft_scales=None,
+                 coded=None, coded_spec=None) -> SimResult:
     """sim_ber; ``label`` prefixes the verbose lines (the CLI's runs with baselines)"""
     import torch
     p = gen.p
@@ -192,14 +222,16 @@ def _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_bloc
     # engine.check: the one-launch forward's error word -- a timed-out or incomplete forward raises
     # at the reduction instead of entering the counts (include/nrx.h nrx_fused_status)
     return _mc_loop(step, engine.check, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors,
-                    target_bler, early_stop, verbose, sync_every, label, soft, lambda: last["h"], soft_scales)
+                    target_bler, early_stop, verbose, sync_every, label, soft, lambda: last["h"], soft_scales,
+                    coded, coded_spec)
 
 
 def sim_ber_baseline(receiver, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_size: int,
                      max_mc_iter: int = 100, num_target_block_errors: int = 100,
                      target_bler: Optional[float] = None, early_stop: bool = True, verbose: bool = False,
                      sync_every: int = 8, label: Optional[str] = None, soft: Optional[list] = None,
-                     soft_scales: Optional[Sequence[float]] = None) -> SimResult:
+                     soft_scales: Optional[Sequence[float]] = None, coded: Optional[list] = None,
+                     coded_spec=None) -> SimResult:
     """``sim_ber`` with a classical baseline (``baseline.BaselineReceiver``,
     ``chest.EstimatorBaselineReceiver``, ``kbest.KBestBaselineReceiver``) in place of the engine:
     the same loop on the same slots (``_mc_loop``), so a baseline curve and the NRX curve of one
@@ -208,7 +240,9 @@ def sim_ber_baseline(receiver, gen: SlotGenerator, ebno_dbs: Sequence[float], ba
     ``soft``: as in ``sim_ber``; the NMSE is the one of the estimate the receiver detected with
     (``receiver.last_h``: ``sb.h_hat`` for the lsnn systems, the estimator's output for lslin / lmmse)
     and None for the perfect-CSI systems.  With an estimate to score, the generator needs
-    ``want_h=True``."""
+    ``want_h=True``.
+
+    ``coded`` / ``coded_spec``: as in ``sim_ber``."""
     if receiver.perfect_csi and not gen.want_h:
         raise ValueError("a perfect-CSI baseline needs SlotGenerator(want_h=True)")
     soft_h = None
@@ -217,7 +251,7 @@ def sim_ber_baseline(receiver, gen: SlotGenerator, ebno_dbs: Sequence[float], ba
             raise ValueError("the NMSE of the soft metrics needs the true channel: SlotGenerator(want_h=True)")
         soft_h = lambda: receiver.last_h  # noqa: E731
     return _mc_loop(receiver, lambda: None, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors,
-                    target_bler, early_stop, verbose, sync_every, label, soft, soft_h, soft_scales)
+                    target_bler, early_stop, verbose, sync_every, label, soft, soft_h, soft_scales, coded, coded_spec)
 
 
 def soft_dict(points, ebno_dbs: Sequence[float], code_rate: Optional[float] = None) -> dict:
@@ -233,6 +267,12 @@ def soft_dict(points, ebno_dbs: Sequence[float], code_rate: Optional[float] = No
             key: [ebno_at_rate([(e, getattr(sr, key)[m]) for e, sr in zip(ebno_dbs, points)], code_rate)
                   for m in range(num_mcs)] for key in ("bmi", "gmi")}
     return d
+
+
+def coded_dict(points) -> dict:
+    """The CLI's ``"coded"`` entry of one system: its ``ldpc.CodedResult`` per Eb/N0 point"""
+    return {"points": [cr.as_dict() for cr in points],
+            "note": "no is the one of ebno_to_no, not re-adjusted by the code's rate; the project's own QC code"}
 
 
 def baseline_note(name: str, receiver) -> Optional[str]:
@@ -278,6 +318,12 @@ def main(argv=None):
                     help="LLR scale factors the GMI is searched over (1..16 positive numbers)")
     ap.add_argument("-code_rate", type=float, default=None,
                     help="with -soft_metrics: report the Eb/N0 at which BMI and GMI reach this rate")
+    ap.add_argument("-ldpc", default=None, choices=["r13", "r12", "r23", "r34"],
+                    help="also decode every batch with the GPU QC-LDPC decoder (ldpc.py; the project's own regular "
+                         "code of that rate, sized to the slot) and report coded BER / BLER for every system; the "
+                         "JSON gains \"coded\" next to every result")
+    ap.add_argument("-ldpc_iter", type=int, default=20, help="decoder iterations (1..100), with early stop")
+    ap.add_argument("-ldpc_cn", default="boxplus", choices=["boxplus", "minsum"], help="check-node update")
     ap.add_argument("-channel", default="iid", choices=["iid"] + list(SCENARIOS),
                     help="iid: one delay / Doppler profile for every user and uncorrelated receive antennas; "
                          "double_tdl_low / double_tdl_high: the two-user profiles of the reference's evaluation "
@@ -317,9 +363,14 @@ def main(argv=None):
     gen = SlotGenerator(params, device=device, want_h=bool(needs_h & set(systems)) or a.soft_metrics)
     ebno = a.ebno_db if a.ebno_db is not None else list(np.arange(-2.0, 8.0, 1.0))
     soft = {"nrx": []} if a.soft_metrics else {}
+    coded = {"nrx": []} if a.ldpc else {}
+    coded_spec = None
+    if a.ldpc:
+        from .ldpc import DecoderSpec
+        coded_spec = DecoderSpec(code_name=a.ldpc, num_iter=a.ldpc_iter, cn_type=a.ldpc_cn)
     res = _sim_ber_nrx(engine, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors, a.target_bler,
                        True, cfg.num_nrx_iter_eval, a.precision, True, a.sync_every, "nrx" if systems else None,
-                       soft.get("nrx"), a.llr_scales)
+                       soft.get("nrx"), a.llr_scales, coded.get("nrx"), coded_spec)
     base = {}
     cov = None
     if {"lmmse_lmmse", "lmmse_kbest"} & set(systems):
@@ -347,9 +398,12 @@ def main(argv=None):
             print(note, flush=True)
         if a.soft_metrics:
             soft[name] = []
+        if a.ldpc:
+            coded[name] = []
         base[name] = sim_ber_baseline(rx, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors,
                                       a.target_bler, verbose=True, sync_every=a.sync_every, label=name,
-                                      soft=soft.get(name), soft_scales=a.llr_scales)
+                                      soft=soft.get(name), soft_scales=a.llr_scales, coded=coded.get(name),
+                                      coded_spec=coded_spec)
     d = None
     if rank == 0:
         d = res.as_dict()
@@ -367,6 +421,8 @@ def main(argv=None):
                 print(f"{name}  Eb/N0 at rate {a.code_rate:g}: BMI {sd['ebno_at_rate']['bmi']}  "
                       f"GMI {sd['ebno_at_rate']['gmi']}", flush=True)
             (d if name == "nrx" else d["baselines"][name])["soft"] = sd
+        for name, points in coded.items():
+            (d if name == "nrx" else d["baselines"][name])["coded"] = coded_dict(points)
         if cov is not None:
             d["num_cov_slots"] = a.num_cov_slots
         print(json.dumps(d))

@@ -2,8 +2,8 @@
 and the NMSE of a channel estimate.
 
 The error counters (``generator.count_errors``) look at the sign of an LLR only.  What a decoder
-sees is its magnitude, and there is no LDPC decoder here, so the quantity that stands where the
-reference reports coded BLER is the *bitwise mutual information* (BMI; Sionna's
+sees is its magnitude.  The quantity that summarises it without a code (the coded BLER itself is
+``ldpc.py``) is the *bitwise mutual information* (BMI; Sionna's
 ``BitwiseMutualInformation``): 1 minus the binary cross-entropy the reference trains on
 (neural_rx.py:687), in bits -- the rate a BICM decoder achieves with exactly these LLRs.  The Eb/N0
 at which it crosses the code rate predicts the waterfall (``ebno_at_rate``).  The *generalised*
