@@ -1,11 +1,10 @@
-// nrx_api.cpp -- host side of libnrx.so: C ABI (include/nrx.h), weight validation and
-// packing, workspace sizing, forward dispatch, and the product-side positional encoding.
+// nrx_api.cpp -- the C ABI of libnrx.so (include/nrx.h): the argument checks the entry points share,
+// workspace sizing, forward dispatch, and the product-side positional encoding.  The model side
+// (topology checks, weight packing, flop count) is nrx_model.cpp.
 //
-// Weight order = Keras get_weights() of the reference CGNN:
-//   StateInit x num_init : 3 x (dw[3,3,Cin,1], pw[1,1,Cin,Cout], b[Cout])
-//   num_it x [ Agg: (W[ds,64], b), (W[64,ds], b) ; Update: 3 x sep ]
-//   LLR heads x H : (W[ds,128], b), (W[128,bits], b)
-//   ChEst : (W[ds,128], b), (W[128,2A], b)
+// An entry point checks its descriptor first (check_grid, check_mcs_bits, ... below), then the
+// handle and the workspace pointer and alignment, then the workspace size (check_workspace), all
+// before its first HIP call, and ends in launched().
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -18,6 +17,7 @@
 
 #include "../../include/nrx.h"
 #include "nrx_internal.h"
+#include "nrx_model.h"
 
 namespace nrx {
 hipError_t launch_forward_f16(const FwdArgs<_Float16, float, _Float16>& args, const ModelW<_Float16, float>& W,
@@ -30,13 +30,8 @@ hipError_t launch_forward_f64(const FwdArgs<double, double, float>& args,
                               Prof* prof);
 hipError_t setup_kernels();
 int strip_width(int precision);
-}  // namespace nrx
 
-using namespace nrx;
-
-namespace {
-
-thread_local std::string g_err;
+static thread_local std::string g_err;
 
 int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -46,242 +41,104 @@ int fail(int code, const std::string& msg) {
 int hip_fail(hipError_t e, const char* what) {
   return fail(NRX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+}  // namespace nrx
 
-struct LayerShape {
-  enum Kind { SEP, DENSE } kind;
-  int cin, cout;
-};
+using namespace nrx;
 
-// Topology checks: the kernels are specialised for the in-scope configs.
-int check_desc(const nrx_desc* d) {
-  if (!d) return fail(NRX_ERR_INVALID_ARG, "desc is NULL");
-  if (d->d_s != kDS) return fail(NRX_ERR_UNSUPPORTED, "kernels are built for d_s = 56");
-  if (d->init_units[0] != kHID || d->init_units[1] != kHID || d->state_units[0] != kHID ||
-      d->state_units[1] != kHID || d->readout_units != kHID || d->agg_units != kAGG)
-    return fail(NRX_ERR_UNSUPPORTED, "kernels are built for 128/128 convs, 64 agg, 128 readout");
-  if (d->num_rx_ant < 1 || 4 * d->num_rx_ant + 2 > 128 || 2 * d->num_rx_ant > 32)
-    return fail(NRX_ERR_UNSUPPORTED, "num_rx_ant must be 1..16");
-  if (d->num_it < 1 || d->num_it > kMaxIt) return fail(NRX_ERR_UNSUPPORTED, "num_it must be 1..8");
-  if (d->num_mcs < 1 || d->num_mcs > kMaxHeads) return fail(NRX_ERR_UNSUPPORTED, "num_mcs must be 1..8");
-  for (int m = 0; m < d->num_mcs; ++m)
-    if (d->bits[m] < 1 || d->bits[m] > 8) return fail(NRX_ERR_UNSUPPORTED, "bits must be 1..8");
-  if (!d->var_mcs_masking && d->num_mcs > 3)
-    return fail(NRX_ERR_UNSUPPORTED, "at most 3 LLR heads (fused readout staging)");
-  if (d->use_h_hat != 0 && d->use_h_hat != 1) return fail(NRX_ERR_INVALID_ARG, "use_h_hat must be 0/1");
+// ---------------------------------------------------------------- shared argument checks
+// One rule has one wording and one code wherever it applies; what differs between entry points on
+// purpose is an argument at the call site.
+namespace {
+
+int check_range(const char* name, long v, long lo, long hi, int code = NRX_ERR_SHAPE) {
+  if (v >= lo && v <= hi) return NRX_OK;
+  return fail(code, std::string(name) + " must be " + std::to_string(lo) + ".." + std::to_string(hi));
+}
+
+// The slot grid [batch][num_tx][num_subcarriers][14].  tx_supported: the detectors' kernels stop at 8
+// users, which is NRX_ERR_UNSUPPORTED, not a bad shape; min_subcarriers: the generator's pilot comb
+// needs 2.
+template <class IO>
+int check_grid(const IO* io, int tx_supported = kMaxUsers, int min_subcarriers = 1) {
+  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
+  if (int rc = check_range("batch", io->batch, 1, 65535)) return rc;
+  if (int rc = check_range("num_subcarriers", io->num_subcarriers, min_subcarriers, 12 * 275)) return rc;
+  if (io->num_tx > tx_supported && tx_supported < kMaxUsers)
+    return fail(NRX_ERR_UNSUPPORTED, "the kernels are built for num_tx <= " + std::to_string(tx_supported));
+  return check_range("num_tx", io->num_tx, 1, kMaxUsers);
+}
+// ... with receive antennas
+template <class IO>
+int check_grid_ant(const IO* io, int tx_supported = kMaxUsers, int min_subcarriers = 1) {
+  if (int rc = check_grid(io, tx_supported, min_subcarriers)) return rc;
+  return check_range("num_rx_ant", io->num_rx_ant, 1, 16);
+}
+
+// num_mcs 1..8 (num_mcs_code: the generator reports it as a bad argument, the others as a bad shape)
+// and every mcs_bits[m] a QAM order the detectors and the generator know (qam: 2, 4 or 6) or 1..8
+int check_mcs_bits(const int32_t* bits, int num_mcs, bool qam, int num_mcs_code = NRX_ERR_SHAPE) {
+  if (int rc = check_range("num_mcs", num_mcs, 1, 8, num_mcs_code)) return rc;
+  for (int m = 0; m < num_mcs; ++m)
+    if (qam ? bits[m] != 2 && bits[m] != 4 && bits[m] != 6 : bits[m] < 1 || bits[m] > 8)
+      return fail(NRX_ERR_INVALID_ARG, qam ? "mcs_bits must be 2, 4 or 6" : "mcs_bits must be 1..8");
+  return NRX_OK;
+}
+// the bit axis of an LLR / bit tensor holds the widest MCS (after check_mcs_bits)
+int check_bits_stride(int bits_stride, const int32_t* bits, int num_mcs) {
+  for (int m = 0; m < num_mcs; ++m)
+    if (bits_stride < bits[m]) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
   return NRX_OK;
 }
 
-int num_init(const nrx_desc* d) { return d->var_mcs_masking ? 1 : d->num_mcs; }
-int num_heads(const nrx_desc* d) { return d->var_mcs_masking ? 1 : d->num_mcs; }
-int bits_max(const nrx_desc* d) {
-  int b = 0;
-  for (int m = 0; m < d->num_mcs; ++m) b = d->bits[m] > b ? d->bits[m] : b;
-  return b;
-}
-int init_cin(const nrx_desc* d) { return (d->use_h_hat ? 4 : 2) * d->num_rx_ant + 2; }
-int init_a2p(int num_rx_ant) { return 2 * num_rx_ant <= 8 ? 8 : (2 * num_rx_ant <= 16 ? 16 : 32); }
-
-std::vector<LayerShape> layer_list(const nrx_desc* d) {
-  std::vector<LayerShape> L;
-  for (int m = 0; m < num_init(d); ++m) {
-    L.push_back({LayerShape::SEP, init_cin(d), kHID});
-    L.push_back({LayerShape::SEP, kHID, kHID});
-    L.push_back({LayerShape::SEP, kHID, kDS});
+// 1..4 ascending DMRS symbols; *mask (optional): their bit mask
+int check_dmrs_symbols(const int32_t* sym, int n, int* mask = nullptr) {
+  if (int rc = check_range("num_dmrs_symbols", n, 1, 4)) return rc;
+  int bits = 0;
+  for (int k = 0; k < n; ++k) {
+    if (sym[k] < 0 || sym[k] >= kT || (k && sym[k] <= sym[k - 1]))
+      return fail(NRX_ERR_INVALID_ARG, "dmrs_symbols must be ascending symbol indices below 14");
+    bits |= 1 << sym[k];
   }
-  for (int i = 0; i < d->num_it; ++i) {
-    L.push_back({LayerShape::DENSE, kDS, kAGG});
-    L.push_back({LayerShape::DENSE, kAGG, kDS});
-    L.push_back({LayerShape::SEP, 2 * kDS + 2, kHID});
-    L.push_back({LayerShape::SEP, kHID, kHID});
-    L.push_back({LayerShape::SEP, kHID, kDS});
-  }
-  const int nh = num_heads(d);
-  for (int h = 0; h < nh; ++h) {
-    L.push_back({LayerShape::DENSE, kDS, kHID});
-    L.push_back({LayerShape::DENSE, kHID, d->var_mcs_masking ? bits_max(d) : d->bits[h]});
-  }
-  L.push_back({LayerShape::DENSE, kDS, kHID});
-  L.push_back({LayerShape::DENSE, kHID, 2 * d->num_rx_ant});
-  return L;
-}
-
-std::vector<int64_t> weight_sizes(const nrx_desc* d) {
-  std::vector<int64_t> s;
-  for (const auto& l : layer_list(d)) {
-    if (l.kind == LayerShape::SEP) {
-      s.push_back(9LL * l.cin);
-      s.push_back((int64_t)l.cin * l.cout);
-      s.push_back(l.cout);
-    } else {
-      s.push_back((int64_t)l.cin * l.cout);
-      s.push_back(l.cout);
-    }
-  }
-  return s;
-}
-
-int round_up(int x, int m) { return (x + m - 1) / m * m; }
-int pow2_at_least(int x, int lo) {
-  int p = lo;
-  while (p < x) p *= 2;
-  return p;
-}
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// Host-side packing into one contiguous blob per precision; pointers are patched to the
-// device copy after upload.
-template <class WT, class BT>
-struct Packer {
-  std::vector<char> blob;
-  size_t put_w(const std::vector<WT>& v) {
-    size_t off = align256(blob.size());
-    blob.resize(off + v.size() * sizeof(WT));
-    memcpy(blob.data() + off, v.data(), v.size() * sizeof(WT));
-    return off;
-  }
-  size_t put_b(const std::vector<BT>& v) {
-    size_t off = align256(blob.size());
-    blob.resize(off + v.size() * sizeof(BT));
-    memcpy(blob.data() + off, v.data(), v.size() * sizeof(BT));
-    return off;
-  }
-  // offsets relative to blob start, fixed up later
-  struct SepOff { size_t dw, pw, b; };
-  struct DenOff { size_t w, b; };
-  // `pos` (optional) places input channel c at packed position pos[c] (StateInit conv1:
-  // the kernel's z image is [y | pe | h] with the antenna blocks padded to A2P).
-  SepOff sep(const float* dw, const float* pw, const float* b, int cin, int cout, int cinp, int coutp,
-             const std::vector<int>* pos = nullptr) {
-    std::vector<WT> dwp((size_t)9 * cinp, WT(0)), pwp((size_t)coutp * cinp, WT(0));
-    std::vector<BT> bp(coutp, BT(0));
-    auto P = [&](int c) { return pos ? (*pos)[c] : c; };
-    for (int tap = 0; tap < 9; ++tap)
-      for (int c = 0; c < cin; ++c) dwp[(size_t)tap * cinp + P(c)] = (WT)dw[(size_t)tap * cin + c];
-    for (int c = 0; c < cin; ++c)
-      for (int o = 0; o < cout; ++o) pwp[(size_t)o * cinp + P(c)] = (WT)pw[(size_t)c * cout + o];
-    for (int o = 0; o < cout; ++o) bp[o] = (BT)b[o];
-    SepOff r;
-    r.dw = put_w(dwp);
-    r.pw = put_w(pwp);
-    r.b = put_b(bp);
-    return r;
-  }
-  // kperm: 0 = natural K order; 32 / 16 = K permuted so that the MFMA C layout of the
-  // producing layer (lane (t,g) holds channels 16n + 4g + j (f16) / 16n + g + 4j (f64))
-  // is directly the B fragment (kernels: CFrag).
-  static int kperm_channel(int p, int kperm) {
-    if (kperm == 32) return 32 * (p / 32) + 16 * ((p % 8) / 4) + 4 * ((p % 32) / 8) + (p % 4);
-    if (kperm == 16) return 16 * (p / 16) + (p % 16) / 4 + 4 * (p % 4);
-    return p;
-  }
-  DenOff dense(const float* w, const float* b, int cin, int cout, int cinp, int coutp, int kperm = 0) {
-    std::vector<WT> wp((size_t)coutp * cinp, WT(0));
-    std::vector<BT> bp(coutp, BT(0));
-    for (int pk = 0; pk < cinp; ++pk) {
-      const int c = kperm_channel(pk, kperm);
-      if (c >= cin) continue;
-      for (int o = 0; o < cout; ++o) wp[(size_t)o * cinp + pk] = (WT)w[(size_t)c * cout + o];
-    }
-    for (int o = 0; o < cout; ++o) bp[o] = (BT)b[o];
-    return DenOff{put_w(wp), put_b(bp)};
-  }
-};
-
-template <class WT, class BT>
-struct DeviceModel {
-  ModelW<WT, BT> W{};
-  void* dev = nullptr;
-  int init_cinp = 0;
-};
-
-template <class WT, class BT>
-int build_model(const nrx_desc* d, const float* const* w, int kc, DeviceModel<WT, BT>* out) {
-  Packer<WT, BT> pk;
-  using SO = typename Packer<WT, BT>::SepOff;
-  using DO = typename Packer<WT, BT>::DenOff;
-  SO init[kMaxInit][3];
-  DO agg[kMaxIt][2];
-  SO upd[kMaxIt][3];
-  DO llr[kMaxHeads][2];
-  DO ch[2];
-  const int icin = init_cin(d);
-  // StateInit input z = [y (2A), pe (2), h (2A)] (copy_pytorch.py:175-183) is laid out
-  // with each antenna block padded to A2P = init_a2p(A): y at [0, 2A), h at [A2P, A2P+2A),
-  // pe at 2 A2P, 2 A2P + 1 (so that an 8-channel lane chunk is all y, all h or pe: the
-  // one-launch forward's conv1 loads them straight from y / h_hat / pe); the padded channels
-  // carry zero weights.
-  const int a2p = init_a2p(d->num_rx_ant);
-  std::vector<int> ipos(icin);
-  for (int c = 0; c < icin; ++c) {
-    const int a2 = 2 * d->num_rx_ant;
-    ipos[c] = c < a2 ? c : (c < a2 + 2 ? 2 * a2p + (c - a2) : a2p + (c - a2 - 2));
-  }
-  const int icinp = pow2_at_least(round_up(2 * a2p + 2, kc), 32);
-  out->init_cinp = icinp;
-  int k = 0;
-  auto sep = [&](int cin, int cout, int cinp, int coutp, const std::vector<int>* pos = nullptr) {
-    SO r = pk.sep(w[k], w[k + 1], w[k + 2], cin, cout, cinp, coutp, pos);
-    k += 3;
-    return r;
-  };
-  // every dense layer of the engine consumes an MFMA accumulator tile: K permuted
-  auto den = [&](int cin, int cout, int cinp, int coutp) {
-    DO r = pk.dense(w[k], w[k + 1], cin, cout, cinp, coutp, kc);
-    k += 2;
-    return r;
-  };
-  // f16: conv2 / conv3 read the strip image the previous layer's in-place epilogue wrote
-  // straight from its accumulators (lane (t, g) stores tiles 2kc, 2kc+1 as one 16-byte
-  // chunk 4kc + g), i.e. their input channels sit in the K-permuted order of the dense
-  // layers: channel c at packed position kperm^-1(c)
-  std::vector<int> hpos(kHID);
-  for (int p = 0; p < kHID; ++p) hpos[Packer<WT, BT>::kperm_channel(p, kc == 32 ? 32 : 0)] = p;
-  const std::vector<int>* hp = kc == 32 ? &hpos : nullptr;
-  for (int m = 0; m < num_init(d); ++m) {
-    init[m][0] = sep(icin, kHID, icinp, kHID, &ipos);
-    init[m][1] = sep(kHID, kHID, kHID, kHID, hp);
-    init[m][2] = sep(kHID, kDS, kHID, kDSP, hp);
-  }
-  for (int i = 0; i < d->num_it; ++i) {
-    agg[i][0] = den(kDS, kAGG, kDSP, kAGG);
-    agg[i][1] = den(kAGG, kDS, kAGG, kDSP);
-    upd[i][0] = sep(2 * kDS + 2, kHID, kUPD_CINP, kHID);
-    upd[i][1] = sep(kHID, kHID, kHID, kHID, hp);
-    upd[i][2] = sep(kHID, kDS, kHID, kDSP, hp);
-  }
-  for (int h = 0; h < num_heads(d); ++h) {
-    const int nb = d->var_mcs_masking ? bits_max(d) : d->bits[h];
-    llr[h][0] = den(kDS, kHID, kDSP, kHID);
-    llr[h][1] = den(kHID, nb, kHID, 16);
-  }
-  const int a2 = 2 * d->num_rx_ant;
-  ch[0] = den(kDS, kHID, kDSP, kHID);
-  ch[1] = den(kHID, a2, kHID, a2 <= 16 ? 16 : 32);
-
-  hipError_t e = hipMalloc(&out->dev, pk.blob.size());
-  if (e != hipSuccess) return hip_fail(e, "hipMalloc(weights)");
-  e = hipMemcpy(out->dev, pk.blob.data(), pk.blob.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return hip_fail(e, "hipMemcpy(weights)");
-  char* base = (char*)out->dev;
-  auto fs = [&](const SO& o) {
-    return SepW<WT, BT>{(const WT*)(base + o.dw), (const WT*)(base + o.pw), (const BT*)(base + o.b)};
-  };
-  auto fd = [&](const DO& o) { return DenseW<WT, BT>{(const WT*)(base + o.w), (const BT*)(base + o.b)}; };
-  for (int m = 0; m < num_init(d); ++m)
-    for (int l = 0; l < 3; ++l) out->W.init[m][l] = fs(init[m][l]);
-  for (int i = 0; i < d->num_it; ++i) {
-    out->W.agg[i][0] = fd(agg[i][0]);
-    out->W.agg[i][1] = fd(agg[i][1]);
-    for (int l = 0; l < 3; ++l) out->W.upd[i][l] = fs(upd[i][l]);
-  }
-  for (int h = 0; h < num_heads(d); ++h) {
-    out->W.llr[h][0] = fd(llr[h][0]);
-    out->W.llr[h][1] = fd(llr[h][1]);
-  }
-  out->W.chest[0] = fd(ch[0]);
-  out->W.chest[1] = fd(ch[1]);
+  if (mask) *mask = bits;
   return NRX_OK;
 }
+int check_cdm_group(const int32_t* group, int num_tx) {
+  for (int u = 0; u < num_tx; ++u)
+    if (group[u] != 0 && group[u] != 1) return fail(NRX_ERR_INVALID_ARG, "cdm_group must be 0/1");
+  return NRX_OK;
+}
+int check_symbol_mask(const char* name, int v) {
+  if (v >= 0 && v < (1 << kT)) return NRX_OK;
+  return fail(NRX_ERR_INVALID_ARG, std::string(name) + " must be a mask of the 14 symbols");
+}
+int check_pos(const char* name, double v) {
+  if (v > 0.0 && std::isfinite(v)) return NRX_OK;
+  return fail(NRX_ERR_INVALID_ARG, std::string(name) + " must be finite and > 0");
+}
+int check_nonneg(const char* name, double v) {
+  if (v >= 0.0 && std::isfinite(v)) return NRX_OK;
+  return fail(NRX_ERR_INVALID_ARG, std::string(name) + " must be finite and >= 0");
+}
+
+int too_small(size_t need) {
+  return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+}
+// The workspace of a launch, after its descriptor checks: the pointer, the alignment of the kernels'
+// widest access to it (1: none), then the size.
+int check_workspace(const void* ws, size_t bytes, size_t need, size_t align) {
+  if (!ws) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
+  if ((uintptr_t)ws & (align - 1))
+    return fail(NRX_ERR_INVALID_ARG, "workspace must be " + std::to_string(align) + "-byte aligned");
+  return bytes < need ? too_small(need) : NRX_OK;
+}
+// the end of a *_workspace_size call, after its descriptor checks
+int store_size(size_t* bytes, size_t need) {
+  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
+  *bytes = need;
+  return NRX_OK;
+}
+// the end of a launching call
+int launched(hipError_t e, const char* what) { return e == hipSuccess ? NRX_OK : hip_fail(e, what); }
 
 }  // namespace
 
@@ -376,12 +233,7 @@ static size_t pe16_bytes(const nrx_shape* s, int precision) {
 
 static int check_shape(const nrx_shape* s) {
   if (!s) return fail(NRX_ERR_INVALID_ARG, "shape is NULL");
-  if (s->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
-  if (s->batch < 1 || s->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (s->num_tx < 1 || s->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
-  if (s->num_subcarriers < 1 || s->num_subcarriers > 12 * 275)
-    return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
-  return NRX_OK;
+  return check_grid(s);
 }
 
 template <class WT, class BT, class S>
@@ -396,12 +248,12 @@ static void fill_args(FwdArgs<WT, BT, S>& a, const nrx_handle* h, const nrx_io* 
   a.M = d->num_mcs;
   a.H = num_heads(d);
   a.init_cinp = init_cinp;
-  a.num_init = num_init(d);
+  a.num_init = num_heads(d);
   a.masking = d->var_mcs_masking;
   a.use_h = d->use_h_hat;
   a.bits_max = bits_max(d);
   for (int i = 0; i < kMaxHeads; ++i)
-    a.head_bits[i] = i < a.H ? (d->var_mcs_masking ? bits_max(d) : d->bits[i]) : 0;
+    a.head_bits[i] = i < a.H ? head_bits(d, i) : 0;
   a.y = io->y;
   a.pe = io->pe;
   a.h_hat = io->h_hat;
@@ -424,18 +276,23 @@ static void fill_args(FwdArgs<WT, BT, S>& a, const nrx_handle* h, const nrx_io* 
   a.ws_bytes = total < 0xFFFFFFFFull ? (unsigned)total : 0xFFFFFFFFu;
 }
 
-
 static int forward_slots(nrx_handle* h, const nrx_io* io, int llr_B, void* workspace, hipStream_t st);
-
-// NRX_ERR_BUSY when a forward that would take the one-launch path arrives on a stream other than
-// the previous one-launch forward's while that forward has not finished (the counters are per
-// handle).  Called before ANY launch of a forward entry point, so a refused call has launched
-// nothing (the y-layout / Aerial preprocessing used to run first).
 static int chunk_slots(const nrx_shape* s, int precision);
 
-static int fused_busy(nrx_handle* h, const nrx_io* io, hipStream_t st, bool* takes) {
-  *takes = false;
+// The one-stream rule: NRX_ERR_BUSY when a forward that takes the one-launch path arrives on a stream
+// other than the previous one-launch forward's while that forward has not finished (the counters are
+// per handle).
+static int busy(const nrx_handle* h, hipStream_t st) {
+  if (h->have_last && h->last_stream != st && hipEventQuery(h->last_ev) == hipErrorNotReady)
+    return fail(NRX_ERR_BUSY, "a one-launch forward of this handle is still running on another stream");
+  return NRX_OK;
+}
+
+// busy() for the whole of a forward entry point, called before ANY of its launches, so a refused
+// call has launched nothing (the y-layout / Aerial preprocessing used to run first).
+static int fused_busy(nrx_handle* h, const nrx_io* io, hipStream_t st) {
   if (io->precision != NRX_PREC_F16) return NRX_OK;
+  bool takes = false;
   // decided on the shapes the forward will run: a forward above the 1 GB workspace runs as slot
   // chunks (nrx_forward), full ones of chunk_slots slots and a remainder, and each chunk may take
   // the one-launch path although the whole batch would not
@@ -446,11 +303,9 @@ static int fused_busy(nrx_handle* h, const nrx_io* io, hipStream_t st, bool* tak
     c.shape.batch = n;
     FwdArgs<_Float16, float, _Float16> a{};
     fill_args(a, h, &c, nullptr, h->m16.init_cinp);   // pointers unused: the decision needs sizes only
-    *takes = *takes || fused_would_run(a, io->num_it, h->fused_ctl());
+    takes = takes || fused_would_run(a, io->num_it, h->fused_ctl());
   }
-  if (*takes && h->have_last && h->last_stream != st && hipEventQuery(h->last_ev) == hipErrorNotReady)
-    return fail(NRX_ERR_BUSY, "a one-launch forward of this handle is still running on another stream");
-  return NRX_OK;
+  return takes ? busy(h, st) : NRX_OK;
 }
 
 extern "C" {
@@ -459,8 +314,7 @@ const char* nrx_last_error(void) { return g_err.c_str(); }
 int32_t nrx_api_version(void) { return NRX_API_VERSION; }
 
 int nrx_weight_layout(const nrx_desc* desc, int32_t* num_weights, int64_t* sizes, int32_t cap) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
+  if (int rc = check_desc(desc)) return rc;
   if (!num_weights) return fail(NRX_ERR_INVALID_ARG, "num_weights is NULL");
   std::vector<int64_t> s = weight_sizes(desc);
   *num_weights = (int32_t)s.size();
@@ -524,8 +378,8 @@ int nrx_create(const nrx_desc* desc, const float* const* weights, const int64_t*
     nrx_destroy(h);
     return hip_fail(e, "fused forward counters");
   }
-  rc = build_model<_Float16, float>(desc, weights, 32, &h->m16);
-  if (!rc) rc = build_model<double, double>(desc, weights, 16, &h->m64);
+  rc = build_model(desc, weights, 32, &h->m16);
+  if (!rc) rc = build_model(desc, weights, 16, &h->m64);
   if (rc) {
     nrx_destroy(h);
     return rc;
@@ -567,8 +421,7 @@ static int chunk_slots(const nrx_shape* s, int precision) {
 
 int nrx_workspace_size(const nrx_handle* h, const nrx_shape* shape, int32_t precision, size_t* bytes) {
   if (!h || !bytes) return fail(NRX_ERR_INVALID_ARG, "null argument");
-  int rc = check_shape(shape);
-  if (rc) return rc;
+  if (int rc = check_shape(shape)) return rc;
   if (precision != NRX_PREC_F16 && precision != NRX_PREC_F32X)
     return fail(NRX_ERR_INVALID_ARG, "unknown precision");
   nrx_shape c = *shape;
@@ -579,17 +432,14 @@ int nrx_workspace_size(const nrx_handle* h, const nrx_shape* shape, int32_t prec
 
 int nrx_forward(nrx_handle* h, const nrx_io* io, void* workspace, size_t workspace_bytes, void* stream) {
   if (!h || !io) return fail(NRX_ERR_INVALID_ARG, "null argument");
-  int rc = check_shape(&io->shape);
-  if (rc) return rc;
+  if (int rc = check_shape(&io->shape)) return rc;
   const nrx_desc* d = &h->desc;
   if (io->num_it < 1 || io->num_it > d->num_it) return fail(NRX_ERR_INVALID_ARG, "Invalid number of iterations");
   if (!io->y || !io->pe || !io->active || !io->llr) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (d->use_h_hat && !io->h_hat) return fail(NRX_ERR_INVALID_ARG, "h_hat is required by this model");
   size_t need = 0;
-  rc = nrx_workspace_size(h, &io->shape, io->precision, &need);
-  if (rc) return rc;
-  if (!workspace || workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (int rc = nrx_workspace_size(h, &io->shape, io->precision, &need)) return rc;
+  if (!workspace || workspace_bytes < need) return too_small(need);
   hipStream_t st = (hipStream_t)stream;
   const int bc = chunk_slots(&io->shape, io->precision);
   if (bc < io->shape.batch) {
@@ -606,8 +456,7 @@ int nrx_forward(nrx_handle* h, const nrx_io* io, void* workspace, size_t workspa
       c.mcs_mask = io->mcs_mask ? io->mcs_mask + (size_t)b0 * U * d->num_mcs : nullptr;
       c.h_ref = io->h_ref ? io->h_ref + (size_t)b0 * U * re * A2 : nullptr;
       c.llr = io->llr + (size_t)b0 * U * re * bits_max(d);
-      rc = forward_slots(h, &c, B, workspace, st);
-      if (rc) return rc;
+      if (int rc = forward_slots(h, &c, B, workspace, st)) return rc;
     }
     return NRX_OK;
   }
@@ -623,8 +472,8 @@ static int forward_slots(nrx_handle* h, const nrx_io* io, int llr_B, void* works
     a.llr_B = llr_B;
     const FusedCtl fc = h->fused_ctl();
     const bool takes = fused_would_run(a, io->num_it, fc);
-    if (takes && h->have_last && h->last_stream != st && hipEventQuery(h->last_ev) == hipErrorNotReady)
-      return fail(NRX_ERR_BUSY, "a one-launch forward of this handle is still running on another stream");
+    if (takes)
+      if (int rc = busy(h, st)) return rc;
     e = launch_forward_f16(a, h->m16.W, io->num_it, st, h->prof, fc);
     if (e == hipSuccess && takes) {
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -640,8 +489,7 @@ static int forward_slots(nrx_handle* h, const nrx_io* io, int llr_B, void* works
     a.llr_B = llr_B;
     e = launch_forward_f64(a, h->m64.W, io->num_it, st, h->prof);
   }
-  if (e != hipSuccess) return hip_fail(e, "kernel launch");
-  return NRX_OK;
+  return launched(e, "kernel launch");
 }
 
 static size_t y_cgnn_bytes(const nrx_handle* h, const nrx_shape* s) {
@@ -650,8 +498,7 @@ static size_t y_cgnn_bytes(const nrx_handle* h, const nrx_shape* s) {
 
 int nrx_workspace_size_ex(const nrx_handle* h, const nrx_shape* shape, int32_t precision, int32_t y_layout,
                           size_t* bytes) {
-  int rc = nrx_workspace_size(h, shape, precision, bytes);
-  if (rc) return rc;
+  if (int rc = nrx_workspace_size(h, shape, precision, bytes)) return rc;
   if (y_layout < NRX_Y_CGNN || y_layout > NRX_Y_SPLIT) return fail(NRX_ERR_INVALID_ARG, "unknown y layout");
   if (y_layout != NRX_Y_CGNN) *bytes += y_cgnn_bytes(h, shape);
   return NRX_OK;
@@ -665,14 +512,11 @@ int nrx_forward_ex(nrx_handle* h, const nrx_io* io, int32_t y_layout, const floa
     return nrx_forward(h, io, workspace, workspace_bytes, stream);
   }
   size_t need = 0;
-  int rc = nrx_workspace_size_ex(h, &io->shape, io->precision, y_layout, &need);
-  if (rc) return rc;
-  if (!workspace || workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (int rc = nrx_workspace_size_ex(h, &io->shape, io->precision, y_layout, &need)) return rc;
+  if (!workspace || workspace_bytes < need) return too_small(need);
   if (!io->y || ((y_layout == NRX_Y_SPLIT) != (y_imag != nullptr)))
     return fail(NRX_ERR_INVALID_ARG, "y / y_imag do not match the y layout");
-  bool takes = false;
-  if ((rc = fused_busy(h, io, (hipStream_t)stream, &takes))) return rc;
+  if (int rc = fused_busy(h, io, (hipStream_t)stream)) return rc;
   const size_t yb = y_cgnn_bytes(h, &io->shape);
   float* ycg = (float*)workspace;
   hipError_t e = launch_y_layout(io->y, y_imag, y_layout, io->shape.batch, io->shape.num_subcarriers,
@@ -720,11 +564,9 @@ AerialWs aerial_layout(const nrx_handle* h, const nrx_aerial_io* io, void* base,
 
 int check_aerial(const nrx_handle* h, const nrx_aerial_io* io) {
   if (!h || !io) return fail(NRX_ERR_INVALID_ARG, "null argument");
-  int rc = check_shape(&io->shape);
-  if (rc) return rc;
+  if (int rc = check_shape(&io->shape)) return rc;
   if (io->shape.num_subcarriers % 12) return fail(NRX_ERR_SHAPE, "num_subcarriers must be a multiple of 12 (PRBs)");
-  if (io->num_dmrs_symbols < 1 || io->num_dmrs_symbols > 14)
-    return fail(NRX_ERR_SHAPE, "num_dmrs_symbols must be 1..14");
+  if (int rc = check_range("num_dmrs_symbols", io->num_dmrs_symbols, 1, 14)) return rc;
   if (io->num_dmrs_subcarriers < 2 || io->num_dmrs_subcarriers > 12 || io->num_dmrs_subcarriers % 2)
     return fail(NRX_ERR_SHAPE, "num_dmrs_subcarriers must be even and 2..12 (FOCC pairs)");
   return NRX_OK;
@@ -748,54 +590,36 @@ hipError_t aerial_prepare(const nrx_handle* h, const nrx_aerial_io* io, float* y
 
 int nrx_aerial_preprocess(const nrx_handle* h, const nrx_aerial_io* io, float* y, float* h_hat, float* pe,
                           int32_t* nn, void* stream) {
-  int rc = check_aerial(h, io);
-  if (rc) return rc;
+  if (int rc = check_aerial(h, io)) return rc;
   if (!io->y_real || !io->y_imag || !io->h_ls_real || !io->h_ls_imag || !io->dmrs_ofdm_pos ||
       !io->dmrs_subcarrier_pos)
     return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (!y || !h_hat || !pe || !nn) return fail(NRX_ERR_INVALID_ARG, "null output pointer");
-  hipError_t e = aerial_prepare(h, io, y, h_hat, pe, nn, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "aerial preprocessing launch");
-  return NRX_OK;
+  return launched(aerial_prepare(h, io, y, h_hat, pe, nn, (hipStream_t)stream), "aerial preprocessing launch");
 }
 
 int nrx_aerial_workspace_size(const nrx_handle* h, const nrx_aerial_io* io, size_t* bytes) {
-  int rc = check_aerial(h, io);
-  if (rc) return rc;
+  if (int rc = check_aerial(h, io)) return rc;
   if (!bytes) return fail(NRX_ERR_INVALID_ARG, "null argument");
   size_t cg = 0;
-  rc = nrx_workspace_size(h, &io->shape, io->precision, &cg);
-  if (rc) return rc;
+  if (int rc = nrx_workspace_size(h, &io->shape, io->precision, &cg)) return rc;
   *bytes = aerial_layout(h, io, nullptr, cg).total;
   return NRX_OK;
 }
 
 int nrx_forward_aerial(nrx_handle* h, const nrx_aerial_io* io, void* workspace, size_t workspace_bytes,
                        void* stream) {
-  int rc = check_aerial(h, io);
-  if (rc) return rc;
+  if (int rc = check_aerial(h, io)) return rc;
   if (!io->y_real || !io->y_imag || !io->h_ls_real || !io->h_ls_imag || !io->dmrs_port_mask ||
       !io->dmrs_ofdm_pos || !io->dmrs_subcarrier_pos || !io->llr)
     return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   size_t cg = 0;
-  rc = nrx_workspace_size(h, &io->shape, io->precision, &cg);
-  if (rc) return rc;
+  if (int rc = nrx_workspace_size(h, &io->shape, io->precision, &cg)) return rc;
   const AerialWs w = aerial_layout(h, io, workspace, cg);
-  if (!workspace || workspace_bytes < w.total)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(w.total) + " bytes");
+  if (!workspace || workspace_bytes < w.total) return too_small(w.total);
   const nrx_shape& s = io->shape;
   hipStream_t st = (hipStream_t)stream;
-  {
-    nrx_io q{};
-    q.shape = s;
-    q.num_it = io->num_it;
-    q.precision = io->precision;
-    bool takes = false;
-    if ((rc = fused_busy(h, &q, st, &takes))) return rc;
-  }
-  hipError_t e = aerial_prepare(h, io, w.y, w.h, w.pe, w.nn, st);
-  if (e != hipSuccess) return hip_fail(e, "aerial preprocessing launch");
-  nrx_io cio{};
+  nrx_io cio{};   // the CGNN forward on the preprocessed tensors (mcs_mask NULL)
   cio.shape = s;
   cio.num_it = io->num_it;
   cio.precision = io->precision;
@@ -803,16 +627,15 @@ int nrx_forward_aerial(nrx_handle* h, const nrx_aerial_io* io, void* workspace, 
   cio.pe = w.pe;
   cio.h_hat = w.h;
   cio.active = io->dmrs_port_mask;
-  cio.mcs_mask = nullptr;
   cio.llr = w.llr;
   cio.h_ref = io->h_hat;
-  rc = nrx_forward(h, &cio, w.cgnn, w.cgnn_bytes, stream);
-  if (rc) return rc;
-  const int bits0 = h->desc.var_mcs_masking ? bits_max(&h->desc) : h->desc.bits[0];
-  e = launch_aerial_llr(w.llr, s.batch, s.num_tx, s.num_subcarriers, s.num_symbols, bits_max(&h->desc), bits0,
-                        io->llr, st);
-  if (e != hipSuccess) return hip_fail(e, "aerial LLR layout launch");
-  return NRX_OK;
+  if (int rc = fused_busy(h, &cio, st)) return rc;
+  hipError_t e = aerial_prepare(h, io, w.y, w.h, w.pe, w.nn, st);
+  if (e != hipSuccess) return hip_fail(e, "aerial preprocessing launch");
+  if (int rc = nrx_forward(h, &cio, w.cgnn, w.cgnn_bytes, stream)) return rc;
+  return launched(launch_aerial_llr(w.llr, s.batch, s.num_tx, s.num_subcarriers, s.num_symbols, bits_max(&h->desc),
+                                    head_bits(&h->desc, 0), io->llr, st),
+                  "aerial LLR layout launch");
 }
 
 int nrx_llr_demap(const float* llr, int32_t batch, int32_t num_tx, int32_t num_subcarriers, int32_t num_symbols,
@@ -822,40 +645,26 @@ int nrx_llr_demap(const float* llr, int32_t batch, int32_t num_tx, int32_t num_s
   if (batch < 1 || num_tx < 1 || num_subcarriers < 1 || num_symbols < 1 || bits < 1 || bits > bits_stride ||
       n_data < 1 || n_data > num_subcarriers * num_symbols)
     return fail(NRX_ERR_SHAPE, "inconsistent demap shape");
-  hipError_t e = launch_llr_demap(llr, batch, num_tx, num_subcarriers, num_symbols, bits_stride, bits, data_re,
-                                  n_data, out, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "llr demap launch");
-  return NRX_OK;
+  return launched(launch_llr_demap(llr, batch, num_tx, num_subcarriers, num_symbols, bits_stride, bits, data_re,
+                                   n_data, out, (hipStream_t)stream),
+                  "llr demap launch");
 }
 
 static int check_gen(const nrx_gen_desc* d) {
   if (!d) return fail(NRX_ERR_INVALID_ARG, "desc is NULL");
-  if (d->batch < 1 || d->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (d->num_tx < 1 || d->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
-  if (d->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
-  if (d->num_subcarriers < 2 || d->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 2..3300");
-  if (d->num_rx_ant < 1 || d->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
-  if (d->num_dmrs_symbols < 1 || d->num_dmrs_symbols > 4) return fail(NRX_ERR_SHAPE, "num_dmrs_symbols must be 1..4");
+  if (int rc = check_grid_ant(d, kMaxUsers, /*min_subcarriers=*/2)) return rc;
   int mask = 0;
-  for (int k = 0; k < d->num_dmrs_symbols; ++k) {
-    const int t = d->dmrs_symbols[k];
-    if (t < 0 || t >= kT || (k && t <= d->dmrs_symbols[k - 1]))
-      return fail(NRX_ERR_INVALID_ARG, "dmrs_symbols must be ascending symbol indices");
-    mask |= 1 << t;
-  }
+  if (int rc = check_dmrs_symbols(d->dmrs_symbols, d->num_dmrs_symbols, &mask)) return rc;
   if (mask != d->dmrs_symbol_mask) return fail(NRX_ERR_INVALID_ARG, "dmrs_symbol_mask does not match dmrs_symbols");
-  if (d->num_mcs < 1 || d->num_mcs > 8) return fail(NRX_ERR_INVALID_ARG, "num_mcs must be 1..8");
-  for (int m = 0; m < d->num_mcs; ++m)
-    if (d->mcs_bits[m] != 2 && d->mcs_bits[m] != 4 && d->mcs_bits[m] != 6)
-      return fail(NRX_ERR_INVALID_ARG, "mcs_bits must be 2, 4 or 6");
-  for (int u = 0; u < d->num_tx; ++u) {
-    if (d->cdm_group[u] != 0 && d->cdm_group[u] != 1) return fail(NRX_ERR_INVALID_ARG, "cdm_group must be 0/1");
+  if (int rc = check_mcs_bits(d->mcs_bits, d->num_mcs, /*qam=*/true, NRX_ERR_INVALID_ARG)) return rc;
+  if (int rc = check_cdm_group(d->cdm_group, d->num_tx)) return rc;
+  for (int u = 0; u < d->num_tx; ++u)
     if (d->mcs_of_user[u] < -1 || d->mcs_of_user[u] >= d->num_mcs)
       return fail(NRX_ERR_INVALID_ARG, "mcs_of_user must be -1..num_mcs-1");
-  }
   if (d->num_active < 1 || d->num_active > d->num_tx) return fail(NRX_ERR_INVALID_ARG, "num_active must be 1..num_tx");
-  if (d->num_taps < 1 || d->num_taps > 8) return fail(NRX_ERR_INVALID_ARG, "num_taps must be 1..8");
-  if (d->num_sinusoids < 1 || d->num_sinusoids > 16) return fail(NRX_ERR_INVALID_ARG, "num_sinusoids must be 1..16");
+  if (int rc = check_range("num_taps", d->num_taps, 1, 8, NRX_ERR_INVALID_ARG)) return rc;
+  if (int rc = check_range("num_sinusoids", d->num_sinusoids, 1, 16, NRX_ERR_INVALID_ARG)) return rc;
+  // an infinite spread or noise power passes, as it always has: only NaN and the sign are refused
   if (!(d->max_delay_s >= 0.0) || !(d->max_doppler_hz >= 0.0) || !(d->subcarrier_spacing > 0.0) || !(d->no >= 0.0))
     return fail(NRX_ERR_INVALID_ARG, "channel parameters must be finite and non-negative (scs > 0)");
   if (d->slot_offset < 0) return fail(NRX_ERR_INVALID_ARG, "slot_offset must be >= 0");
@@ -864,9 +673,7 @@ static int check_gen(const nrx_gen_desc* d) {
 
 int nrx_gen_workspace_size(const nrx_gen_desc* desc, size_t* bytes) {
   if (int rc = check_gen(desc)) return rc;
-  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
-  *bytes = gen_workspace_bytes(*desc, nullptr, nullptr);
-  return NRX_OK;
+  return store_size(bytes, gen_workspace_bytes(*desc, nullptr, nullptr));
 }
 
 int nrx_generate_slots(const nrx_gen_desc* desc, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
@@ -878,38 +685,27 @@ int nrx_generate_slots_ex(const nrx_gen_desc* desc, const nrx_gen_chan* chan, co
                           size_t workspace_bytes, void* stream) {
   if (int rc = check_gen(desc)) return rc;
   nrx_gen_chan c{};                          // NULL chan: every port has the desc's scalars, no mixing
-  if (chan) {
-    for (int u = 0; u < desc->num_tx; ++u) {
-      if (!(chan->max_delay_s[u] >= 0.0) || !std::isfinite(chan->max_delay_s[u]) ||
-          !(chan->max_doppler_hz[u] >= 0.0) || !std::isfinite(chan->max_doppler_hz[u]))
-        return fail(NRX_ERR_INVALID_ARG, "per-port delay and Doppler spreads must be finite and non-negative");
-      c.max_delay_s[u] = chan->max_delay_s[u];
-      c.max_doppler_hz[u] = chan->max_doppler_hz[u];
-    }
-    if ((uintptr_t)chan->rx_mix & 7) return fail(NRX_ERR_INVALID_ARG, "rx_mix must be 8-byte aligned");
-    c.rx_mix = chan->rx_mix;
-  } else {
-    for (int u = 0; u < desc->num_tx; ++u) {
-      c.max_delay_s[u] = desc->max_delay_s;
-      c.max_doppler_hz[u] = desc->max_doppler_hz;
-    }
+  for (int u = 0; u < desc->num_tx; ++u) {
+    c.max_delay_s[u] = chan ? chan->max_delay_s[u] : desc->max_delay_s;
+    c.max_doppler_hz[u] = chan ? chan->max_doppler_hz[u] : desc->max_doppler_hz;
+    if (!chan) continue;
+    if (int rc = check_nonneg("per-port delay spread", c.max_delay_s[u])) return rc;
+    if (int rc = check_nonneg("per-port Doppler spread", c.max_doppler_hz[u])) return rc;
   }
-  if (!out || !out->y || !workspace) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  int bmax = 0;
-  for (int m = 0; m < desc->num_mcs; ++m) bmax = desc->mcs_bits[m] > bmax ? desc->mcs_bits[m] : bmax;
-  if (out->bits && out->bits_stride < bmax) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
+  if (chan && ((uintptr_t)chan->rx_mix & 7)) return fail(NRX_ERR_INVALID_ARG, "rx_mix must be 8-byte aligned");
+  c.rx_mix = chan ? chan->rx_mix : nullptr;
+  if (!out || !out->y) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (out->bits)
+    if (int rc = check_bits_stride(out->bits_stride, desc->mcs_bits, desc->num_mcs)) return rc;
   if ((out->y_real == nullptr) != (out->y_imag == nullptr) || (out->h_ls_real == nullptr) != (out->h_ls_imag == nullptr))
     return fail(NRX_ERR_INVALID_ARG, "Aerial outputs come in (real, imag) pairs");
   if (out->h_ls_real && desc->num_subcarriers % 12)
     return fail(NRX_ERR_SHAPE, "Aerial pilot list needs num_subcarriers % 12 == 0");
-  const size_t need = gen_workspace_bytes(*desc, nullptr, nullptr);
-  if (workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  hipError_t e = launch_generate(*desc, c, *out, workspace, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "slot generator launch");
-  return NRX_OK;
+  if (int rc = check_workspace(workspace, workspace_bytes, gen_workspace_bytes(*desc, nullptr, nullptr), 1)) return rc;
+  return launched(launch_generate(*desc, c, *out, workspace, (hipStream_t)stream), "slot generator launch");
 }
 
+// llr / bits of any slot count, with up to 31 symbols (the mask's bits): not the 14-symbol grid
 int nrx_count_errors(const nrx_count_io* io, void* stream) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "null argument");
   if (!io->llr || !io->bits || !io->active || !io->counts) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
@@ -919,79 +715,43 @@ int nrx_count_errors(const nrx_count_io* io, void* stream) {
   for (int m = 0; m < io->num_mcs; ++m)
     if (io->mcs_bits[m] < 1 || io->mcs_bits[m] > io->bits_stride)
       return fail(NRX_ERR_SHAPE, "mcs_bits must be 1..bits_stride");
-  hipError_t e = launch_count_errors(*io, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "error counter launch");
-  return NRX_OK;
+  return launched(launch_count_errors(*io, (hipStream_t)stream), "error counter launch");
 }
 
-int nrx_lmmse_detect(const nrx_lmmse_io* io, void* stream) {
+// the fields nrx_lmmse_io and nrx_kbest_io share
+extern "C++" {
+template <class IO>
+static int check_detector(const IO* io) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
   if (!io->y || !io->h || !io->active || !io->llr) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
-  if (!(io->err_var >= 0.0) || !std::isfinite(io->err_var))
-    return fail(NRX_ERR_INVALID_ARG, "err_var must be finite and >= 0");
-  if (io->num_mcs < 1 || io->num_mcs > 8) return fail(NRX_ERR_SHAPE, "num_mcs must be 1..8");
-  int bmax = 0;
-  for (int m = 0; m < io->num_mcs; ++m) {
-    if (io->mcs_bits[m] != 2 && io->mcs_bits[m] != 4 && io->mcs_bits[m] != 6)
-      return fail(NRX_ERR_INVALID_ARG, "mcs_bits must be 2, 4 or 6");
-    bmax = io->mcs_bits[m] > bmax ? io->mcs_bits[m] : bmax;
-  }
-  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
-  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
-  if (io->num_tx < 1) return fail(NRX_ERR_SHAPE, "num_tx must be >= 1");
-  if (io->num_tx > 8) return fail(NRX_ERR_UNSUPPORTED, "the LMMSE kernel is built for num_tx <= 8");
-  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
-  if (io->bits_stride < bmax) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
-  hipError_t e = launch_lmmse(*io, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "lmmse detector launch");
-  return NRX_OK;
+  if (int rc = check_pos("no", io->no)) return rc;
+  if (int rc = check_nonneg("err_var", io->err_var)) return rc;
+  if (int rc = check_mcs_bits(io->mcs_bits, io->num_mcs, /*qam=*/true)) return rc;
+  if (int rc = check_grid_ant(io, /*tx_supported=*/8)) return rc;
+  return check_bits_stride(io->bits_stride, io->mcs_bits, io->num_mcs);
+}
+}  // extern "C++"
+
+int nrx_lmmse_detect(const nrx_lmmse_io* io, void* stream) {
+  if (int rc = check_detector(io)) return rc;
+  return launched(launch_lmmse(*io, (hipStream_t)stream), "lmmse detector launch");
 }
 
 static int check_kbest(const nrx_kbest_io* io) {
-  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
-  if (!io->y || !io->h || !io->active || !io->llr) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
-  if (!(io->err_var >= 0.0) || !std::isfinite(io->err_var))
-    return fail(NRX_ERR_INVALID_ARG, "err_var must be finite and >= 0");
-  if (!(io->llr_clip > 0.0) || !std::isfinite(io->llr_clip))
-    return fail(NRX_ERR_INVALID_ARG, "llr_clip must be finite and > 0");
-  if (io->k < 1 || io->k > 64) return fail(NRX_ERR_INVALID_ARG, "k must be 1..64");
-  if (io->num_mcs < 1 || io->num_mcs > 8) return fail(NRX_ERR_SHAPE, "num_mcs must be 1..8");
-  int bmax = 0;
-  for (int m = 0; m < io->num_mcs; ++m) {
-    if (io->mcs_bits[m] != 2 && io->mcs_bits[m] != 4 && io->mcs_bits[m] != 6)
-      return fail(NRX_ERR_INVALID_ARG, "mcs_bits must be 2, 4 or 6");
-    bmax = io->mcs_bits[m] > bmax ? io->mcs_bits[m] : bmax;
-  }
-  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
-  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
-  if (io->num_tx < 1) return fail(NRX_ERR_SHAPE, "num_tx must be >= 1");
-  if (io->num_tx > 8) return fail(NRX_ERR_UNSUPPORTED, "the K-best kernels are built for num_tx <= 8");
-  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
-  if (io->bits_stride < bmax) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
-  return NRX_OK;
+  if (int rc = check_detector(io)) return rc;
+  if (int rc = check_pos("llr_clip", io->llr_clip)) return rc;
+  return check_range("k", io->k, 1, 64, NRX_ERR_INVALID_ARG);
 }
 
 int nrx_kbest_workspace_size(const nrx_kbest_io* io, size_t* bytes) {
   if (int rc = check_kbest(io)) return rc;
-  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
-  *bytes = kbest_workspace_bytes(*io);
-  return NRX_OK;
+  return store_size(bytes, kbest_workspace_bytes(*io));
 }
 
 int nrx_kbest_detect(const nrx_kbest_io* io, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_kbest(io)) return rc;
-  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
-  if ((uintptr_t)workspace & 15) return fail(NRX_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-  const size_t need = kbest_workspace_bytes(*io);
-  if (workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  hipError_t e = launch_kbest(*io, workspace, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "k-best detector launch");
-  return NRX_OK;
+  if (int rc = check_workspace(workspace, workspace_bytes, kbest_workspace_bytes(*io), 16)) return rc;
+  return launched(launch_kbest(*io, workspace, (hipStream_t)stream), "k-best detector launch");
 }
 
 // nrx_cov_io and nrx_cov_space_io carry the same fields
@@ -1000,69 +760,39 @@ template <class IO>
 static int check_cov(const IO* io) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
   if (!io->h || !io->acc) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
-  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
-  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
-  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
-  return NRX_OK;
+  return check_grid_ant(io);
 }
 }  // extern "C++"
 
 int nrx_cov_workspace_size(const nrx_cov_io* io, size_t* bytes) {
   if (int rc = check_cov(io)) return rc;
-  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
-  *bytes = cov_workspace_bytes(*io);
-  return NRX_OK;
+  return store_size(bytes, cov_workspace_bytes(*io));
 }
 
 int nrx_cov_accumulate(const nrx_cov_io* io, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_cov(io)) return rc;
-  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
-  const size_t need = cov_workspace_bytes(*io);
-  if (workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  hipError_t e = launch_cov_accumulate(*io, workspace, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "covariance launch");
-  return NRX_OK;
+  if (int rc = check_workspace(workspace, workspace_bytes, cov_workspace_bytes(*io), 1)) return rc;
+  return launched(launch_cov_accumulate(*io, workspace, (hipStream_t)stream), "covariance launch");
 }
 
 int nrx_cov_space_workspace_size(const nrx_cov_space_io* io, size_t* bytes) {
   if (int rc = check_cov(io)) return rc;
-  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
-  *bytes = cov_space_workspace_bytes(*io);
-  return NRX_OK;
+  return store_size(bytes, cov_space_workspace_bytes(*io));
 }
 
 int nrx_cov_space_accumulate(const nrx_cov_space_io* io, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_cov(io)) return rc;
-  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
-  const size_t need = cov_space_workspace_bytes(*io);
-  if (workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  hipError_t e = launch_cov_space(*io, workspace, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "spatial covariance launch");
-  return NRX_OK;
+  if (int rc = check_workspace(workspace, workspace_bytes, cov_space_workspace_bytes(*io), 1)) return rc;
+  return launched(launch_cov_space(*io, workspace, (hipStream_t)stream), "spatial covariance launch");
 }
 
 // the shape, DMRS and group fields that nrx_chest_io and nrx_chest3_io share
 extern "C++" {
 template <class IO>
 static int check_chest_shape(const IO* io) {
-  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
-  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
-  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
-  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
-  if (io->num_dmrs_symbols < 1 || io->num_dmrs_symbols > 4) return fail(NRX_ERR_SHAPE, "num_dmrs_symbols must be 1..4");
-  for (int k = 0; k < io->num_dmrs_symbols; ++k) {
-    const int t = io->dmrs_symbols[k];
-    if (t < 0 || t >= kT || (k && t <= io->dmrs_symbols[k - 1]))
-      return fail(NRX_ERR_INVALID_ARG, "dmrs_symbols must be ascending symbol indices below 14");
-  }
-  for (int u = 0; u < io->num_tx; ++u)
-    if (io->cdm_group[u] != 0 && io->cdm_group[u] != 1) return fail(NRX_ERR_INVALID_ARG, "cdm_group must be 0/1");
-  return NRX_OK;
+  if (int rc = check_grid_ant(io)) return rc;
+  if (int rc = check_dmrs_symbols(io->dmrs_symbols, io->num_dmrs_symbols)) return rc;
+  return check_cdm_group(io->cdm_group, io->num_tx);
 }
 }  // extern "C++"
 
@@ -1071,22 +801,18 @@ static int check_chest(const nrx_chest_io* io, bool lmmse) {
   if (!io->h_hat || !io->active || !io->h_out) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (lmmse && (!io->filt || !io->tcoef || !io->vconj)) return fail(NRX_ERR_INVALID_ARG, "null table pointer");
   if (lmmse && ((uintptr_t)io->filt & 7)) return fail(NRX_ERR_INVALID_ARG, "filt must be 8-byte aligned");
-  if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
+  if (int rc = check_pos("no", io->no)) return rc;
   return check_chest_shape(io);
 }
 
 int nrx_chest_lmmse(const nrx_chest_io* io, void* stream) {
   if (int rc = check_chest(io, true)) return rc;
-  hipError_t e = launch_chest_lmmse(*io, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "lmmse channel estimator launch");
-  return NRX_OK;
+  return launched(launch_chest_lmmse(*io, (hipStream_t)stream), "lmmse channel estimator launch");
 }
 
 int nrx_chest_lin(const nrx_chest_io* io, void* stream) {
   if (int rc = check_chest(io, false)) return rc;
-  hipError_t e = launch_chest_lin(*io, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "linear channel estimator launch");
-  return NRX_OK;
+  return launched(launch_chest_lin(*io, (hipStream_t)stream), "linear channel estimator launch");
 }
 
 static int check_chest3(const nrx_chest3_io* io, bool tables) {
@@ -1096,105 +822,73 @@ static int check_chest3(const nrx_chest3_io* io, bool tables) {
     if (!io->qh || !io->gf || !io->nu || !io->tcoef || !io->vconj || !io->lam || !io->vs || !io->mu)
       return fail(NRX_ERR_INVALID_ARG, "null table pointer");
     if (((uintptr_t)io->qh | (uintptr_t)io->gf) & 7) return fail(NRX_ERR_INVALID_ARG, "qh and gf must be 8-byte aligned");
-    if (!(io->no > 0.0) || !std::isfinite(io->no)) return fail(NRX_ERR_INVALID_ARG, "no must be finite and > 0");
+    if (int rc = check_pos("no", io->no)) return rc;
   }
   return check_chest_shape(io);
 }
 
 int nrx_chest3_workspace_size(const nrx_chest3_io* io, size_t* bytes) {
   if (int rc = check_chest3(io, false)) return rc;
-  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
-  *bytes = chest3_workspace_bytes(*io);
-  return NRX_OK;
+  return store_size(bytes, chest3_workspace_bytes(*io));
 }
 
 int nrx_chest_lmmse3(const nrx_chest3_io* io, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_chest3(io, true)) return rc;
-  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
-  if ((uintptr_t)workspace & 3) return fail(NRX_ERR_INVALID_ARG, "workspace must be 4-byte aligned");
-  const size_t need = chest3_workspace_bytes(*io);
-  if (workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  hipError_t e = launch_chest_lmmse3(*io, workspace, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "3-D lmmse channel estimator launch");
-  return NRX_OK;
+  if (int rc = check_workspace(workspace, workspace_bytes, chest3_workspace_bytes(*io), 4)) return rc;
+  return launched(launch_chest_lmmse3(*io, workspace, (hipStream_t)stream), "3-D lmmse channel estimator launch");
 }
+
+// the LLR-tensor fields that nrx_llr_stats_io and nrx_ldpc_gather_io take over from nrx_count_io, on
+// the 14-symbol grid and with 1..8 bits per symbol
+extern "C++" {
+template <class IO>
+static int check_llr_grid(const IO* io) {
+  if (int rc = check_symbol_mask("dmrs_symbol_mask", io->dmrs_symbol_mask)) return rc;
+  if (int rc = check_mcs_bits(io->mcs_bits, io->num_mcs, /*qam=*/false)) return rc;
+  if (int rc = check_grid(io)) return rc;
+  if (io->num_heads != 1 && io->num_heads != io->num_mcs) return fail(NRX_ERR_SHAPE, "num_heads must be 1 or num_mcs");
+  return check_bits_stride(io->bits_stride, io->mcs_bits, io->num_mcs);
+}
+}  // extern "C++"
 
 static int check_llr_stats(const nrx_llr_stats_io* io) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
   if (!io->llr || !io->bits || !io->active || !io->loss || !io->cnt || !io->nonfinite)
     return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  if (io->num_scales < 1 || io->num_scales > 16) return fail(NRX_ERR_INVALID_ARG, "num_scales must be 1..16");
+  if (int rc = check_range("num_scales", io->num_scales, 1, 16, NRX_ERR_INVALID_ARG)) return rc;
   for (int s = 0; s < io->num_scales; ++s)
-    if (!(io->scales[s] > 0.0) || !std::isfinite(io->scales[s]))
-      return fail(NRX_ERR_INVALID_ARG, "scales must be finite and > 0");
-  if (io->dmrs_symbol_mask < 0 || io->dmrs_symbol_mask >= (1 << kT))
-    return fail(NRX_ERR_INVALID_ARG, "dmrs_symbol_mask must be a mask of the 14 symbols");
-  if (io->num_mcs < 1 || io->num_mcs > 8) return fail(NRX_ERR_SHAPE, "num_mcs must be 1..8");
-  int bmax = 0;
-  for (int m = 0; m < io->num_mcs; ++m) {
-    if (io->mcs_bits[m] < 1 || io->mcs_bits[m] > 8) return fail(NRX_ERR_INVALID_ARG, "mcs_bits must be 1..8");
-    bmax = io->mcs_bits[m] > bmax ? io->mcs_bits[m] : bmax;
-  }
-  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
-  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
-  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
-  if (io->num_heads != 1 && io->num_heads != io->num_mcs) return fail(NRX_ERR_SHAPE, "num_heads must be 1 or num_mcs");
-  if (io->bits_stride < bmax) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
-  return NRX_OK;
+    if (int rc = check_pos("scales", io->scales[s])) return rc;
+  return check_llr_grid(io);
 }
 
 int nrx_llr_stats_workspace_size(const nrx_llr_stats_io* io, size_t* bytes) {
   if (int rc = check_llr_stats(io)) return rc;
-  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
-  *bytes = llr_stats_workspace_bytes(*io);
-  return NRX_OK;
+  return store_size(bytes, llr_stats_workspace_bytes(*io));
 }
 
 int nrx_llr_stats(const nrx_llr_stats_io* io, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_llr_stats(io)) return rc;
-  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
-  if ((uintptr_t)workspace & 7) return fail(NRX_ERR_INVALID_ARG, "workspace must be 8-byte aligned");
-  const size_t need = llr_stats_workspace_bytes(*io);
-  if (workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  hipError_t e = launch_llr_stats(*io, workspace, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "llr statistics launch");
-  return NRX_OK;
+  if (int rc = check_workspace(workspace, workspace_bytes, llr_stats_workspace_bytes(*io), 8)) return rc;
+  return launched(launch_llr_stats(*io, workspace, (hipStream_t)stream), "llr statistics launch");
 }
 
 static int check_nmse(const nrx_nmse_io* io) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
   if (!io->h_est || !io->h_true || !io->active || !io->err || !io->ref || !io->items)
     return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  if (io->symbol_mask < 0 || io->symbol_mask >= (1 << kT))
-    return fail(NRX_ERR_INVALID_ARG, "symbol_mask must be a mask of the 14 symbols");
-  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
-  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
-  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
-  if (io->num_rx_ant < 1 || io->num_rx_ant > 16) return fail(NRX_ERR_SHAPE, "num_rx_ant must be 1..16");
-  return NRX_OK;
+  if (int rc = check_symbol_mask("symbol_mask", io->symbol_mask)) return rc;
+  return check_grid_ant(io);
 }
 
 int nrx_nmse_workspace_size(const nrx_nmse_io* io, size_t* bytes) {
   if (int rc = check_nmse(io)) return rc;
-  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
-  *bytes = nmse_workspace_bytes(*io);
-  return NRX_OK;
+  return store_size(bytes, nmse_workspace_bytes(*io));
 }
 
 int nrx_chest_nmse(const nrx_nmse_io* io, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_nmse(io)) return rc;
-  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
-  if ((uintptr_t)workspace & 7) return fail(NRX_ERR_INVALID_ARG, "workspace must be 8-byte aligned");
-  const size_t need = nmse_workspace_bytes(*io);
-  if (workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  hipError_t e = launch_chest_nmse(*io, workspace, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "channel nmse launch");
-  return NRX_OK;
+  if (int rc = check_workspace(workspace, workspace_bytes, nmse_workspace_bytes(*io), 8)) return rc;
+  return launched(launch_chest_nmse(*io, workspace, (hipStream_t)stream), "channel nmse launch");
 }
 
 // ---- QC-LDPC decoder: the host table is validated and packed into per-layer edge lists
@@ -1266,15 +960,13 @@ void nrx_ldpc_destroy(nrx_ldpc* h) {
 static int check_ldpc_io(const nrx_ldpc_io* io) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
   if (!io->llr_in || !io->hard || !io->iters || !io->parity_ok) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  if (io->num_iter < 1 || io->num_iter > 100) return fail(NRX_ERR_INVALID_ARG, "num_iter must be 1..100");
+  if (int rc = check_range("num_iter", io->num_iter, 1, 100, NRX_ERR_INVALID_ARG)) return rc;
   if (io->cn_type != 0 && io->cn_type != 1) return fail(NRX_ERR_INVALID_ARG, "cn_type must be 0 (boxplus) or 1 (min-sum)");
   if (io->early_stop != 0 && io->early_stop != 1) return fail(NRX_ERR_INVALID_ARG, "early_stop must be 0 or 1");
   if (io->cn_type == 1 && !(io->ms_scale > 0.0f && io->ms_scale <= 1.0f))
     return fail(NRX_ERR_INVALID_ARG, "ms_scale must be in (0, 1]");
-  if (!(io->llr_clip > 0.0f) || !std::isfinite(io->llr_clip))
-    return fail(NRX_ERR_INVALID_ARG, "llr_clip must be finite and > 0");
-  if (io->num_cw < 1 || io->num_cw > (1 << 20)) return fail(NRX_ERR_SHAPE, "num_cw must be 1..2^20");
-  return NRX_OK;
+  if (int rc = check_pos("llr_clip", io->llr_clip)) return rc;
+  return check_range("num_cw", io->num_cw, 1, 1 << 20);
 }
 
 static size_t ldpc_workspace_bytes(const nrx_ldpc* h, const nrx_ldpc_io* io) {
@@ -1285,65 +977,40 @@ static size_t ldpc_workspace_bytes(const nrx_ldpc* h, const nrx_ldpc_io* io) {
 int nrx_ldpc_workspace_size(const nrx_ldpc* h, const nrx_ldpc_io* io, size_t* bytes) {
   if (int rc = check_ldpc_io(io)) return rc;
   if (!h) return fail(NRX_ERR_INVALID_ARG, "null handle");
-  if (!bytes) return fail(NRX_ERR_INVALID_ARG, "bytes is NULL");
-  *bytes = ldpc_workspace_bytes(h, io);
-  return NRX_OK;
+  return store_size(bytes, ldpc_workspace_bytes(h, io));
 }
 
 int nrx_ldpc_decode(nrx_ldpc* h, const nrx_ldpc_io* io, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_ldpc_io(io)) return rc;
   if (!h) return fail(NRX_ERR_INVALID_ARG, "null handle");
-  if (!workspace) return fail(NRX_ERR_INVALID_ARG, "null workspace pointer");
-  if ((uintptr_t)workspace & 15) return fail(NRX_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-  const size_t need = ldpc_workspace_bytes(h, io);
-  if (workspace_bytes < need)
-    return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (int rc = check_workspace(workspace, workspace_bytes, ldpc_workspace_bytes(h, io), 16)) return rc;
   if (h->device < 0) return fail(NRX_ERR_INVALID_ARG, "no device: the handle was created with device = -1");
-  hipError_t e = launch_ldpc_decode(h->d, *io, workspace, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "ldpc decode launch");
-  return NRX_OK;
+  return launched(launch_ldpc_decode(h->d, *io, workspace, (hipStream_t)stream), "ldpc decode launch");
 }
 
 int nrx_ldpc_gather(const nrx_ldpc_gather_io* io, void* stream) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
   if (!io->llr || !io->bits || !io->active || !io->llr_in || !io->skip)
     return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  if (io->dmrs_symbol_mask < 0 || io->dmrs_symbol_mask >= (1 << kT))
-    return fail(NRX_ERR_INVALID_ARG, "dmrs_symbol_mask must be a mask of the 14 symbols");
-  if (io->num_mcs < 1 || io->num_mcs > 8) return fail(NRX_ERR_SHAPE, "num_mcs must be 1..8");
-  int bmax = 0;
-  for (int m = 0; m < io->num_mcs; ++m) {
-    if (io->mcs_bits[m] < 1 || io->mcs_bits[m] > 8) return fail(NRX_ERR_INVALID_ARG, "mcs_bits must be 1..8");
-    bmax = io->mcs_bits[m] > bmax ? io->mcs_bits[m] : bmax;
-  }
-  if (io->num_symbols != kT) return fail(NRX_ERR_SHAPE, "num_symbols must be 14");
-  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (io->num_subcarriers < 1 || io->num_subcarriers > 3300) return fail(NRX_ERR_SHAPE, "num_subcarriers must be 1..3300");
-  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
-  if (io->num_heads != 1 && io->num_heads != io->num_mcs) return fail(NRX_ERR_SHAPE, "num_heads must be 1 or num_mcs");
-  if (io->bits_stride < bmax) return fail(NRX_ERR_SHAPE, "bits_stride < max(mcs_bits)");
-  if (io->num_cw_per_user < 1 || io->num_cw_per_user > 64) return fail(NRX_ERR_SHAPE, "num_cw_per_user must be 1..64");
+  if (int rc = check_llr_grid(io)) return rc;
+  if (int rc = check_range("num_cw_per_user", io->num_cw_per_user, 1, 64)) return rc;
+  if (int rc = check_range("n", io->n, 4, kLdpcMaxN)) return rc;
   if ((int64_t)io->batch * io->num_tx * io->num_cw_per_user > (1 << 20))
     return fail(NRX_ERR_SHAPE, "batch * num_tx * num_cw_per_user must be <= 2^20");
-  if (io->n < 4 || io->n > kLdpcMaxN) return fail(NRX_ERR_SHAPE, "n must be 4..26112");
-  if (io->n_tx < 1 || io->n_tx > (1 << 20)) return fail(NRX_ERR_SHAPE, "n_tx must be 1..2^20");
+  if (int rc = check_range("n_tx", io->n_tx, 1, 1 << 20)) return rc;
   if (!io->tx_col && io->n_tx > io->n) return fail(NRX_ERR_SHAPE, "n_tx > n needs a tx_col");
-  hipError_t e = launch_ldpc_gather(*io, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "ldpc gather launch");
-  return NRX_OK;
+  return launched(launch_ldpc_gather(*io, (hipStream_t)stream), "ldpc gather launch");
 }
 
 int nrx_ldpc_count(const nrx_ldpc_count_io* io, void* stream) {
   if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
   if (!io->hard || !io->skip || !io->counts) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
-  if (io->batch < 1 || io->batch > 65535) return fail(NRX_ERR_SHAPE, "batch must be 1..65535");
-  if (io->num_tx < 1 || io->num_tx > kMaxUsers) return fail(NRX_ERR_SHAPE, "num_tx must be 1..16");
-  if (io->num_cw_per_user < 1 || io->num_cw_per_user > 64) return fail(NRX_ERR_SHAPE, "num_cw_per_user must be 1..64");
-  if (io->n < 4 || io->n > kLdpcMaxN) return fail(NRX_ERR_SHAPE, "n must be 4..26112");
+  if (int rc = check_range("batch", io->batch, 1, 65535)) return rc;
+  if (int rc = check_range("num_tx", io->num_tx, 1, kMaxUsers)) return rc;
+  if (int rc = check_range("num_cw_per_user", io->num_cw_per_user, 1, 64)) return rc;
+  if (int rc = check_range("n", io->n, 4, kLdpcMaxN)) return rc;
   if (io->num_info < 1 || io->num_info > io->n) return fail(NRX_ERR_SHAPE, "num_info must be 1..n");
-  hipError_t e = launch_ldpc_count(*io, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "ldpc count launch");
-  return NRX_OK;
+  return launched(launch_ldpc_count(*io, (hipStream_t)stream), "ldpc count launch");
 }
 
 int nrx_profile_enable(nrx_handle* h, int32_t enable) {
@@ -1453,15 +1120,7 @@ int nrx_compute_pe(int32_t num_tx, int32_t F, int32_t T, const int32_t* dmrs_sym
 }
 
 double nrx_flops_per_re_user(const nrx_desc* d, int32_t num_it) {
-  if (check_desc(d)) return 0.0;
-  auto sep = [](double ci, double co) { return 9 * ci + ci * co; };
-  const double init = sep(init_cin(d), kHID) + sep(kHID, kHID) + sep(kHID, kDS);
-  const double it = kDS * kAGG + kAGG * kDS + sep(2 * kDS + 2, kHID) + sep(kHID, kHID) + sep(kHID, kDS);
-  double heads = 0;
-  for (int h = 0; h < num_heads(d); ++h)
-    heads += kDS * kHID + kHID * (d->var_mcs_masking ? bits_max(d) : d->bits[h]);
-  const double ch = kDS * kHID + kHID * 2.0 * d->num_rx_ant;
-  return 2.0 * (init * num_init(d) + num_it * it + heads + ch);
+  return check_desc(d) ? 0.0 : flops_per_re_user(d, num_it);
 }
 
 }  // extern "C"

@@ -751,7 +751,7 @@ struct EpiInPlace {
     constexpr int NQ = COUTP * (int)sizeof(S) / 16;
     if constexpr (sizeof(S) == 2) {
       // f16: the image of an in-place layer's output is in the K-permuted channel order of
-      // the consumer (nrx_api.cpp build_model, hpos): lane (t, g)'s 4 channels of tiles
+      // the consumer (nrx_model.cpp build_model, hpos): lane (t, g)'s 4 channels of tiles
       // 2kc and 2kc+1 are chunk 4kc + g, so each tile pair is one 16-byte store of the
       // lane's own values.  The lane's chunk addresses are formed once per pass (opaque
       // to LLVM so that they stay registers); a row adds r * slot_pitch as the DS
@@ -865,7 +865,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 // state run in the conv3 epilogue straight from the accumulators: the MFMA C layout of a
 // 16-channel tile (lane (t, g) holds channels 16 n + P::co(g, j)) is reused as the B
 // operand of the next MFMA, with that layer's K axis permuted on the host to match
-// (nrx_api.cpp, kperm_*).  After an update that is not the last, the epilogue applies
+// (nrx_model.cpp, kperm_channel).  After an update that is not the last, the epilogue applies
 // the aggregation MLP of the next iteration and stores act_u * sp_u; the next launch's
 // z-load (or k_combine for U > 2) forms the leave-one-out mean.  After the last update the
 // epilogue runs the LLR / ChEst readouts instead.
@@ -1619,7 +1619,7 @@ __device__ __forceinline__ void strip_block(const BlockParams<P>& prm, char* X, 
 // ---------------------------------------------------------------- per-user block bodies
 // StateInit_m of user u on the strip.  z = [y*ns | h*ns | pe] with each antenna block
 // padded to A2P channels (y at [0, 2A), h at [A2P, A2P+2A), pe at 2 A2P, 2 A2P + 1; the host
-// packs conv1's weights to match, nrx_api.cpp build_model).  One thread per (slot, symbol)
+// packs conv1's weights to match, nrx_model.cpp build_model).  One thread per (slot, symbol)
 // row of the z image: vector loads of the y / h rows and the pe pair, channel assembly in
 // registers at compile-time positions, then 16-byte LDS stores.
 template <int A2P>

@@ -4,7 +4,7 @@
 //   state / aggregate buffers  s, a : [B][U][F][14][56]   (compact, no padding in HBM;
 //                                     the kernels pad T -> 16 and channels in LDS)
 //   storage type: _Float16 (NRX_PREC_F16) or float (NRX_PREC_F32X)
-// Packed weights (one blob per precision, built by nrx_create):
+// Packed weights (one blob per precision, built by nrx_create: nrx_model.cpp):
 //   separable conv: dw [9][CINP] (tap = i*3 + j, i along F, j along T),
 //                   pwT [COUTP][CINP] (transposed pointwise kernel), bias [COUTP]
 //   dense:          wT [COUTP][CINP], bias [COUTP]
@@ -37,6 +37,9 @@ constexpr int kHalo = 3;      // 3 stacked 3x3 convs per block
 // workspace through one buffer descriptor with 32-bit offsets and marks zero chunks with offsets
 // at or beyond it; a larger forward runs in slot chunks (nrx_api.cpp chunk_slots)
 constexpr unsigned kGzRange = 0x40000000u;
+// StateInit pads each antenna block of its input z = [y | h | pe] to A2P channels; the weight packer
+// (nrx_model.cpp) and the launchers (nrx_launch.inc) pick the kernels' A2P with this one rule
+constexpr int init_a2p(int num_rx_ant) { return 2 * num_rx_ant <= 8 ? 8 : (2 * num_rx_ant <= 16 ? 16 : 32); }
 
 // ---- LDS images of the f16 weights (kernels: SepStage / DenseStage).  A W^T [COUTP][CINP] image is a stack
 // of 16-row tiles addressed like an activation image: element (co, chunk q of 8 inputs) at

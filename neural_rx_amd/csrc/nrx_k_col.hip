@@ -1,6 +1,7 @@
 // nrx_k_col.hip -- the whole-column register-resident launches (k_init_col, k_update_col;
 // nrx_col.inc), one code object of their own; called by the f16 24-row tier's launch loop
-// (Launch<P16>::run) for the stages the schedule mask gives them (nrx_update_schedule).
+// (Launch<P16>::run) for the stages the schedule mask gives them (nrx_update_schedule); the stage
+// plan of the one-launch column forward is nrx_launch.inc's plan_stage, as for every launcher.
 #include "nrx_device.inc"
 #include "nrx_launch.inc"
 
@@ -107,58 +108,25 @@ bool fwd_col_applicable(const FwdArgs<_Float16, float, _Float16>& a, int num_it,
 
 hipError_t launch_fwd_col(const FwdArgs<_Float16, float, _Float16>& args, const ModelW<_Float16, float>& W, int num_it,
                           hipStream_t st, Prof* prof, const FusedCtl& fc) {
-  auto B_ = [&](int kid) { if (prof) prof->begin(kid, st); };
-  auto E_ = [&](int kid) { if (prof) prof->end(kid, st); };
   ColFwdParams fp{};
   fp.sync = reinterpret_cast<FusedSync*>(fc.sync);
   fp.nst = 1 + num_it;
   fp.nq = xcc_count();
   fp.spin_limit = fc.spin_limit;
   fp.dbg_err = fc.dbg_err;
-  const int nq = args.F * kT * 2 * args.A / 4;
-  const bool norm_pre = nq > kNormFusedMaxQ;
-  if (norm_pre) {
-    B_(K_NORM);
-    k_norm<<<args.B, 1024, 0, st>>>(args.y, nq, args.norm);
-    E_(K_NORM);
-  }
-  FwdArgs<_Float16, float, _Float16> a = args;
+  const bool norm_pre = norm_prepass(args, st, prof);
   for (int s = 0; s < fp.nst; ++s) {
-    BlockParams<P16>& bp = fp.st[s];
+    BlockParams<P16>& bp = fp.st[s];   // in place (pair, order_rev stay 0)
+    plan_stage(bp, args, W, num_it, s, TAIL_READOUT_WB);
     bp.inline_combine = 1;
-    bp.pair = 0;
-    bp.order_rev = 0;
     bp.norm_pre = norm_pre;
     bp.strips = col_strips(args.F);
-    bp.m = 0;
     bp.gz = 1;
-    bp.llr[0][0] = W.llr[0][0];
-    bp.llr[0][1] = W.llr[0][1];
-    bp.chest[0] = W.chest[0];
-    bp.chest[1] = W.chest[1];
-    if (s == 0) {
-      for (int l = 0; l < 3; ++l) bp.w[l] = W.init[0][l];
-      bp.tail = TAIL_AGG;
-      bp.agg[0] = W.agg[0][0];
-      bp.agg[1] = W.agg[0][1];
-    } else {
-      std::swap(a.s_in, a.s_out);
-      std::swap(a.a, a.a_out);
-      const int i = s - 1;
-      for (int l = 0; l < 3; ++l) bp.w[l] = W.upd[i][l];
-      const bool last = i == num_it - 1;
-      bp.tail = last ? TAIL_READOUT_WB : TAIL_AGG;
-      if (!last) {
-        bp.agg[0] = W.agg[i + 1][0];
-        bp.agg[1] = W.agg[i + 1][1];
-      }
-    }
-    bp.a = a;
   }
   col_stamp_select(st);
-  B_(K_FWD_COL);
+  if (prof) prof->begin(K_FWD_COL, st);
   k_fwd_col<16><<<cu_count(), 512, kColLds, st>>>(fp);
-  E_(K_FWD_COL);
+  if (prof) prof->end(K_FWD_COL, st);
   return hipGetLastError();
 }
 

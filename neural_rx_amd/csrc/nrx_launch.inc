@@ -54,6 +54,61 @@ static int cu_count() {
   return g_cu_count[dev];
 }
 
+// ---- the stage plan every forward launcher shares (Launch<P>::run, run_fused, launch_fwd_col)
+// A forward is a list of stages: StateInit m = 0 .. num_init - 1 into s_out (m > 0 accumulating), then
+// num_it updates on the ping-ponged state / aggregate planes.  The tail of a stage runs the NEXT
+// iteration's aggregation MLP (the last StateInit: iteration 0's) or, in the last update, the readout.
+// plan_stage fills what stage s's kernels read of it, in place: a, w, m, tail, agg and the heads.
+// ro_tail (TAIL_READOUT or TAIL_READOUT_WB) is the caller's choice, and so are the launch-wide fields
+// strips, gz, inline_combine, norm_pre, pair and order_rev.  What no kernel of the stage reads is
+// zero: agg of the readout stage, m of an update.
+template <class P>
+static void plan_stage(BlockParams<P>& bp, const FwdArgs<typename P::WT, typename P::BT, typename P::S>& args,
+                       const ModelW<typename P::WT, typename P::BT>& W, int num_it, int s, int ro_tail) {
+  const int i = s - args.num_init;   // the update's iteration; < 0: StateInit s
+  const bool last = i == num_it - 1;
+  bp.a = args;
+  if (i >= 0 && i % 2 == 0) {
+    std::swap(bp.a.s_in, bp.a.s_out);
+    std::swap(bp.a.a, bp.a.a_out);
+  }
+  for (int l = 0; l < 3; ++l) bp.w[l] = i < 0 ? W.init[s][l] : W.upd[i][l];
+  bp.m = i < 0 ? s : 0;
+  bp.tail = i < 0 ? (s == args.num_init - 1 ? TAIL_AGG : TAIL_NONE) : (last ? ro_tail : TAIL_AGG);
+  for (int k = 0; k < 2; ++k)
+    bp.agg[k] = last ? DenseW<typename P::WT, typename P::BT>{} : W.agg[i < 0 ? 0 : i + 1][k];
+  for (int h = 0; h < args.H; ++h) {
+    bp.llr[h][0] = W.llr[h][0];
+    bp.llr[h][1] = W.llr[h][1];
+  }
+  bp.chest[0] = W.chest[0];
+  bp.chest[1] = W.chest[1];
+}
+
+// The k_norm pre-pass: slots too long for the StateInit items to norm themselves (kNormFusedMaxQ) get
+// their norm from a launch of its own.  Returns BlockParams::norm_pre.
+template <class A>
+static bool norm_prepass(const A& args, hipStream_t st, Prof* prof) {
+  const int nq = args.F * kT * 2 * args.A / 4;
+  if (nq <= kNormFusedMaxQ) return false;
+  if (prof) prof->begin(K_NORM, st);
+  k_norm<<<args.B, 1024, 0, st>>>(args.y, nq, args.norm);
+  if (prof) prof->end(K_NORM, st);
+  return true;
+}
+
+#ifdef NRX_STAMPS
+// NRX_STAMP_LAUNCH = i stamps update i of the three-launch forward, -1 - m its StateInit m
+static void stamp_select(int launch, hipStream_t st) {
+  static const int sel = getenv("NRX_STAMP_LAUNCH") ? atoi(getenv("NRX_STAMP_LAUNCH")) : 0;
+  const int on = launch == sel;
+  (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_nrx_stamp_on), &on, sizeof(int), 0, hipMemcpyHostToDevice, st);
+  (void)hipStreamSynchronize(st);
+}
+#else
+static void stamp_select(int, hipStream_t) {}
+#endif
+
 template <class P>
 struct Launch {
   using A = FwdArgs<typename P::WT, typename P::BT, typename P::S>;
@@ -88,28 +143,18 @@ struct Launch {
     else k_init<P, A2P, TAIL_NONE><<<grid, 512, L, st>>>(bp);
   }
 
-  static hipError_t run(const A& args0, const MW& W, int num_it, hipStream_t st, Prof* prof, int update_rr = 0) {
-    A args = args0;
+  static hipError_t run(const A& args, const MW& W, int num_it, hipStream_t st, Prof* prof, int update_rr = 0) {
     const int strips = (args.F + P::FO - 1) / P::FO;
     constexpr int L = strip_lds_bytes<P>();
     const bool ch32 = 2 * args.A > 16;
     auto B_ = [&](int k) { if (prof) prof->begin(k, st); };
     auto E_ = [&](int k) { if (prof) prof->end(k, st); };
     BlockParams<P> bp{};
-    bp.a = args;
     bp.inline_combine = args.U <= kInlineUsers;
-    bp.pair = 0;
-    bp.gz = 0;
     if constexpr (std::is_same<P, P16>::value)   // 24-row strips, the workspace within GZ's offsets
       bp.gz = NRX_UPDATE_GZ != 0 && args.ws_bytes < kGzOob && args.pe16 != nullptr;
     bp.strips = strips;
-    const int nq = args.F * kT * 2 * args.A / 4;
-    bp.norm_pre = nq > kNormFusedMaxQ;
-    if (bp.norm_pre) {
-      B_(K_NORM);
-      k_norm<<<args.B, 1024, 0, st>>>(args.y, nq, args.norm);
-      E_(K_NORM);
-    }
+    bp.norm_pre = norm_prepass(args, st, prof);
     int launch_no = 0;
     // U > kInlineUsers: the leave-one-out combine runs as its own launch on the sp rows
     auto combine = [&](typename P::S* sp) {
@@ -119,69 +164,35 @@ struct Launch {
       k_combine<P><<<g, 256, 0, st>>>(sp, args.active, args.U, args.F);
       E_(K_COMBINE);
     };
-    for (int h = 0; h < args.H; ++h) {
-      bp.llr[h][0] = W.llr[h][0];
-      bp.llr[h][1] = W.llr[h][1];
-    }
-    bp.chest[0] = W.chest[0];
-    bp.chest[1] = W.chest[1];
-    // StateInit -> s_out; tail of the last StateInit launch: aggregation of iteration 0
     const dim3 grid(strips * args.U * args.B);
+    // StateInit, one launch per m (Var-IO), by the whole-column kernel (2A = 8: weights staged once per
+    // workgroup) where the schedule gives it the stage, else by the strip kernel
     bool col_init = false;
     if constexpr (std::is_same<P, P16>::value)
       col_init = (update_rr & kSchedColInit) && col_init_applicable(args);
-    if (col_init) {
-      // whole-column StateInit (2A = 8): weights staged once per workgroup; Var-IO: one launch per
-      // StateInit m, accumulating, the last one with iteration 0's aggregation tail
-      if constexpr (std::is_same<P, P16>::value) {
-        B_(K_INIT_COL);
-        for (int m = 0; m < args.num_init; ++m) {
-          for (int l = 0; l < 3; ++l) bp.w[l] = W.init[m][l];
-          bp.m = m;
-          bp.tail = m == args.num_init - 1 ? TAIL_AGG : TAIL_NONE;
-          bp.agg[0] = W.agg[0][0];
-          bp.agg[1] = W.agg[0][1];
-          bp.order_rev = launch_no++ & 1;
+    B_(col_init ? K_INIT_COL : K_INIT);
+    for (int m = 0; m < args.num_init; ++m) {
+      plan_stage(bp, args, W, num_it, m, TAIL_READOUT);
+      bp.order_rev = launch_no++ & 1;
+      if (col_init) {
+        if constexpr (std::is_same<P, P16>::value) {
           const hipError_t e = launch_init_col(bp, st);
           if (e != hipSuccess) return e;
         }
-        E_(K_INIT_COL);
+        continue;
       }
-    }
-    if (!col_init) B_(K_INIT);
-    for (int m = 0; m < (col_init ? 0 : args.num_init); ++m) {
-      for (int l = 0; l < 3; ++l) bp.w[l] = W.init[m][l];
-      bp.m = m;
-      bp.tail = m == args.num_init - 1 ? TAIL_AGG : TAIL_NONE;
-      bp.agg[0] = W.agg[0][0];
-      bp.agg[1] = W.agg[0][1];
+      stamp_select(-1 - m, st);
       const bool tl = bp.tail == TAIL_AGG;
-      bp.order_rev = launch_no++ & 1;
-#ifdef NRX_STAMPS
-      {
-        static const int sel = getenv("NRX_STAMP_LAUNCH") ? atoi(getenv("NRX_STAMP_LAUNCH")) : 0;
-        const int on = sel == -1 - m;
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_nrx_stamp_on), &on, sizeof(int), 0, hipMemcpyHostToDevice, st);
-        (void)hipStreamSynchronize(st);
-      }
-#endif
-      // antenna block padding A2P (must match nrx_api.cpp init_a2p)
-      if (2 * args.A <= 8) launch_init<8>(grid, L, st, bp, tl);
-      else if (2 * args.A <= 16) launch_init<16>(grid, L, st, bp, tl);
+      const int a2p = init_a2p(args.A);
+      if (a2p == 8) launch_init<8>(grid, L, st, bp, tl);
+      else if (a2p == 16) launch_init<16>(grid, L, st, bp, tl);
       else launch_init<32>(grid, L, st, bp, tl);
     }
-    if (!col_init) E_(K_INIT);
+    E_(col_init ? K_INIT_COL : K_INIT);
     combine(bp.a.a_out);
     for (int i = 0; i < num_it; ++i) {
-      std::swap(bp.a.s_in, bp.a.s_out);
-      std::swap(bp.a.a, bp.a.a_out);
-      for (int l = 0; l < 3; ++l) bp.w[l] = W.upd[i][l];
       const bool last = i == num_it - 1;
-      bp.tail = last ? TAIL_READOUT : TAIL_AGG;
-      if (!last) {
-        bp.agg[0] = W.agg[i + 1][0];
-        bp.agg[1] = W.agg[i + 1][1];
-      }
+      plan_stage(bp, args, W, num_it, args.num_init + i, TAIL_READOUT);
       bp.order_rev = launch_no++ & 1;
       bool rr = false, col = false;
       if constexpr (std::is_same<P, P16>::value) {
@@ -191,14 +202,7 @@ struct Launch {
       }
       const int kid = col ? K_UPDATE_COL : rr ? K_UPDATE_RR : K_UPDATE;
       B_(kid);
-#ifdef NRX_STAMPS
-      {
-        static const int sel = getenv("NRX_STAMP_LAUNCH") ? atoi(getenv("NRX_STAMP_LAUNCH")) : 0;
-        const int on = i == sel;
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_nrx_stamp_on), &on, sizeof(int), 0, hipMemcpyHostToDevice, st);
-        (void)hipStreamSynchronize(st);
-      }
-#endif
+      stamp_select(i, st);
       if (col) {
         // whole-column update stage: 48-position items, weights staged once per workgroup
         if constexpr (std::is_same<P, P16>::value) {
@@ -356,51 +360,13 @@ static hipError_t run_fused(const FwdArgs<_Float16, float, _Float16>& args, cons
   fp.nq = xcc_count();
   fp.spin_limit = fc.spin_limit;
   fp.dbg_err = fc.dbg_err;
-  const int nq = args.F * kT * 2 * args.A / 4;
-  const bool norm_pre = nq > kNormFusedMaxQ;
-  auto B_ = [&](int k) { if (prof) prof->begin(k, st); };
-  auto E_ = [&](int k) { if (prof) prof->end(k, st); };
-  if (norm_pre) {
-    B_(K_NORM);
-    k_norm<<<args.B, 1024, 0, st>>>(args.y, nq, args.norm);
-    E_(K_NORM);
-  }
-  FwdArgs<_Float16, float, _Float16> a = args;
+  const bool norm_pre = norm_prepass(args, st, prof);
   for (int s = 0; s < fp.nst; ++s) {
-    BlockParams<P>& bp = fp.st[s];
+    BlockParams<P>& bp = fp.st[s];   // in place: FusedParams is several KB (pair, order_rev, gz stay 0)
+    plan_stage(bp, args, W, num_it, s, fp.heads_x ? TAIL_READOUT : TAIL_READOUT_WB);
     bp.inline_combine = comb ? 0 : 1;   // U > 2: the combine stages write a_u in place
-    bp.pair = 0;
-    bp.order_rev = 0;
     bp.norm_pre = norm_pre;
     bp.strips = (args.F + P::FO - 1) / P::FO;
-    bp.m = 0;
-    for (int h = 0; h < args.H; ++h) {
-      bp.llr[h][0] = W.llr[h][0];
-      bp.llr[h][1] = W.llr[h][1];
-    }
-    bp.chest[0] = W.chest[0];
-    bp.chest[1] = W.chest[1];
-    if (s < fp.ninit) {
-      // StateInit m = s into s_out (m > 0 accumulating); the last one runs iteration 0's
-      // aggregation MLP
-      for (int l = 0; l < 3; ++l) bp.w[l] = W.init[s][l];
-      bp.m = s;
-      bp.tail = s == fp.ninit - 1 ? TAIL_AGG : TAIL_NONE;
-      bp.agg[0] = W.agg[0][0];
-      bp.agg[1] = W.agg[0][1];
-    } else {
-      std::swap(a.s_in, a.s_out);
-      std::swap(a.a, a.a_out);
-      const int i = s - fp.ninit;
-      for (int l = 0; l < 3; ++l) bp.w[l] = W.upd[i][l];
-      const bool last = i == num_it - 1;
-      bp.tail = last ? (fp.heads_x ? TAIL_READOUT : TAIL_READOUT_WB) : TAIL_AGG;
-      if (!last) {
-        bp.agg[0] = W.agg[i + 1][0];
-        bp.agg[1] = W.agg[i + 1][1];
-      }
-    }
-    bp.a = a;
   }
 #ifdef NRX_STAMPS
   {
@@ -409,17 +375,16 @@ static hipError_t run_fused(const FwdArgs<_Float16, float, _Float16>& args, cons
     (void)hipStreamSynchronize(st);
   }
 #endif
-  B_(K_FUSED);
-  const int a2p = 2 * args.A > 16 ? 32 : (2 * args.A <= 8 ? 8 : 16);
+  if (prof) prof->begin(K_FUSED, st);
+  const int a2p = init_a2p(args.A);
   const int mode0 = fused_mode<P>(args);
   const int mode = a2p == 32 && mode0 == 0 ? 1 : mode0;   // 2A = 32 has the general kernels only
   hipError_t e = mode == 0 ? launch_kforward_m0(a2p, fp, cus, st)
                  : mode == 1 ? launch_kforward_m1(a2p, fp, cus, st)
                              : launch_kforward_m2(a2p, fp, cus, st);
   if (e != hipSuccess) return e;
-  E_(K_FUSED);
+  if (prof) prof->end(K_FUSED, st);
   return hipGetLastError();
 }
-
 
 }  // namespace nrx

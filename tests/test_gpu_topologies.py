@@ -1,6 +1,6 @@
 """The CGNN engine over the topology range nrx_create accepts (needs an MI355X).
 
-check_desc / check_shape (nrx_api.cpp) accept 1..16 rx antennas, 1..8 bits per head, up to 8 MCS
+check_desc (nrx_model.cpp) / check_shape (nrx_api.cpp) accept 1..16 rx antennas, 1..8 bits per head, up to 8 MCS
 with masking (3 heads without), models with and without h_hat and 1..16 users; the rest of the
 GPU suite runs 4 and 16 antennas, 4 / 6 bits, h_hat always, one-hot MCS masks and U in {1, 2, 3,
 4, 8}.  The six seeded topologies below reach what that leaves out:
