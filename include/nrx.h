@@ -295,6 +295,96 @@ typedef struct nrx_gen_chan {
 int nrx_generate_slots_ex(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_out* out,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- carrier frequency offset
+ * A per-user carrier frequency offset (CFO) at the transmitter: the reference's cfo_offset_ppm(_eval)
+ * (utils/impairments.py:18-110, applied at utils/e2e_model.py:320-321), a uniform draw in +-max per
+ * (slot, user).  With scs = subcarrier_spacing, kappa = 1.07 the generator's symbol-time factor, N the
+ * FFT size and eps[b][u] the offset in subcarrier spacings:
+ *   eps[b][u] = cfo_hz[u] / scs                           (constant)
+ *             = (cfo_hz[u] / scs) (2 uni(w) - 1)           (otherwise; w = word 0 of the Philox draw
+ *               (slot, stream 6, element u): a stream of its own, so no other draw moves)
+ *   x'[b,u,k,t] = e^{j theta_t} sum_{m < F} c[m - k] x[b,u,m,t]
+ *   c[d]    = D_N(d + eps),  D_N(v) = e^{j pi (N - 1) v / N} sin(pi v) / (N sin(pi v / N)),
+ *             D_N(v) = 1 where v / N is an integer
+ *   theta_t = 2 pi eps (kappa t + (kappa - 1))
+ * which is OFDM modulation with a cyclic prefix of (kappa - 1) N samples, a rotation of sample n by
+ * e^{j 2 pi (eps / N) n}, and demodulation; leakage outside the F allocated subcarriers is dropped.
+ * With N = F the map is circulant and unitary.  The channel acts on x' (y, h_hat and the Aerial
+ * outputs follow from it); the LS step still divides by the clean pilot.  All of it in f64.
+ *   - h_with_phase = 0: h stays the channel alone, the reference's perfect CSI.
+ *     h_with_phase = 1: h is the diagonal of the effective channel, h e^{j theta_t} D_N(eps) --
+ *     what a perfect-CSI receiver and a channel NMSE should be scored against (the f32 h is
+ *     multiplied in f64 and rounded once more).
+ *   - eps_out (optional, device [B][U] f64, 8-byte aligned) receives eps of every (slot, user),
+ *     active or not.
+ * cfo == NULL, or every cfo_hz[u] with u < U equal to 0, launches nothing new, needs the workspace
+ * of nrx_gen_workspace_size and gives outputs bit-identical to nrx_generate_slots_ex (eps_out is
+ * then not written).  Otherwise the workspace grows by the x' buffer [B][U][F][14] complex f64
+ * (nrx_gen_workspace_size_cfo).  Slot slot_offset + b stays a pure function of the global slot
+ * index; no atomics, the same bits on every call.
+ * A negative or non-finite cfo_hz[u] with u < U, constant or h_with_phase outside {0, 1}, or an
+ * eps_out that is not 8-byte aligned is NRX_ERR_INVALID_ARG; fft_size non-zero and outside F..8192
+ * is NRX_ERR_SHAPE; entries of ports >= U are not read; the other checks are those of
+ * nrx_generate_slots_ex, all made before the first HIP call. */
+typedef struct nrx_gen_cfo {
+  double cfo_hz[16];           /* per port, finite and >= 0: the offset (constant) or its maximum */
+  int32_t constant;            /* 0: drawn per (slot, user) in +-cfo_hz[u]; 1: exactly cfo_hz[u] */
+  int32_t fft_size;            /* N; 0 = F (the PUSCH grid without guard carriers), else F..8192 */
+  int32_t h_with_phase;        /* 0 / 1 */
+  int32_t pad_;
+  double* eps_out;             /* device [B][U], or NULL */
+} nrx_gen_cfo;
+
+int nrx_gen_workspace_size_cfo(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, size_t* bytes);
+int nrx_generate_slots_cfo(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                           const nrx_gen_out* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* DMRS-based CFO estimate and compensation on the receiver side.  Both are asynchronous on `stream`,
+ * use no atomics and no workspace, and give the same bits on every call and for every batch split.
+ *
+ * nrx_cfo_estimate: eps[b][u] (f64) from h_in = h_hat, read at the own pilots only (subcarriers f
+ * with f mod 2 = cdm_group[u] on the DMRS symbols, as the channel estimators do).  With g the smallest
+ * gap between consecutive DMRS symbols and the sum over the consecutive pairs (D, D + g) with that
+ * gap, the antennas a and the own pilots p,
+ *   r = sum h_hat[p, D + g, a] conj(h_hat[p, D, a]),   eps = arg(r) / (2 pi kappa g),
+ * reduced in f64 in a fixed order, one workgroup per (slot, user); eps = 0 with fewer than two DMRS
+ * symbols, r = 0 or an inactive user (active <= 0).  Unambiguous for |eps| < 1 / (2 kappa g): 0.0519,
+ * 1.56 kHz, for symbols (2, 11) at 30 kHz.  A per-tap Doppler shift common to a user's taps looks
+ * like a CFO to this estimator, and it is meant to: both turn the channel between the DMRS symbols,
+ * and compensating the common rotation helps either way.  h_out, ref_mode and sign are not read.
+ *
+ * nrx_cfo_rotate: h_out[b,u,f,t,.] = h_in[b,u,f,t,.] e^{j sign 2 pi kappa eps[b][u] (t - t_ref)},
+ * f64 arithmetic rounded once to f32; h_out == h_in is allowed.  ref_mode
+ *   NRX_CFO_REF_NEAREST_DMRS  t_ref = the first listed DMRS symbol nearest t (the generator's
+ *                             nearest-pilot rule): with sign = +1 it compensates the nearest-neighbour
+ *                             h_hat that the CGNN and the LS-NN baselines consume;
+ *   NRX_CFO_REF_ZERO          t_ref = 0: sign = -1 de-rotates the pilots before nrx_chest_lin /
+ *                             nrx_chest_lmmse / nrx_chest_lmmse3, sign = +1 re-rotates their output.
+ * active and cdm_group are not read.
+ *
+ * A NULL io / h_in / eps (estimate: or active; rotate: or h_out), an eps that is not 8-byte aligned,
+ * a DMRS symbol outside 0..13 or not ascending, a cdm_group outside {0, 1}, and for the rotation a
+ * ref_mode outside the two above or a sign other than +-1 is NRX_ERR_INVALID_ARG; the shape limits
+ * and codes are those of nrx_chest_io.  Every argument is checked before the first HIP call. */
+#define NRX_CFO_REF_NEAREST_DMRS 0
+#define NRX_CFO_REF_ZERO 1
+typedef struct nrx_cfo_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B, U (1..16), F (1..3300), T = 14 */
+  int32_t num_rx_ant;          /* A, 1..16 */
+  int32_t num_dmrs_symbols;    /* nd, 1..4 */
+  int32_t dmrs_symbols[4];     /* ascending */
+  int32_t cdm_group[16];       /* per port, 0/1 */
+  int32_t ref_mode;            /* nrx_cfo_rotate: NRX_CFO_REF_* */
+  int32_t sign;                /* nrx_cfo_rotate: +1 / -1 */
+  const float* h_in;           /* [B][U][F][T][2A] */
+  const float* active;         /* [B][U] (nrx_cfo_estimate) */
+  double*      eps;            /* [B][U]: written by nrx_cfo_estimate, read by nrx_cfo_rotate */
+  float*       h_out;          /* [B][U][F][T][2A] (nrx_cfo_rotate) */
+} nrx_cfo_io;
+
+int nrx_cfo_estimate(const nrx_cfo_io* io, void* stream);
+int nrx_cfo_rotate(const nrx_cfo_io* io, void* stream);
+
 /* Uncoded error counters of one batch (sim_ber's counting, scripts/evaluate.py:193-202,
  * with the active-port masking of E2E_Model._mask_active_dmrs, e2e_model.py:195-209):
  * counts[u][0..3] += (bit errors, bits, block errors, blocks) over the active (slot, user)

@@ -36,8 +36,11 @@ EXPORTS = [
     "nrx_generate_slots_ex", "nrx_cov_space_workspace_size", "nrx_cov_space_accumulate",
     "nrx_chest3_workspace_size", "nrx_chest_lmmse3", "nrx_aerial_preprocess",
     "nrx_ldpc_create", "nrx_ldpc_destroy", "nrx_ldpc_workspace_size", "nrx_ldpc_decode", "nrx_ldpc_gather",
-    "nrx_ldpc_count",
+    "nrx_ldpc_count", "nrx_gen_workspace_size_cfo", "nrx_generate_slots_cfo", "nrx_cfo_estimate", "nrx_cfo_rotate",
 ]
+# nrx_cfo_io.ref_mode (NRX_CFO_REF_*)
+CFO_REF_NEAREST_DMRS = 0
+CFO_REF_ZERO = 1
 # enum nrx_y_layout
 Y_LAYOUTS = {"cgnn": 0, "sionna": 1, "split": 2}
 KERNELS = ["norm", "state_init", "state_update", "forward", "state_update_rr", "combine", "state_update_col",
@@ -163,6 +166,36 @@ class nrx_gen_chan(ctypes.Structure):
         ("max_delay_s", ctypes.c_double * 16),
         ("max_doppler_hz", ctypes.c_double * 16),
         ("rx_mix", ctypes.c_void_p),
+    ]
+
+
+class nrx_gen_cfo(ctypes.Structure):
+    _fields_ = [
+        ("cfo_hz", ctypes.c_double * 16),
+        ("constant", ctypes.c_int32),
+        ("fft_size", ctypes.c_int32),
+        ("h_with_phase", ctypes.c_int32),
+        ("pad_", ctypes.c_int32),
+        ("eps_out", ctypes.c_void_p),
+    ]
+
+
+class nrx_cfo_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_rx_ant", ctypes.c_int32),
+        ("num_dmrs_symbols", ctypes.c_int32),
+        ("dmrs_symbols", ctypes.c_int32 * 4),
+        ("cdm_group", ctypes.c_int32 * 16),
+        ("ref_mode", ctypes.c_int32),
+        ("sign", ctypes.c_int32),
+        ("h_in", ctypes.c_void_p),
+        ("active", ctypes.c_void_p),
+        ("eps", ctypes.c_void_p),
+        ("h_out", ctypes.c_void_p),
     ]
 
 
@@ -486,6 +519,15 @@ def load(path: str = LIB_PATH):
     lib.nrx_generate_slots_ex.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_out), c.c_void_p, c.c_size_t,
                                           c.c_void_p]
     lib.nrx_generate_slots_ex.restype = c.c_int
+    lib.nrx_gen_workspace_size_cfo.argtypes = [P(nrx_gen_desc), P(nrx_gen_cfo), P(c.c_size_t)]
+    lib.nrx_gen_workspace_size_cfo.restype = c.c_int
+    lib.nrx_generate_slots_cfo.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo), P(nrx_gen_out), c.c_void_p,
+                                           c.c_size_t, c.c_void_p]
+    lib.nrx_generate_slots_cfo.restype = c.c_int
+    lib.nrx_cfo_estimate.argtypes = [P(nrx_cfo_io), c.c_void_p]
+    lib.nrx_cfo_estimate.restype = c.c_int
+    lib.nrx_cfo_rotate.argtypes = [P(nrx_cfo_io), c.c_void_p]
+    lib.nrx_cfo_rotate.restype = c.c_int
     lib.nrx_cov_space_workspace_size.argtypes = [P(nrx_cov_space_io), P(c.c_size_t)]
     lib.nrx_cov_space_workspace_size.restype = c.c_int
     lib.nrx_cov_space_accumulate.argtypes = [P(nrx_cov_space_io), c.c_void_p, c.c_size_t, c.c_void_p]

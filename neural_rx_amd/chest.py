@@ -327,15 +327,18 @@ class ChannelEstimator:
     ``set_covariance``) and designs its filter whenever ``no`` changes (``self.design``);
     ``"lmmse3"`` needs ``R_s`` as well and designs once per covariance.  ``tables=`` pins given
     ``LMMSEDesign`` / ``LMMSE3Design`` tables instead.  Every element of the output is written;
-    inactive users are 0."""
+    inactive users are 0.  ``cfo`` (a ``cfo.CFOCompensator``, here or per call): every call
+    estimates the carrier frequency offset, de-rotates the pilots, estimates, and re-rotates the
+    output (``CFOCompensator.wrap``)."""
 
     def __init__(self, kind: str, params: GenParams, device: int = 0, R_f=None, R_t=None,
-                 tables=None, R_s=None):
+                 tables=None, R_s=None, cfo=None):
         if kind not in KINDS:
             raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
         self.kind = kind
         self.p = params
         self.device = device
+        self.cfo = cfo
         self._lib = _lib.load()
         self.R_f, self.R_t, self.R_s = R_f, R_t, R_s
         self.design = None
@@ -384,10 +387,14 @@ class ChannelEstimator:
             self._set_design(lmmse_design(self.R_f, self.R_t, self.p, no))
         return self.design
 
-    def __call__(self, sb: SlotBatch, no: float, out=None, stream=None, workspace=None):
+    def __call__(self, sb: SlotBatch, no: float, out=None, stream=None, workspace=None, cfo=None):
         """``workspace`` (lmmse3 only, the one estimator with a workspace): a uint8 device tensor
         of at least ``nrx_chest3_workspace_size`` bytes (``last_workspace_bytes`` after a call),
-        any content, instead of the estimator's own."""
+        any content, instead of the estimator's own.  ``cfo``: a ``cfo.CFOCompensator`` for this
+        call, None for the estimator's own (``self.cfo``), False for none."""
+        cfo = self.cfo if cfo is None else cfo
+        if cfo:
+            return cfo.wrap(self)(sb, no, out=out, stream=stream, workspace=workspace)
         torch = _torch()
         p = self.p
         hh = sb.h_hat
@@ -481,7 +488,7 @@ class EstimatorBaselineReceiver:
     perfect_csi = False
     SYSTEMS = SYSTEMS
 
-    def __init__(self, system: str, params: GenParams, device: int = 0, R_f=None, R_t=None, R_s=None):
+    def __init__(self, system: str, params: GenParams, device: int = 0, R_f=None, R_t=None, R_s=None, cfo=None):
         if system not in SYSTEMS:
             raise ValueError(f"system must be one of {SYSTEMS}, got {system!r}")
         if params.num_tx > MAX_TX:
@@ -489,6 +496,7 @@ class EstimatorBaselineReceiver:
         self.system = system
         self.p = params
         self._device = device
+        self.cfo = cfo          # a cfo.CFOCompensator the estimator runs through, or None
         self.detector = LMMSEDetector(device)
         self._out = None
         self.last_h = None      # the estimate the last call detected with
@@ -500,7 +508,7 @@ class EstimatorBaselineReceiver:
         """``R_s=None`` keeps the 2-D filter; a matrix selects the 3-D one (``baseline_lmmse_lmmse`` only)"""
         kind = "lin" if self.system != "baseline_lmmse_lmmse" else "lmmse" if R_s is None else "lmmse3"
         if self.estimator is None or self.estimator.kind != kind:
-            self.estimator = ChannelEstimator(kind, self.p, self._device)
+            self.estimator = ChannelEstimator(kind, self.p, self._device, cfo=self.cfo)
         if kind == "lmmse3":
             self.estimator.set_covariance(R_f, R_t, R_s)
         else:

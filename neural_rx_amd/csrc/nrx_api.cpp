@@ -681,8 +681,43 @@ int nrx_generate_slots(const nrx_gen_desc* desc, const nrx_gen_out* out, void* w
   return nrx_generate_slots_ex(desc, nullptr, out, workspace, workspace_bytes, stream);
 }
 
+// the carrier frequency offset of a generator call: *g resolved for the kernels, *on whether any
+// port < U has a non-zero offset (none: the call is nrx_generate_slots_ex)
+static int check_gen_cfo(const nrx_gen_desc* d, const nrx_gen_cfo* cfo, GenCfo* g, bool* on) {
+  *on = false;
+  if (!cfo) return NRX_OK;
+  for (int u = 0; u < d->num_tx; ++u) {
+    if (int rc = check_nonneg("per-port carrier frequency offset", cfo->cfo_hz[u])) return rc;
+    g->eps_max[u] = cfo->cfo_hz[u] / d->subcarrier_spacing;
+    *on = *on || cfo->cfo_hz[u] > 0.0;
+  }
+  if (int rc = check_range("cfo constant", cfo->constant, 0, 1, NRX_ERR_INVALID_ARG)) return rc;
+  if (int rc = check_range("h_with_phase", cfo->h_with_phase, 0, 1, NRX_ERR_INVALID_ARG)) return rc;
+  if ((uintptr_t)cfo->eps_out & 7) return fail(NRX_ERR_INVALID_ARG, "eps_out must be 8-byte aligned");
+  if (cfo->fft_size)
+    if (int rc = check_range("fft_size", cfo->fft_size, d->num_subcarriers, 8192)) return rc;
+  g->constant = cfo->constant;
+  g->fft_size = cfo->fft_size ? cfo->fft_size : d->num_subcarriers;
+  g->h_with_phase = cfo->h_with_phase;
+  g->eps_out = cfo->eps_out;
+  return NRX_OK;
+}
+
+int nrx_gen_workspace_size_cfo(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, size_t* bytes) {
+  if (int rc = check_gen(desc)) return rc;
+  GenCfo g{};
+  bool on;
+  if (int rc = check_gen_cfo(desc, cfo, &g, &on)) return rc;
+  return store_size(bytes, gen_workspace_bytes(*desc, nullptr, nullptr) + (on ? cfo_workspace_bytes(*desc) : 0));
+}
+
 int nrx_generate_slots_ex(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_out* out, void* workspace,
                           size_t workspace_bytes, void* stream) {
+  return nrx_generate_slots_cfo(desc, chan, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+int nrx_generate_slots_cfo(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                           const nrx_gen_out* out, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_gen(desc)) return rc;
   nrx_gen_chan c{};                          // NULL chan: every port has the desc's scalars, no mixing
   for (int u = 0; u < desc->num_tx; ++u) {
@@ -694,6 +729,9 @@ int nrx_generate_slots_ex(const nrx_gen_desc* desc, const nrx_gen_chan* chan, co
   }
   if (chan && ((uintptr_t)chan->rx_mix & 7)) return fail(NRX_ERR_INVALID_ARG, "rx_mix must be 8-byte aligned");
   c.rx_mix = chan ? chan->rx_mix : nullptr;
+  GenCfo g{};
+  bool cfo_on;
+  if (int rc = check_gen_cfo(desc, cfo, &g, &cfo_on)) return rc;
   if (!out || !out->y) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (out->bits)
     if (int rc = check_bits_stride(out->bits_stride, desc->mcs_bits, desc->num_mcs)) return rc;
@@ -701,8 +739,10 @@ int nrx_generate_slots_ex(const nrx_gen_desc* desc, const nrx_gen_chan* chan, co
     return fail(NRX_ERR_INVALID_ARG, "Aerial outputs come in (real, imag) pairs");
   if (out->h_ls_real && desc->num_subcarriers % 12)
     return fail(NRX_ERR_SHAPE, "Aerial pilot list needs num_subcarriers % 12 == 0");
-  if (int rc = check_workspace(workspace, workspace_bytes, gen_workspace_bytes(*desc, nullptr, nullptr), 1)) return rc;
-  return launched(launch_generate(*desc, c, *out, workspace, (hipStream_t)stream), "slot generator launch");
+  const size_t need = gen_workspace_bytes(*desc, nullptr, nullptr) + (cfo_on ? cfo_workspace_bytes(*desc) : 0);
+  if (int rc = check_workspace(workspace, workspace_bytes, need, 1)) return rc;
+  return launched(launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr),
+                  "slot generator launch");
 }
 
 // llr / bits of any slot count, with up to 31 symbols (the mask's bits): not the 14-symbol grid
@@ -813,6 +853,29 @@ int nrx_chest_lmmse(const nrx_chest_io* io, void* stream) {
 int nrx_chest_lin(const nrx_chest_io* io, void* stream) {
   if (int rc = check_chest(io, false)) return rc;
   return launched(launch_chest_lin(*io, (hipStream_t)stream), "linear channel estimator launch");
+}
+
+static int check_cfo_io(const nrx_cfo_io* io, bool rotate) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->h_in || !io->eps || !(rotate ? (const void*)io->h_out : (const void*)io->active))
+    return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if ((uintptr_t)io->eps & 7) return fail(NRX_ERR_INVALID_ARG, "eps must be 8-byte aligned");
+  if (rotate) {
+    if (int rc = check_range("ref_mode", io->ref_mode, NRX_CFO_REF_NEAREST_DMRS, NRX_CFO_REF_ZERO, NRX_ERR_INVALID_ARG))
+      return rc;
+    if (io->sign != 1 && io->sign != -1) return fail(NRX_ERR_INVALID_ARG, "sign must be +1 or -1");
+  }
+  return check_chest_shape(io);
+}
+
+int nrx_cfo_estimate(const nrx_cfo_io* io, void* stream) {
+  if (int rc = check_cfo_io(io, false)) return rc;
+  return launched(launch_cfo_estimate(*io, (hipStream_t)stream), "cfo estimator launch");
+}
+
+int nrx_cfo_rotate(const nrx_cfo_io* io, void* stream) {
+  if (int rc = check_cfo_io(io, true)) return rc;
+  return launched(launch_cfo_rotate(*io, (hipStream_t)stream), "cfo rotation launch");
 }
 
 static int check_chest3(const nrx_chest3_io* io, bool tables) {

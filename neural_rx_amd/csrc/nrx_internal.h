@@ -170,9 +170,28 @@ hipError_t launch_aerial_llr(const float* llr, int B, int U, int F, int T, int b
 // gen_workspace_bytes(d, nullptr, nullptr) = workspace size.
 struct GenWs;
 size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base);
+// cfo (optional, nrx_generate_slots_cfo with a non-zero offset): the workspace holds the x' buffer
+// (cfo_workspace_bytes) behind the generator's own
+struct GenCfo;
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
-                           hipStream_t st);
+                           hipStream_t st, const GenCfo* cfo = nullptr);
 hipError_t launch_count_errors(const nrx_count_io& c, hipStream_t st);
+
+// Carrier frequency offset (nrx_cfo.hip); validated by nrx_generate_slots_cfo / nrx_cfo_estimate /
+// nrx_cfo_rotate.  x, xp: [B][U][F][14] complex f64 (re, im)
+struct GenCfo {
+  double eps_max[16];                // cfo_hz[u] / subcarrier_spacing
+  int constant;
+  int fft_size;                      // N, resolved (never 0)
+  int h_with_phase;
+  double* eps_out;
+};
+size_t cfo_workspace_bytes(const nrx_gen_desc& d);
+hipError_t launch_cfo_apply(const nrx_gen_desc& d, const GenCfo& c, const double* x, const float* active, double* xp,
+                            hipStream_t st);
+hipError_t launch_cfo_h_phase(const nrx_gen_desc& d, const GenCfo& c, float* h, hipStream_t st);
+hipError_t launch_cfo_estimate(const nrx_cfo_io& io, hipStream_t st);
+hipError_t launch_cfo_rotate(const nrx_cfo_io& io, hipStream_t st);
 
 // LMMSE + max-log baseline detector (nrx_lmmse.hip); io validated by nrx_lmmse_detect
 hipError_t launch_lmmse(const nrx_lmmse_io& io, hipStream_t st);

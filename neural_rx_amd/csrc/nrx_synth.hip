@@ -28,6 +28,7 @@
 
 #include "../../include/nrx.h"
 #include "nrx_internal.h"
+#include "nrx_rng.h"
 
 namespace nrx {
 
@@ -42,42 +43,7 @@ struct GenWs {
 
 namespace {
 
-enum { ST_RE = 0, ST_ACTIVE = 1, ST_MCS = 2, ST_DELAY = 3, ST_TAP = 4, ST_NOISE = 5 };
-
-constexpr double kPi = 3.14159265358979323846;
-constexpr double kCP = 1.07;      // symbol time = 1.07 / scs (normal cyclic prefix)
 constexpr double kPDP = 3.0;      // PDP decay constant = max_delay / 3
-
-struct U4 {
-  uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                     uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-    const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0;
-    c1 = lo1;
-    c2 = n2;
-    c3 = lo0;
-  }
-  return {c0, c1, c2, c3};
-}
-
-__device__ __forceinline__ U4 draw(const nrx_gen_desc& d, int64_t b, int stream, uint32_t idx) {
-  const uint64_t g = (uint64_t)(d.slot_offset + b);
-  return philox(idx, (uint32_t)g, (uint32_t)(g >> 32), (uint32_t)stream, (uint32_t)d.seed,
-                (uint32_t)(d.seed >> 32));
-}
-
-__device__ __forceinline__ double uni(uint32_t w) { return ((double)w + 0.5) * 0x1p-32; }
 
 __device__ __forceinline__ double2 box_muller(uint32_t w0, uint32_t w1) {
   const double r = sqrt(-2.0 * log(uni(w0)));
@@ -578,9 +544,9 @@ size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base) {
 }
 
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
-                           hipStream_t st) {
+                           hipStream_t st, const GenCfo* cfo) {
   GenWs w;
-  gen_workspace_bytes(d, &w, (char*)ws);
+  const size_t own = gen_workspace_bytes(d, &w, (char*)ws);
   const int64_t B = d.batch, U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols, A = d.num_rx_ant,
                 L = d.num_taps;
   auto blocks = [](int64_t n) { return (unsigned)((n + 255) / 256); };
@@ -591,8 +557,19 @@ hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const n
   const int at = (int)(A * T);
   int FB = 256 / at;
   if (FB > 4) FB = 4;
-  k_gen_rx<<<dim3((unsigned)((F + FB - 1) / FB), (unsigned)B), FB * at, 0, st>>>(d, w, FB, o.y, o.h, o.y_real,
-                                                                                o.y_imag);
+  // with a carrier frequency offset the channel acts on x' = (CFO) x, which lies behind the
+  // generator's own workspace; the clean x stays for the LS division by the known pilots
+  GenWs wr = w;
+  if (cfo) {
+    wr.x = reinterpret_cast<double2*>((char*)ws + own);
+    if (hipError_t e = launch_cfo_apply(d, *cfo, reinterpret_cast<const double*>(w.x), w.active,
+                                        reinterpret_cast<double*>(wr.x), st))
+      return e;
+  }
+  k_gen_rx<<<dim3((unsigned)((F + FB - 1) / FB), (unsigned)B), FB * at, 0, st>>>(d, wr, FB, o.y, o.h, o.y_real,
+                                                                                 o.y_imag);
+  if (cfo && cfo->h_with_phase && o.h)
+    if (hipError_t e = launch_cfo_h_phase(d, *cfo, o.h, st)) return e;
   if (o.h_hat) k_gen_ls<<<blocks(B * U * F * T * A), 256, 0, st>>>(d, w, o.y, o.h_hat);
   if (o.h_ls_real)
     k_gen_ls_aerial<<<blocks(B * d.num_dmrs_symbols * (F / 12) * 6 * U * A), 256, 0, st>>>(d, w, o.y, o.h_ls_real,

@@ -19,6 +19,12 @@ point without errors; ``target_bler`` ends it once the BLER falls below the targ
 
     python -m neural_rx_amd.evaluate -config_name nrx_rt -num_tx_eval 2 \
         -ebno_db 0 2 4 6 8 -batch_size 128 -max_mc_iter 50
+
+``-cfo_hz`` / ``-cfo_ppm`` add a per-user carrier frequency offset at the transmitter (the reference's
+``cfo_offset_ppm_eval``); ``-cfo_comp`` runs every system behind the DMRS-based compensation of
+``cfo.py``.  One stated departure: under a CFO the generator runs with ``h_with_phase``, so the
+perfect-CSI systems and the NMSE see the diagonal of the effective channel; the reference hands its
+perfect-CSI baselines the un-rotated channel, with which they collapse.
 """
 from __future__ import annotations
 
@@ -35,6 +41,7 @@ from .config import dmrs_symbols, get_config
 from .generator import SCENARIOS, GenParams, SlotGenerator, count_errors, ebno_to_no, rx_correlation, scenario
 from .baseline import BaselineReceiver
 from .chest import COV_SLOT_OFFSET, EstimatorBaselineReceiver, estimate_covariance
+from .cfo import CFOCompensator
 from .kbest import KBestBaselineReceiver
 from .receiver import CGNNEngine, compute_pe, spec_for
 
@@ -164,6 +171,44 @@ def _mc_loop(step, check, gen: SlotGenerator, ebno_dbs: Sequence[float], batch_s
     return res
 
 
+class CfoStats:
+    """Per noise level, the squared error of the DMRS-based CFO estimate against the generator's
+    ``cfo_eps`` over the active (slot, user) pairs of this rank, accumulated on the device."""
+
+    def __init__(self, comp: CFOCompensator):
+        self.comp = comp
+        self.acc = {}
+
+    def add(self, sb, no: float) -> None:
+        import torch
+        err = (self.comp.estimate(sb) - sb.cfo_eps) * (sb.active > 0)
+        v = torch.stack([(err * err).sum(), (sb.active > 0).sum().to(torch.float64)])
+        self.acc[no] = self.acc[no] + v if no in self.acc else v
+
+    def rms(self, no: float) -> Optional[float]:
+        if no not in self.acc:
+            return None
+        s, n = self.acc[no].tolist()
+        return float(np.sqrt(s / n)) if n else None
+
+
+class CompensatedReceiver:
+    """A baseline that reads ``sb.h_hat`` (``baseline.BaselineReceiver``) behind
+    ``CFOCompensator.apply_nn``; the perfect-CSI systems pass through."""
+
+    def __init__(self, receiver, comp: CFOCompensator):
+        self.receiver, self.comp = receiver, comp
+        self.perfect_csi = receiver.perfect_csi
+
+    contaminated = property(lambda self: self.receiver.contaminated)
+    last_h = property(lambda self: self.receiver.last_h)
+
+    def __call__(self, sb, no, out=None, stream=None):
+        if not self.perfect_csi:
+            sb = self.comp.apply_nn(sb, stream=stream)
+        return self.receiver(sb, no, out=out, stream=stream)
+
+
 def soft_line(sr) -> str:
     """``BMI .. GMI .. (x scale) NMSE ..`` of a ``SoftResult``, one BMI / GMI per MCS"""
     f = lambda v: "-" if v is None or v != v else f"{v:.4f}"  # noqa: E731
@@ -200,8 +245,10 @@ def sim_ber(engine: CGNNEngine, gen: SlotGenerator, ebno_dbs: Sequence[float], b
 
 def _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_block_errors, target_bler,
                  early_stop, num_it, precision, verbose, sync_every, label, soft=None, soft_scales=None,
-                 coded=None, coded_spec=None) -> SimResult:
-    """sim_ber; ``label`` prefixes the verbose lines (the CLI's runs with baselines)"""
+                 coded=None, coded_spec=None, cfo=None, cfo_stats=None) -> SimResult:
+    """sim_ber; ``label`` prefixes the verbose lines (the CLI's runs with baselines); ``cfo`` (a
+    ``CFOCompensator``): the forward reads the compensated ``h_hat``; ``cfo_stats`` (``CfoStats``)
+    gains every batch"""
     import torch
     p = gen.p
     dev = torch.device(f"cuda:{gen.device}")
@@ -214,6 +261,10 @@ def _sim_ber_nrx(engine, gen, ebno_dbs, batch_size, max_mc_iter, num_target_bloc
     last = {}
 
     def step(sb, no):
+        if cfo_stats is not None:
+            cfo_stats.add(sb, no)
+        if cfo is not None:
+            sb = cfo.apply_nn(sb)
         mcs_mask = sb.mcs_mask if spec.num_mcs > 1 else None
         llr, last["h"] = engine.forward(sb.y, pe, sb.h_hat, sb.active, mcs_mask=mcs_mask, num_it=num_it,
                                         precision=precision, out=llr_out, want_h=want_h)
@@ -334,7 +385,20 @@ def main(argv=None):
     ap.add_argument("-chest_2d", action="store_true",
                     help="on a correlated channel lmmse_lmmse uses the spatial covariance (nrx_chest_lmmse3); this "
                          "keeps the 2-D filter that ignores it, so that both can be tabulated")
+    ap.add_argument("-cfo_hz", type=float, default=None, metavar="HZ",
+                    help="per-user carrier frequency offset at the transmitter, drawn uniformly in +-HZ per "
+                         "(slot, user) (GenParams.cfo_hz); the generator then runs with h_with_phase")
+    ap.add_argument("-cfo_ppm", type=float, default=None, metavar="PPM",
+                    help="the same as a fraction of the carrier: HZ = carrier_frequency_hz / 1e6 * PPM")
+    ap.add_argument("-carrier_frequency_hz", type=float, default=2.14e9)
+    ap.add_argument("-cfo_constant", action="store_true", help="every user has exactly the offset, not a draw")
+    ap.add_argument("-cfo_comp", action="store_true",
+                    help="DMRS-based CFO estimation and compensation (cfo.py) in front of every system: the NRX and "
+                         "lsnn_lmmse read the compensated h_hat, the estimators run between a de-rotation and a "
+                         "re-rotation")
     a = ap.parse_args(argv)
+    if a.cfo_hz is not None and a.cfo_ppm is not None:
+        ap.error("-cfo_hz and -cfo_ppm are two ways to say the same thing: give one")
 
     import torch
     import torch.distributed as dist
@@ -356,6 +420,10 @@ def main(argv=None):
         params = scenario(a.channel, params)
     if a.rx_corr is not None:
         params = dataclasses.replace(params, rx_corr=rx_correlation(params.num_rx_ant, a.rx_corr))
+    cfo_hz = a.cfo_hz if a.cfo_hz is not None else \
+        a.carrier_frequency_hz / 1e6 * a.cfo_ppm if a.cfo_ppm is not None else None
+    if cfo_hz is not None:
+        params = dataclasses.replace(params, cfo_hz=cfo_hz, cfo_constant=a.cfo_constant, h_with_phase=True)
     # a correlated channel: the LMMSE estimator takes the spatial covariance unless -chest_2d keeps it out
     chest3 = params.rx_corr is not None and not a.chest_2d
     systems = {n: "baseline_" + n for n in a.baselines}
@@ -368,9 +436,12 @@ def main(argv=None):
     if a.ldpc:
         from .ldpc import DecoderSpec
         coded_spec = DecoderSpec(code_name=a.ldpc, num_iter=a.ldpc_iter, cn_type=a.ldpc_cn)
+    comp = CFOCompensator(params, device=device) if a.cfo_comp or cfo_hz is not None else None
+    cfo_stats = CfoStats(comp) if cfo_hz is not None else None
+    comp = comp if a.cfo_comp else None
     res = _sim_ber_nrx(engine, gen, ebno, a.batch_size, a.max_mc_iter, a.num_target_block_errors, a.target_bler,
                        True, cfg.num_nrx_iter_eval, a.precision, True, a.sync_every, "nrx" if systems else None,
-                       soft.get("nrx"), a.llr_scales, coded.get("nrx"), coded_spec)
+                       soft.get("nrx"), a.llr_scales, coded.get("nrx"), coded_spec, comp, cfo_stats)
     base = {}
     cov = None
     if {"lmmse_lmmse", "lmmse_kbest"} & set(systems):
@@ -378,21 +449,27 @@ def main(argv=None):
         # estimates the same matrices from the same slots
         if a.num_cov_slots < 1 or COV_SLOT_OFFSET <= len(ebno) * a.max_mc_iter * world * a.batch_size:
             raise ValueError("-num_cov_slots must be >= 1 and the Monte-Carlo slots must end below 2^40")
-        est = estimate_covariance(gen, a.num_cov_slots, a.batch_size)
+        # behind the compensation the estimator sees de-rotated pilots: its covariance is the one of the
+        # channel without the offset
+        cov_gen = gen if comp is None or cfo_hz is None else \
+            SlotGenerator(dataclasses.replace(params, cfo_hz=None), device=device, want_h=True)
+        est = estimate_covariance(cov_gen, a.num_cov_slots, a.batch_size)
         cov = est.matrices()
         R_s = est.space() if chest3 else None
     for name, system in systems.items():
         if system in KBestBaselineReceiver.SYSTEMS:
-            rx = KBestBaselineReceiver(system, params, device=device, k=a.kbest_k)
+            rx = KBestBaselineReceiver(system, params, device=device, k=a.kbest_k, cfo=comp)
             if cov is not None:
                 rx.set_covariance(*cov)
         elif system in EstimatorBaselineReceiver.SYSTEMS:
             # the filter is designed again at every Eb/N0 point (ChannelEstimator.prepare)
-            rx = EstimatorBaselineReceiver(system, params, device=device)
+            rx = EstimatorBaselineReceiver(system, params, device=device, cfo=comp)
             if cov is not None:
                 rx.set_covariance(*cov, R_s=R_s)
         else:
             rx = BaselineReceiver(system, params, device=device)
+            if comp is not None:
+                rx = CompensatedReceiver(rx, comp)
         note = baseline_note(name, rx)
         if note and rank == 0:
             print(note, flush=True)
@@ -413,6 +490,14 @@ def main(argv=None):
             d.update(channel=a.channel, user_profiles=[list(x) for x in params.profiles()],
                      rx_corr=a.rx_corr if a.rx_corr is not None else SCENARIOS.get(a.channel),
                      chest="lmmse3" if chest3 else "lmmse")
+        if cfo_hz is not None or a.cfo_comp:       # a run without either keeps the keys it always had
+            d["cfo"] = dict(cfo_hz=cfo_hz, cfo_ppm=a.cfo_ppm, carrier_frequency_hz=a.carrier_frequency_hz,
+                            constant=a.cfo_constant, comp=a.cfo_comp, h_with_phase=cfo_hz is not None,
+                            subcarrier_spacing=params.subcarrier_spacing)
+            if cfo_stats is not None:
+                # rms of eps_hat - eps (in subcarrier spacings) over this rank's active (slot, user) pairs
+                d["cfo"]["eps_rms_error"] = [cfo_stats.rms(ebno_to_no(float(e), len(params.dmrs_symbols)))
+                                             for e in res.ebno_db]
         if base:
             d["baselines"] = {name: r.as_dict() for name, r in base.items()}
         for name, points in soft.items():

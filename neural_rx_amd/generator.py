@@ -14,6 +14,10 @@ correlation (utils/channel_models.py:20-161), through ``nrx_generate_slots_ex``.
 
 Everything runs through ``libnrx.so`` (``nrx_generate_slots`` / ``nrx_generate_slots_ex`` /
 ``nrx_count_errors``, include/nrx.h); torch tensors are only device containers.
+
+``GenParams.cfo_hz`` adds a per-user carrier frequency offset at the transmitter (the reference's
+``cfo_offset_ppm(_eval)``, utils/impairments.py:18-110), through ``nrx_generate_slots_cfo``; the
+receiver-side remedy is ``neural_rx_amd/cfo.py``.
 """
 from __future__ import annotations
 
@@ -63,6 +67,12 @@ class GenParams:
     user_profiles: Optional[Sequence] = None
     # receive-antenna correlation, A x A Hermitian PSD (rx_correlation); None = i.i.d. antennas
     rx_corr: Optional[np.ndarray] = None
+    # carrier frequency offset in Hz, one value or one per port (include/nrx.h nrx_gen_cfo); None = the
+    # generator without it.  Drawn uniformly in +-cfo_hz per (slot, user) unless cfo_constant.
+    cfo_hz: Optional[object] = None
+    cfo_constant: bool = False
+    fft_size: int = 0                  # N of the CFO's Dirichlet kernel; 0 = num_subcarriers
+    h_with_phase: bool = False         # SlotBatch.h = the diagonal of the effective channel under the CFO
 
     @classmethod
     def from_config(cls, cfg: NRXConfig | str, num_tx: Optional[int] = None, num_prbs: Optional[int] = None,
@@ -120,6 +130,17 @@ class GenParams:
             raise ValueError(f"user_profiles needs one (max_delay_s, max_doppler_hz) per port: "
                              f"{self.num_tx}, got {len(prof)}")
         return prof
+
+    def cfo_per_port(self) -> Optional[list]:
+        """``cfo_hz`` of every port, or None"""
+        if self.cfo_hz is None:
+            return None
+        v = [float(x) for x in np.atleast_1d(np.asarray(self.cfo_hz, np.float64))]
+        if len(v) == 1:
+            v = v * self.num_tx
+        if len(v) != self.num_tx:
+            raise ValueError(f"cfo_hz needs one value or one per port: {self.num_tx}, got {len(v)}")
+        return v
 
     def rx_mix(self) -> Optional[np.ndarray]:
         """``M = V diag(sqrt(mu)) V^H``, the Hermitian square root of ``rx_corr`` (complex128
@@ -198,6 +219,7 @@ class SlotBatch:
     y_imag: "object" = None
     h_ls_real: "object" = None
     h_ls_imag: "object" = None
+    cfo_eps: "object" = None   # [B, U] f64: the carrier frequency offset in subcarrier spacings, or None
 
 
 class SlotGenerator:
@@ -225,11 +247,21 @@ class SlotGenerator:
                 self._mix = torch.from_numpy(m).to(f"cuda:{device}")
                 c.rx_mix = self._mix.data_ptr()
             self._chan = c
+        self._cfo = None
+        if params.cfo_hz is not None:
+            c = _lib.nrx_gen_cfo()
+            for u, hz in enumerate(params.cfo_per_port()):
+                c.cfo_hz[u] = hz
+            c.constant, c.fft_size, c.h_with_phase = int(params.cfo_constant), int(params.fft_size), int(params.h_with_phase)
+            self._cfo = c
 
     def workspace_bytes(self, batch: int) -> int:
         n = ctypes.c_size_t()
         d = self.p.desc(batch, 0.0)
-        _lib.check(self._lib.nrx_gen_workspace_size(ctypes.byref(d), ctypes.byref(n)))
+        if self._cfo is not None:
+            _lib.check(self._lib.nrx_gen_workspace_size_cfo(ctypes.byref(d), ctypes.byref(self._cfo), ctypes.byref(n)))
+        else:
+            _lib.check(self._lib.nrx_gen_workspace_size(ctypes.byref(d), ctypes.byref(n)))
         return n.value
 
     def _alloc(self, batch: int) -> SlotBatch:
@@ -254,6 +286,8 @@ class SlotGenerator:
             sb.y_imag = torch.empty_like(sb.y_real)
             sb.h_ls_real = torch.empty((batch, npil, U, A), **f32)
             sb.h_ls_imag = torch.empty_like(sb.h_ls_real)
+        if self._cfo is not None:      # zeros: an all-zero cfo_hz is the generator without it, which writes no eps
+            sb.cfo_eps = torch.zeros((batch, U), dtype=torch.float64, device=dev)
         self._bufs = {key: sb}
         return sb
 
@@ -281,7 +315,12 @@ class SlotGenerator:
         o.h_ls_real, o.h_ls_imag = ptr(sb.h_ls_real), ptr(sb.h_ls_imag)
         if stream is None:
             stream = torch.cuda.current_stream(sb.y.device).cuda_stream
-        if self._chan is not None:
+        if self._cfo is not None:
+            self._cfo.eps_out = ptr(sb.cfo_eps)
+            _lib.check(self._lib.nrx_generate_slots_cfo(
+                ctypes.byref(d), ctypes.byref(self._chan) if self._chan is not None else None,
+                ctypes.byref(self._cfo), ctypes.byref(o), ws.data_ptr(), ws.numel(), stream))
+        elif self._chan is not None:
             _lib.check(self._lib.nrx_generate_slots_ex(ctypes.byref(d), ctypes.byref(self._chan), ctypes.byref(o),
                                                        ws.data_ptr(), ws.numel(), stream))
         else:

@@ -107,11 +107,13 @@ class KBestBaselineReceiver:
     ``R_t``, here or through ``set_covariance``, and works on LS estimates at the pilots, so it is
     meaningful for at most one active port per CDM group).
     ``baseline_perf_csi_kbest``: ``sb.h`` (the generator must run with ``want_h=True``) and
-    ``err_var = 0``."""
+    ``err_var = 0``.
+    ``cfo`` (a ``cfo.CFOCompensator``): the estimator leg runs through it (``chest.ChannelEstimator``)."""
 
     SYSTEMS = SYSTEMS
 
-    def __init__(self, system: str, params: GenParams, device: int = 0, k: int = MAX_K, R_f=None, R_t=None):
+    def __init__(self, system: str, params: GenParams, device: int = 0, k: int = MAX_K, R_f=None, R_t=None,
+                 cfo=None):
         if system not in SYSTEMS:
             raise ValueError(f"system must be one of {SYSTEMS}, got {system!r}")
         if params.num_tx > MAX_TX:
@@ -124,7 +126,7 @@ class KBestBaselineReceiver:
         self.perfect_csi = system == "baseline_perf_csi_kbest"
         # the estimator leg is the one of baseline_lmmse_lmmse: same estimate, same err_var
         self._est = None if self.perfect_csi else \
-            EstimatorBaselineReceiver("baseline_lmmse_lmmse", params, device, R_f=R_f, R_t=R_t)
+            EstimatorBaselineReceiver("baseline_lmmse_lmmse", params, device, R_f=R_f, R_t=R_t, cfo=cfo)
         self.detector = KBestDetector(device)
         self._out = None
         self.last_h = None      # the estimate the last call detected with; None with perfect CSI
