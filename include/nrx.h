@@ -385,6 +385,84 @@ typedef struct nrx_cfo_io {
 int nrx_cfo_estimate(const nrx_cfo_io* io, void* stream);
 int nrx_cfo_rotate(const nrx_cfo_io* io, void* stream);
 
+/* ---------------------------------------------------------------- cover-coded DMRS ports, LS estimator
+ * DMRS ports in the arrangement of DMRS configuration type 1, as this project defines it, and the
+ * receiver-side least-squares estimate that despreads them (the step of the reference's
+ * NeuralPUSCHReceiver.estimate_channel, neural_rx.py:1462-1514).  tests/dmrs_ref.py states both in
+ * numpy float64.
+ *
+ * Port u is (g, wf, wt) = (cdm_group[u], focc[u], tocc[u]): the comb offset, a frequency cover over
+ * the pairs (j, j^1) of comb positions j = f >> 1, and a time cover over the pairs (k, k^1) of
+ * positions k in dmrs_symbols.  With r[g][j][k] the base sequence of CDM group g, port u sends
+ *   x_u[f, t_k] = active r[g][j][k] (-1)^(wf (j & 1)) (-1)^(wt (k & 1))     on f mod 2 = g, else 0,
+ * so the up to 8 ports are orthogonal over a 2 x 2 block of pilots.  The estimate is, with
+ * z[j][k][a] = y[f][t_k][a] conj(p) / |p|^2, p = pilots[g][j][k],
+ *   h_ls_u[j][k][a] = mean over j' in {j, j^1 if despread_f}, k' in {k, k^1 if despread_t} of
+ *                     (-1)^(wf (j' & 1) + wt (k' & 1)) z[j'][k'][a],
+ * complex f64 arithmetic on the f32 inputs, rounded once to f32; a port with active <= 0 gives zeros.
+ *   h_hat      [B][U][F][T][2A]  h_ls at the port's nearest own pilot: Manhattan distance, first in
+ *              the pilot order (subcarrier-major, then DMRS symbol) -- the generator's rule.  A port
+ *              without a pilot in the grid (F = 1, group 1) gives zeros.
+ *   h_ls_real / h_ls_imag [B][Npil][U][A]  the Aerial pilot list (nrx_aerial_io; Npil = nd F / 2,
+ *              p = k F / 2 + j, needs F % 12 == 0): the estimate before frequency despreading,
+ *              (-1)^(wf (j & 1)) times the mean over the time pair only, so that the pair average of
+ *              nrx_forward_aerial / nrx_aerial_preprocess performs the frequency despreading.
+ * Asynchronous on `stream`; no workspace, no atomics, no allocation, no host synchronisation; the
+ * same bits on every call and for every batch split.
+ *
+ * Checks, all before the first HIP call: a NULL io / y / pilots, all three outputs NULL, or only one
+ * of h_ls_real / h_ls_imag is NRX_ERR_INVALID_ARG; the shape limits and codes are those of
+ * nrx_chest_io; focc / tocc of a port < U or despread_f / despread_t outside {0, 1}, two ports < U
+ * with the same (g, wf, wt), a port with wf = 1 without despread_f or with wt = 1 without despread_t,
+ * and despread_t with an odd num_dmrs_symbols or a pair that is not (t, t + 1) are
+ * NRX_ERR_INVALID_ARG; despread_f with F % 4 != 0 and the Aerial list with F % 12 != 0 are
+ * NRX_ERR_SHAPE.  Entries of ports >= U are not read. */
+typedef struct nrx_ls_io {
+  int32_t batch, num_tx, num_subcarriers, num_symbols;   /* B, U (1..16), F (1..3300), T = 14 */
+  int32_t num_rx_ant;          /* A, 1..16 */
+  int32_t num_dmrs_symbols;    /* nd, 1..4 */
+  int32_t dmrs_symbols[4];     /* ascending */
+  int32_t cdm_group[16];       /* per port, 0/1 */
+  int32_t focc[16];            /* per port, 0/1: frequency cover */
+  int32_t tocc[16];            /* per port, 0/1: time cover */
+  int32_t despread_f;          /* 0/1: average the frequency pair (needs F % 4 == 0) */
+  int32_t despread_t;          /* 0/1: average the time pair (needs DMRS symbols in pairs t, t + 1) */
+  const float* y;              /* [B][F][T][2A] */
+  const float* pilots;         /* [2][Pmax][nd][2] (re, im), Pmax = (F + 1) / 2; any non-zero values */
+  const float* active;         /* [B][U], or NULL = every port active */
+  float*       h_hat;          /* [B][U][F][T][2A], or NULL */
+  float*       h_ls_real;      /* [B][Npil][U][A], or NULL (with h_ls_imag) */
+  float*       h_ls_imag;
+} nrx_ls_io;
+
+int nrx_ls_estimate(const nrx_ls_io* io, void* stream);
+
+/* The slot generator with such ports.  The base sequence is r[g][j][k] = s0 + j s1 with
+ * s = 1 - 2 bit, bits 0 and 1 of word 0 of the Philox draw (slot 0, stream 7, element
+ * (g Pmax + j) 4 + k): amplitude sqrt(2), a function of the seed alone -- not of the slot or the user
+ * -- and a stream of its own, so no other draw moves.  It is this project's sequence, not the Gold
+ * sequence of TS 38.211.
+ * dmrs == NULL is exactly nrx_generate_slots_cfo: the same launches, workspace and bits.  With a
+ * dmrs, the pilots of port u are x_u above with cdm_group from the desc; data REs, bits, mcs, active,
+ * h and the noise keep their draws, so y differs on the DMRS symbols only; h_hat and the Aerial
+ * list come from the device code of nrx_ls_estimate, run on the generator's y, pilot table and active
+ * mask (bit-equal to that call); pilots_out (optional, device [2][Pmax][nd][2] f32) receives the
+ * table.  The workspace grows by the table (nrx_gen_workspace_size_dmrs).  The port checks are those
+ * of nrx_ls_estimate, the others those of nrx_generate_slots_cfo, all before the first HIP call. */
+typedef struct nrx_gen_dmrs {
+  int32_t focc[16];            /* per port, 0/1 */
+  int32_t tocc[16];            /* per port, 0/1 */
+  int32_t despread_f;          /* 0/1, of the generator's own LS outputs */
+  int32_t despread_t;
+  float* pilots_out;           /* device, or NULL */
+} nrx_gen_dmrs;
+
+int nrx_gen_workspace_size_dmrs(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
+                                size_t* bytes);
+int nrx_generate_slots_dmrs(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                            const nrx_gen_dmrs* dmrs, const nrx_gen_out* out, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* Uncoded error counters of one batch (sim_ber's counting, scripts/evaluate.py:193-202,
  * with the active-port masking of E2E_Model._mask_active_dmrs, e2e_model.py:195-209):
  * counts[u][0..3] += (bit errors, bits, block errors, blocks) over the active (slot, user)

@@ -37,6 +37,7 @@ EXPORTS = [
     "nrx_chest3_workspace_size", "nrx_chest_lmmse3", "nrx_aerial_preprocess",
     "nrx_ldpc_create", "nrx_ldpc_destroy", "nrx_ldpc_workspace_size", "nrx_ldpc_decode", "nrx_ldpc_gather",
     "nrx_ldpc_count", "nrx_gen_workspace_size_cfo", "nrx_generate_slots_cfo", "nrx_cfo_estimate", "nrx_cfo_rotate",
+    "nrx_ls_estimate", "nrx_gen_workspace_size_dmrs", "nrx_generate_slots_dmrs",
 ]
 # nrx_cfo_io.ref_mode (NRX_CFO_REF_*)
 CFO_REF_NEAREST_DMRS = 0
@@ -196,6 +197,39 @@ class nrx_cfo_io(ctypes.Structure):
         ("active", ctypes.c_void_p),
         ("eps", ctypes.c_void_p),
         ("h_out", ctypes.c_void_p),
+    ]
+
+
+class nrx_ls_io(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("num_tx", ctypes.c_int32),
+        ("num_subcarriers", ctypes.c_int32),
+        ("num_symbols", ctypes.c_int32),
+        ("num_rx_ant", ctypes.c_int32),
+        ("num_dmrs_symbols", ctypes.c_int32),
+        ("dmrs_symbols", ctypes.c_int32 * 4),
+        ("cdm_group", ctypes.c_int32 * 16),
+        ("focc", ctypes.c_int32 * 16),
+        ("tocc", ctypes.c_int32 * 16),
+        ("despread_f", ctypes.c_int32),
+        ("despread_t", ctypes.c_int32),
+        ("y", ctypes.c_void_p),
+        ("pilots", ctypes.c_void_p),
+        ("active", ctypes.c_void_p),
+        ("h_hat", ctypes.c_void_p),
+        ("h_ls_real", ctypes.c_void_p),
+        ("h_ls_imag", ctypes.c_void_p),
+    ]
+
+
+class nrx_gen_dmrs(ctypes.Structure):
+    _fields_ = [
+        ("focc", ctypes.c_int32 * 16),
+        ("tocc", ctypes.c_int32 * 16),
+        ("despread_f", ctypes.c_int32),
+        ("despread_t", ctypes.c_int32),
+        ("pilots_out", ctypes.c_void_p),
     ]
 
 
@@ -528,6 +562,13 @@ def load(path: str = LIB_PATH):
     lib.nrx_cfo_estimate.restype = c.c_int
     lib.nrx_cfo_rotate.argtypes = [P(nrx_cfo_io), c.c_void_p]
     lib.nrx_cfo_rotate.restype = c.c_int
+    lib.nrx_ls_estimate.argtypes = [P(nrx_ls_io), c.c_void_p]
+    lib.nrx_ls_estimate.restype = c.c_int
+    lib.nrx_gen_workspace_size_dmrs.argtypes = [P(nrx_gen_desc), P(nrx_gen_cfo), P(nrx_gen_dmrs), P(c.c_size_t)]
+    lib.nrx_gen_workspace_size_dmrs.restype = c.c_int
+    lib.nrx_generate_slots_dmrs.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo), P(nrx_gen_dmrs),
+                                            P(nrx_gen_out), c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.nrx_generate_slots_dmrs.restype = c.c_int
     lib.nrx_cov_space_workspace_size.argtypes = [P(nrx_cov_space_io), P(c.c_size_t)]
     lib.nrx_cov_space_workspace_size.restype = c.c_int
     lib.nrx_cov_space_accumulate.argtypes = [P(nrx_cov_space_io), c.c_void_p, c.c_size_t, c.c_void_p]

@@ -93,7 +93,9 @@ class BaselineReceiver:
     ``baseline_lsnn_lmmse``: ``sb.h_hat`` and ``err_var = num_active * no / 2`` -- the generator's
     pilots have energy 2, so the LS error of each active user has variance ``no / 2`` per antenna,
     and at a data RE those errors (times unit-energy symbols) add to the noise.  Meaningful for
-    at most one active port per CDM group (module docstring).
+    at most one active port per CDM group (module docstring) -- unless the ports carry cover codes
+    (``GenParams.dmrs``): ``sb.h_hat`` is then the despread estimate over ``n = dmrs.block`` pilots
+    (1, 2 or 4), ``err_var = num_active * no / (2 n)``, and ports of one group are separated.
     ``baseline_perf_csi_lmmse``: ``sb.h`` (the generator must run with ``want_h=True``) and
     ``err_var = 0``."""
 
@@ -116,13 +118,14 @@ class BaselineReceiver:
         p = self.p
         na = p.num_tx if p.num_active is None else p.num_active
         groups = list(p.cdm_group[:p.num_tx])
-        return not self.perfect_csi and na > 1 and max(groups.count(g) for g in set(groups)) > 1
+        return not self.perfect_csi and p.dmrs is None and na > 1 and max(groups.count(g) for g in set(groups)) > 1
 
     def err_var(self, no: float) -> float:
         if self.perfect_csi:
             return 0.0
         na = self.p.num_tx if self.p.num_active is None else self.p.num_active
-        return na * float(no) / 2.0
+        n = 1 if self.p.dmrs is None else self.p.dmrs.block
+        return na * float(no) / (2.0 * n)
 
     def __call__(self, sb: SlotBatch, no: float, out=None, stream=None):
         p = self.p

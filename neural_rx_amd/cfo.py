@@ -33,6 +33,9 @@ def _torch():
 
 class CFOCompensator:
     def __init__(self, params: GenParams, device: int = 0):
+        if params.dmrs is not None and params.dmrs.despread_t:
+            raise ValueError("the DMRS-based CFO estimate does not work on time-despread pilots (ports with a time "
+                             "cover): the two symbols of a pair hold one estimate, so the closest pair shows no rotation")
         self.p = params
         self.device = device
         self._lib = _lib.load()

@@ -174,7 +174,8 @@ class LMMSEDesign:
     no: float
 
 
-def lmmse_design(R_f: np.ndarray, R_t: np.ndarray, params: GenParams, no: float, dtype=np.float32) -> LMMSEDesign:
+def lmmse_design(R_f: np.ndarray, R_t: np.ndarray, params: GenParams, no: float, dtype=np.float32,
+                 despread_f: bool = False) -> LMMSEDesign:
     """The exact 2-D Wiener filter under ``R_t (x) R_f`` for LS estimates at the own pilots
     ``P = {f : f mod 2 = group}`` of the DMRS symbols ``D`` with noise ``sigma^2 = no / 2`` (the
     generator's pilots have energy 2), in the eigen form of ``R_t[D, D] = V diag(lambda) V^H``:
@@ -188,9 +189,20 @@ def lmmse_design(R_f: np.ndarray, R_t: np.ndarray, params: GenParams, no: float,
     The error map is ``e[f, t] = R_f[0, 0] - sum_j W_ij conj(C_ij)`` with ``C = R_t[:, D] (x) R_f[:, P]``,
     from the unrounded filter.  Components with ``lambda_k <= 1e-12 lambda_max`` are dropped (zero
     tables).  The tables are rounded once to float32, the kernel's format (``dtype=np.float64``
-    keeps them unrounded, for checks)."""
+    keeps them unrounded, for checks).
+
+    ``despread_f``: the pilots hold frequency-despread LS estimates (``ls.py``, cover-coded ports): both
+    pilots of a pair (P_2q, P_2q+1) hold ``o_q = (h[P_2q] + h[P_2q+1]) / 2`` plus noise of variance
+    ``sigma^2 / 2``.  With ``S`` the |P|/2 x |P| averaging matrix the filter of the observations is
+
+        W'_k = R_f[:, P] S^T (S R_f[P, P] S^T + (sigma^2 / (2 lambda_k)) I)^-1
+
+    and the kernel's table, which multiplies the pilots as they lie in ``h_hat``, is
+    ``W[:, 2q] = W[:, 2q+1] = W'[:, q] / 2``; the error map follows from ``W'``.  Needs F % 4 == 0."""
     if not no > 0:
         raise ValueError("no must be > 0")
+    if despread_f and params.num_subcarriers % 4:
+        raise ValueError("despread_f needs num_subcarriers % 4 == 0")
     F, T = params.num_subcarriers, NUM_SYMBOLS
     D = list(params.dmrs_symbols)
     nd = len(D)
@@ -216,9 +228,12 @@ def lmmse_design(R_f: np.ndarray, R_t: np.ndarray, params: GenParams, no: float,
             P = pilot_subcarriers(F, g)
             if not len(P):
                 continue
-            Rfp = R_f[:, P]
-            W = np.linalg.solve(R_f[np.ix_(P, P)] + (sigma2 / lam[k]) * np.eye(len(P)), Rfp.conj().T).conj().T
-            filt[g, k, :, :len(P)] = W
+            Rfp, Rpp, s2 = R_f[:, P], R_f[np.ix_(P, P)], sigma2
+            if despread_f:
+                S = np.kron(np.eye(len(P) // 2), [[0.5, 0.5]])
+                Rfp, Rpp, s2 = Rfp @ S.T, S @ Rpp @ S.T, sigma2 / 2.0
+            W = np.linalg.solve(Rpp + (s2 / lam[k]) * np.eye(Rpp.shape[0]), Rfp.conj().T).conj().T
+            filt[g, k, :, :len(P)] = np.repeat(W, 2, axis=1) / 2.0 if despread_f else W
             q = np.real(np.sum(W * np.conj(Rfp), axis=1))                     # [F]
             err[g] -= lam[k] * q[:, None] * (np.abs(tcoef[k]) ** 2)[None, :]
     for g in (0, 1):
@@ -339,6 +354,15 @@ class ChannelEstimator:
         self.p = params
         self.device = device
         self.cfo = cfo
+        # cover-coded ports (GenParams.dmrs): h_hat holds despread estimates.  A frequency pair holds one
+        # value, which lin interpolates as it is and lmmse designs its filter for; the rest is out of scope
+        self.despread_f = params.dmrs is not None and params.dmrs.despread_f
+        if params.dmrs is not None and params.dmrs.despread_t:
+            raise ValueError(f"the {kind} estimator does not take time-despread pilots (ports with a time cover): "
+                             "the two symbols of a pair hold one estimate")
+        if self.despread_f and kind == "lmmse3":
+            raise ValueError("the 3-D LMMSE estimator is not designed for cover-coded DMRS ports: use the 2-D "
+                             "filter (evaluate: -chest_2d)")
         self._lib = _lib.load()
         self.R_f, self.R_t, self.R_s = R_f, R_t, R_s
         self.design = None
@@ -384,7 +408,7 @@ class ChannelEstimator:
         if self.design is None or self.design.no != float(no):
             if self.R_f is None or self.R_t is None:
                 raise ValueError("the LMMSE estimator needs the covariance matrices (set_covariance)")
-            self._set_design(lmmse_design(self.R_f, self.R_t, self.p, no))
+            self._set_design(lmmse_design(self.R_f, self.R_t, self.p, no, despread_f=self.despread_f))
         return self.design
 
     def __call__(self, sb: SlotBatch, no: float, out=None, stream=None, workspace=None, cfo=None):
@@ -478,7 +502,10 @@ class EstimatorBaselineReceiver:
     a ``CovarianceEstimator``, here or through ``set_covariance``), both followed by the LMMSE
     detector of ``baseline.LMMSEDetector``.  Same call signature and ``contaminated`` property as
     ``baseline.BaselineReceiver``, and the same limit: both work on LS estimates at the pilots, so
-    they are meaningful for at most one active port per CDM group.
+    they are meaningful for at most one active port per CDM group -- or for cover-coded ports
+    (``GenParams.dmrs``), whose despread estimates separate the ports of a group: lin runs unchanged on
+    them, lmmse designs its filter for them (``lmmse_design(despread_f=True)``).  Refused: the 3-D
+    filter under cover codes, and every estimator on time-despread pilots.
 
     The detector takes one scalar ``err_var`` where Sionna passes a per-RE map -- an approximation
     in both systems: lmmse passes ``num_active x`` the mean over users' groups, subcarriers and data
@@ -522,11 +549,11 @@ class EstimatorBaselineReceiver:
     def contaminated(self) -> bool:
         """the LS estimates can be pilot-contaminated: two active ports may share a CDM group"""
         groups = list(self.p.cdm_group[:self.p.num_tx])
-        return self._num_active > 1 and max(groups.count(g) for g in set(groups)) > 1
+        return self.p.dmrs is None and self._num_active > 1 and max(groups.count(g) for g in set(groups)) > 1
 
     def err_var(self, no: float) -> float:
-        if self.estimator.kind == "lin":
-            return self._num_active * float(no) / 2.0
+        if self.estimator.kind == "lin":     # the LS error at a pilot, over the despreading block
+            return self._num_active * float(no) / (2.0 * (2 if self.estimator.despread_f else 1))
         d = self.estimator.prepare(no)
         data = [t for t in range(NUM_SYMBOLS) if t not in self.p.dmrs_symbols]
         groups = list(self.p.cdm_group[:self.p.num_tx])

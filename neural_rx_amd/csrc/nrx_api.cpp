@@ -107,6 +107,37 @@ int check_cdm_group(const int32_t* group, int num_tx) {
     if (group[u] != 0 && group[u] != 1) return fail(NRX_ERR_INVALID_ARG, "cdm_group must be 0/1");
   return NRX_OK;
 }
+// Cover-coded DMRS ports (nrx_ls_estimate, nrx_generate_slots_dmrs), after check_grid, check_dmrs_symbols and
+// check_cdm_group: covers and despreading flags 0/1, every port < num_tx its own (group, focc, tocc), a cover
+// only with its despreading, and the grid in whole despreading blocks
+int check_dmrs_ports(int num_tx, const int32_t* group, const int32_t* focc, const int32_t* tocc, int despread_f,
+                     int despread_t, int num_subcarriers, const int32_t* sym, int num_dmrs_symbols) {
+  if (int rc = check_range("despread_f", despread_f, 0, 1, NRX_ERR_INVALID_ARG)) return rc;
+  if (int rc = check_range("despread_t", despread_t, 0, 1, NRX_ERR_INVALID_ARG)) return rc;
+  unsigned seen = 0;
+  for (int u = 0; u < num_tx; ++u) {
+    if ((focc[u] != 0 && focc[u] != 1) || (tocc[u] != 0 && tocc[u] != 1))
+      return fail(NRX_ERR_INVALID_ARG, "focc and tocc must be 0/1");
+    const unsigned bit = 1u << (group[u] + 2 * focc[u] + 4 * tocc[u]);
+    if (seen & bit) return fail(NRX_ERR_INVALID_ARG, "two ports share one (cdm_group, focc, tocc)");
+    seen |= bit;
+    if (focc[u] && !despread_f) return fail(NRX_ERR_INVALID_ARG, "a port with focc = 1 needs despread_f");
+    if (tocc[u] && !despread_t) return fail(NRX_ERR_INVALID_ARG, "a port with tocc = 1 needs despread_t");
+  }
+  if (despread_f && num_subcarriers % 4)
+    return fail(NRX_ERR_SHAPE, "despread_f needs num_subcarriers % 4 == 0 (pairs of comb positions)");
+  if (despread_t) {
+    bool ok = num_dmrs_symbols % 2 == 0;
+    for (int k = 0; ok && k < num_dmrs_symbols; k += 2) ok = sym[k + 1] == sym[k] + 1;
+    if (!ok) return fail(NRX_ERR_INVALID_ARG, "despread_t needs dmrs_symbols in pairs (t, t + 1)");
+  }
+  return NRX_OK;
+}
+int check_aerial_list(const void* re, const void* im, int num_subcarriers) {
+  if ((re == nullptr) != (im == nullptr)) return fail(NRX_ERR_INVALID_ARG, "Aerial outputs come in (real, imag) pairs");
+  if (re && num_subcarriers % 12) return fail(NRX_ERR_SHAPE, "Aerial pilot list needs num_subcarriers % 12 == 0");
+  return NRX_OK;
+}
 int check_symbol_mask(const char* name, int v) {
   if (v >= 0 && v < (1 << kT)) return NRX_OK;
   return fail(NRX_ERR_INVALID_ARG, std::string(name) + " must be a mask of the 14 symbols");
@@ -718,6 +749,29 @@ int nrx_generate_slots_ex(const nrx_gen_desc* desc, const nrx_gen_chan* chan, co
 
 int nrx_generate_slots_cfo(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
                            const nrx_gen_out* out, void* workspace, size_t workspace_bytes, void* stream) {
+  return nrx_generate_slots_dmrs(desc, chan, cfo, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+static int check_gen_dmrs(const nrx_gen_desc* d, const nrx_gen_dmrs* dmrs) {
+  if (!dmrs) return NRX_OK;
+  return check_dmrs_ports(d->num_tx, d->cdm_group, dmrs->focc, dmrs->tocc, dmrs->despread_f, dmrs->despread_t,
+                          d->num_subcarriers, d->dmrs_symbols, d->num_dmrs_symbols);
+}
+
+int nrx_gen_workspace_size_dmrs(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
+                                size_t* bytes) {
+  if (int rc = check_gen(desc)) return rc;
+  GenCfo g{};
+  bool on;
+  if (int rc = check_gen_cfo(desc, cfo, &g, &on)) return rc;
+  if (int rc = check_gen_dmrs(desc, dmrs)) return rc;
+  return store_size(bytes, gen_workspace_bytes(*desc, nullptr, nullptr) + (on ? cfo_workspace_bytes(*desc) : 0) +
+                               (dmrs ? dmrs_workspace_bytes(*desc) : 0));
+}
+
+int nrx_generate_slots_dmrs(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                            const nrx_gen_dmrs* dmrs, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
+                            void* stream) {
   if (int rc = check_gen(desc)) return rc;
   nrx_gen_chan c{};                          // NULL chan: every port has the desc's scalars, no mixing
   for (int u = 0; u < desc->num_tx; ++u) {
@@ -732,17 +786,32 @@ int nrx_generate_slots_cfo(const nrx_gen_desc* desc, const nrx_gen_chan* chan, c
   GenCfo g{};
   bool cfo_on;
   if (int rc = check_gen_cfo(desc, cfo, &g, &cfo_on)) return rc;
+  if (int rc = check_gen_dmrs(desc, dmrs)) return rc;
   if (!out || !out->y) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (out->bits)
     if (int rc = check_bits_stride(out->bits_stride, desc->mcs_bits, desc->num_mcs)) return rc;
-  if ((out->y_real == nullptr) != (out->y_imag == nullptr) || (out->h_ls_real == nullptr) != (out->h_ls_imag == nullptr))
+  if ((out->y_real == nullptr) != (out->y_imag == nullptr))
     return fail(NRX_ERR_INVALID_ARG, "Aerial outputs come in (real, imag) pairs");
-  if (out->h_ls_real && desc->num_subcarriers % 12)
-    return fail(NRX_ERR_SHAPE, "Aerial pilot list needs num_subcarriers % 12 == 0");
-  const size_t need = gen_workspace_bytes(*desc, nullptr, nullptr) + (cfo_on ? cfo_workspace_bytes(*desc) : 0);
+  if (int rc = check_aerial_list(out->h_ls_real, out->h_ls_imag, desc->num_subcarriers)) return rc;
+  const size_t need = gen_workspace_bytes(*desc, nullptr, nullptr) + (cfo_on ? cfo_workspace_bytes(*desc) : 0) +
+                      (dmrs ? dmrs_workspace_bytes(*desc) : 0);
   if (int rc = check_workspace(workspace, workspace_bytes, need, 1)) return rc;
-  return launched(launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr),
+  return launched(launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr, dmrs),
                   "slot generator launch");
+}
+
+int nrx_ls_estimate(const nrx_ls_io* io, void* stream) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->y || !io->pilots) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (!io->h_hat && !io->h_ls_real && !io->h_ls_imag) return fail(NRX_ERR_INVALID_ARG, "null output pointer");
+  if (int rc = check_grid_ant(io)) return rc;
+  if (int rc = check_dmrs_symbols(io->dmrs_symbols, io->num_dmrs_symbols)) return rc;
+  if (int rc = check_cdm_group(io->cdm_group, io->num_tx)) return rc;
+  if (int rc = check_dmrs_ports(io->num_tx, io->cdm_group, io->focc, io->tocc, io->despread_f, io->despread_t,
+                                io->num_subcarriers, io->dmrs_symbols, io->num_dmrs_symbols))
+    return rc;
+  if (int rc = check_aerial_list(io->h_ls_real, io->h_ls_imag, io->num_subcarriers)) return rc;
+  return launched(launch_ls_estimate(*io, (hipStream_t)stream), "ls estimator launch");
 }
 
 // llr / bits of any slot count, with up to 31 symbols (the mask's bits): not the 14-symbol grid

@@ -173,8 +173,14 @@ size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base);
 // cfo (optional, nrx_generate_slots_cfo with a non-zero offset): the workspace holds the x' buffer
 // (cfo_workspace_bytes) behind the generator's own
 struct GenCfo;
+// dmrs (optional, nrx_generate_slots_dmrs): cover-coded ports; the pilot table (dmrs_workspace_bytes) lies
+// behind everything else, and h_hat / the Aerial list come from launch_ls_estimate
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
-                           hipStream_t st, const GenCfo* cfo = nullptr);
+                           hipStream_t st, const GenCfo* cfo = nullptr, const nrx_gen_dmrs* dmrs = nullptr);
+size_t dmrs_workspace_bytes(const nrx_gen_desc& d);
+
+// Despreading LS estimator (nrx_ls.hip); io validated by nrx_ls_estimate / nrx_generate_slots_dmrs
+hipError_t launch_ls_estimate(const nrx_ls_io& io, hipStream_t st);
 hipError_t launch_count_errors(const nrx_count_io& c, hipStream_t st);
 
 // Carrier frequency offset (nrx_cfo.hip); validated by nrx_generate_slots_cfo / nrx_cfo_estimate /

@@ -9,8 +9,9 @@
 
 namespace nrx {
 
-// stream ids of the counter word c3 (oracle/synth_ref.py STREAM_*; ST_CFO: tests/cfo_ref.py)
-enum { ST_RE = 0, ST_ACTIVE = 1, ST_MCS = 2, ST_DELAY = 3, ST_TAP = 4, ST_NOISE = 5, ST_CFO = 6 };
+// stream ids of the counter word c3 (oracle/synth_ref.py STREAM_*; ST_CFO: tests/cfo_ref.py;
+// ST_DMRS: tests/dmrs_ref.py)
+enum { ST_RE = 0, ST_ACTIVE = 1, ST_MCS = 2, ST_DELAY = 3, ST_TAP = 4, ST_NOISE = 5, ST_CFO = 6, ST_DMRS = 7 };
 
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kCP = 1.07;      // symbol time = 1.07 / scs (normal cyclic prefix)

@@ -10,6 +10,8 @@
 //   k_gen_taps     per (slot, user, antenna, tap, symbol): sum-of-sinusoids tap gain g(t)
 //   k_gen_mix      per (slot, user, tap, symbol): receive-antenna mixing of the finished taps
 //                  (nrx_generate_slots_ex with rx_mix; tests/synth_chan_ref.py states it)
+//   k_gen_pilots   per table entry: the DMRS base sequence of cover-coded ports (nrx_generate_slots_dmrs;
+//                  tests/dmrs_ref.py states it), whose h_hat / Aerial list come from nrx_ls.hip
 //   k_gen_tx       per (slot, user, RE): Philox bits, Gray QAM / DMRS QPSK x sqrt(2), x *= active
 //   k_gen_rx       per (slot, subcarrier): the user/tap phasors of that subcarrier in LDS,
 //                  then y[a][t] = sum_u H_u x_u + AWGN (and the true channel, optional)
@@ -215,9 +217,36 @@ __global__ __launch_bounds__(256) void k_gen_mix(GenWs w, const double* __restri
   }
 }
 
+// Cover-coded DMRS ports (nrx_generate_slots_dmrs): the base sequence r[g][j][k] as a table
+// [2][pmax][nd][2] f32 (exactly +-1), and the covers of port u in bit u.  ptab == nullptr: every port
+// draws its own pilots from its ST_RE words, the generator without a nrx_gen_dmrs.
+struct GenDmrs {
+  const float* ptab;
+  int pmax;
+  unsigned focc, tocc;
+};
+
+// r[g][j][k] = s0 + j s1, s = 1 - 2 bit of word 0 of the draw (slot 0, ST_DMRS, (g pmax + j) 4 + k):
+// a function of the seed alone.  One thread per table entry; out (optional) is the caller's copy.
+__global__ __launch_bounds__(256) void k_gen_pilots(nrx_gen_desc d, int pmax, float* __restrict__ tab,
+                                                    float* __restrict__ out) {
+  const int nd = d.num_dmrs_symbols;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 2 * pmax * nd) return;
+  const int k = i % nd, gj = i / nd;
+  const U4 r = philox((uint32_t)(gj * 4 + k), 0u, 0u, (uint32_t)ST_DMRS, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+  const float re = 1.0f - 2.0f * (float)(r.x & 1u), im = 1.0f - 2.0f * (float)((r.x >> 1) & 1u);
+  tab[2 * i] = re;
+  tab[2 * i + 1] = im;
+  if (out) {
+    out[2 * i] = re;
+    out[2 * i + 1] = im;
+  }
+}
+
 // one thread per (b, u, f, t)
 __global__ __launch_bounds__(256) void k_gen_tx(nrx_gen_desc d, GenWs w, uint8_t* __restrict__ bits,
-                                                int bits_stride) {
+                                                int bits_stride, GenDmrs dm) {
   const int U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols;
   const int64_t n = (int64_t)d.batch * U * F * T;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -230,7 +259,14 @@ __global__ __launch_bounds__(256) void k_gen_tx(nrx_gen_desc d, GenWs w, uint8_t
   const bool dmrs = (d.dmrs_symbol_mask >> t) & 1;
   const int m = d.mcs_bits[w.mcs[b * U + u]];
   double2 x;
-  if (dmrs) {
+  if (dmrs && dm.ptab) {
+    const int g = d.cdm_group[u], j = f >> 1;
+    const int k = __popc((unsigned)d.dmrs_symbol_mask & ((1u << t) - 1u));
+    const float* pp = dm.ptab + (((size_t)g * dm.pmax + j) * d.num_dmrs_symbols + k) * 2;
+    const bool neg = (((dm.focc >> u) & 1u) & (unsigned)j & 1u) != (((dm.tocc >> u) & 1u) & (unsigned)k & 1u);
+    const double sg = neg ? -1.0 : 1.0;
+    x = (f & 1) == g ? make_double2(sg * pp[0], sg * pp[1]) : make_double2(0.0, 0.0);
+  } else if (dmrs) {
     const double2 q = qam(r.y, 2);
     x = (f & 1) == d.cdm_group[u] ? make_double2(q.x * sqrt(2.0), q.y * sqrt(2.0)) : make_double2(0.0, 0.0);
   } else {
@@ -543,8 +579,12 @@ size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base) {
   return o;
 }
 
+size_t dmrs_workspace_bytes(const nrx_gen_desc& d) {
+  return al((size_t)2 * ((d.num_subcarriers + 1) / 2) * d.num_dmrs_symbols * 2 * sizeof(float));
+}
+
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
-                           hipStream_t st, const GenCfo* cfo) {
+                           hipStream_t st, const GenCfo* cfo, const nrx_gen_dmrs* dmrs) {
   GenWs w;
   const size_t own = gen_workspace_bytes(d, &w, (char*)ws);
   const int64_t B = d.batch, U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols, A = d.num_rx_ant,
@@ -553,7 +593,18 @@ hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const n
   k_gen_params<<<(unsigned)B, 64, 0, st>>>(d, c, w, o.active, o.mcs_mask, o.mcs);
   k_gen_taps<<<(unsigned)((B * U * A * L + kTapGroups - 1) / kTapGroups), kTapGroups * kT, 0, st>>>(d, c, w);
   if (c.rx_mix) k_gen_mix<<<blocks(B * U * L * kT), 256, 0, st>>>(w, c.rx_mix, (int)A, (int)(L * kT), B * U * L * kT);
-  k_gen_tx<<<blocks(B * U * F * T), 256, 0, st>>>(d, w, o.bits, o.bits_stride);
+  GenDmrs dm{};
+  if (dmrs) {
+    dm.ptab = reinterpret_cast<float*>((char*)ws + own + (cfo ? cfo_workspace_bytes(d) : 0));
+    dm.pmax = (int)((F + 1) / 2);
+    for (int u = 0; u < U; ++u) {
+      dm.focc |= (unsigned)dmrs->focc[u] << u;
+      dm.tocc |= (unsigned)dmrs->tocc[u] << u;
+    }
+    k_gen_pilots<<<blocks(2 * dm.pmax * d.num_dmrs_symbols), 256, 0, st>>>(d, dm.pmax, const_cast<float*>(dm.ptab),
+                                                                          dmrs->pilots_out);
+  }
+  k_gen_tx<<<blocks(B * U * F * T), 256, 0, st>>>(d, w, o.bits, o.bits_stride, dm);
   const int at = (int)(A * T);
   int FB = 256 / at;
   if (FB > 4) FB = 4;
@@ -570,6 +621,19 @@ hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const n
                                                                                  o.y_imag);
   if (cfo && cfo->h_with_phase && o.h)
     if (hipError_t e = launch_cfo_h_phase(d, *cfo, o.h, st)) return e;
+  if (dmrs) {      // one definition: the receiver-side estimator, on this call's y, pilot table and active mask
+    if (!o.h_hat && !o.h_ls_real) return hipGetLastError();
+    nrx_ls_io io{};
+    io.batch = d.batch, io.num_tx = d.num_tx, io.num_subcarriers = d.num_subcarriers, io.num_symbols = d.num_symbols;
+    io.num_rx_ant = d.num_rx_ant, io.num_dmrs_symbols = d.num_dmrs_symbols;
+    for (int k = 0; k < d.num_dmrs_symbols; ++k) io.dmrs_symbols[k] = d.dmrs_symbols[k];
+    for (int u = 0; u < U; ++u)
+      io.cdm_group[u] = d.cdm_group[u], io.focc[u] = dmrs->focc[u], io.tocc[u] = dmrs->tocc[u];
+    io.despread_f = dmrs->despread_f, io.despread_t = dmrs->despread_t;
+    io.y = o.y, io.pilots = dm.ptab, io.active = w.active;
+    io.h_hat = o.h_hat, io.h_ls_real = o.h_ls_real, io.h_ls_imag = o.h_ls_imag;
+    return launch_ls_estimate(io, st);
+  }
   if (o.h_hat) k_gen_ls<<<blocks(B * U * F * T * A), 256, 0, st>>>(d, w, o.y, o.h_hat);
   if (o.h_ls_real)
     k_gen_ls_aerial<<<blocks(B * d.num_dmrs_symbols * (F / 12) * 6 * U * A), 256, 0, st>>>(d, w, o.y, o.h_ls_real,

@@ -25,6 +25,10 @@ point without errors; ``target_bler`` ends it once the BLER falls below the targ
 ``cfo.py``.  One stated departure: under a CFO the generator runs with ``h_with_phase``, so the
 perfect-CSI systems and the NMSE see the diagonal of the effective channel; the reference hands its
 perfect-CSI baselines the un-rotated channel, with which they collapse.
+
+``-dmrs_cover`` gives the ``-num_tx_eval`` users orthogonal cover-coded DMRS ports (``ls.DMRSPorts``):
+``h_hat`` is then the despreading LS estimate and users of one CDM group no longer collide on their
+pilots; ``-dmrs_symbols 2 3 10 11`` supplies the symbol pairs that more than four ports need.
 """
 from __future__ import annotations
 
@@ -37,12 +41,13 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .config import dmrs_symbols, get_config
+from .config import get_config
 from .generator import SCENARIOS, GenParams, SlotGenerator, count_errors, ebno_to_no, rx_correlation, scenario
 from .baseline import BaselineReceiver
 from .chest import COV_SLOT_OFFSET, EstimatorBaselineReceiver, estimate_covariance
 from .cfo import CFOCompensator
 from .kbest import KBestBaselineReceiver
+from .ls import DMRSPorts
 from .receiver import CGNNEngine, compute_pe, spec_for
 
 
@@ -396,6 +401,13 @@ def main(argv=None):
                     help="DMRS-based CFO estimation and compensation (cfo.py) in front of every system: the NRX and "
                          "lsnn_lmmse read the compensated h_hat, the estimators run between a de-rotation and a "
                          "re-rotation")
+    ap.add_argument("-dmrs_cover", action="store_true",
+                    help="cover-coded DMRS ports (ls.DMRSPorts.for_config) for -num_tx_eval users, all active: CDM "
+                         "group x frequency cover x time cover, despread by the LS estimator (nrx_ls_estimate); more "
+                         "than 4 users need DMRS symbols in pairs (-dmrs_symbols 2 3 10 11)")
+    ap.add_argument("-dmrs_symbols", type=int, nargs="+", default=None, metavar="T",
+                    help="DMRS symbols in place of the config's, ascending, at most 4; the positional encoding, the "
+                         "data REs, the pilot overhead of Eb/N0 and the LDPC code size follow")
     a = ap.parse_args(argv)
     if a.cfo_hz is not None and a.cfo_ppm is not None:
         ap.error("-cfo_hz and -cfo_ppm are two ways to say the same thing: give one")
@@ -413,8 +425,12 @@ def main(argv=None):
     spec = spec_for(cfg)
     from . import weights as W
     engine = CGNNEngine(spec, W.load(cfg.label), device=device)
-    u = cfg.max_num_tx
+    u = (a.num_tx_eval or cfg.max_num_tx) if a.dmrs_cover else cfg.max_num_tx
     params = GenParams.from_config(cfg, num_tx=u, num_prbs=a.num_prbs, var_mcs=a.var_mcs, seed=a.seed)
+    if a.dmrs_symbols is not None:
+        params = dataclasses.replace(params, dmrs_symbols=tuple(a.dmrs_symbols))
+    if a.dmrs_cover:
+        params = dataclasses.replace(params, dmrs=DMRSPorts.for_config(cfg, u))
     params.num_active = a.num_tx_eval or u
     if a.channel != "iid":
         params = scenario(a.channel, params)
@@ -484,8 +500,11 @@ def main(argv=None):
     d = None
     if rank == 0:
         d = res.as_dict()
-        d.update(config=cfg.label, num_tx_eval=params.num_active, dmrs_symbols=list(dmrs_symbols(cfg)),
+        d.update(config=cfg.label, num_tx_eval=params.num_active, dmrs_symbols=list(params.dmrs_symbols),
                  world=world, slots_per_s=res.slots / res.seconds)
+        if a.dmrs_cover:            # a run without it keeps the keys it always had
+            d["dmrs_cover"] = dict(cdm_group=list(params.dmrs.cdm_group), focc=list(params.dmrs.focc),
+                                   tocc=list(params.dmrs.tocc), block=params.dmrs.block)
         if params.correlated:       # the iid run keeps the keys it always had
             d.update(channel=a.channel, user_profiles=[list(x) for x in params.profiles()],
                      rx_corr=a.rx_corr if a.rx_corr is not None else SCENARIOS.get(a.channel),

@@ -18,6 +18,10 @@ Everything runs through ``libnrx.so`` (``nrx_generate_slots`` / ``nrx_generate_s
 ``GenParams.cfo_hz`` adds a per-user carrier frequency offset at the transmitter (the reference's
 ``cfo_offset_ppm(_eval)``, utils/impairments.py:18-110), through ``nrx_generate_slots_cfo``; the
 receiver-side remedy is ``neural_rx_amd/cfo.py``.
+
+``GenParams.dmrs`` (an ``ls.DMRSPorts``) gives the ports orthogonal cover codes, through
+``nrx_generate_slots_dmrs``: ``h_hat`` and the Aerial pilot list are then the despreading LS estimate
+of ``neural_rx_amd/ls.py`` and ``SlotBatch.pilots`` is the pilot table an external caller of it needs.
 """
 from __future__ import annotations
 
@@ -29,6 +33,7 @@ import numpy as np
 
 from . import _lib
 from .config import NRXConfig, dmrs_symbols, get_config, user_cdm_groups
+from .ls import DMRSPorts
 
 NUM_SYMBOLS = 14
 
@@ -73,6 +78,16 @@ class GenParams:
     cfo_constant: bool = False
     fft_size: int = 0                  # N of the CFO's Dirichlet kernel; 0 = num_subcarriers
     h_with_phase: bool = False         # SlotBatch.h = the diagonal of the effective channel under the CFO
+    # cover-coded DMRS ports (ls.DMRSPorts; its cdm_group replaces the one above); None = the generator
+    # without cover codes, where every port draws its own pilots
+    dmrs: Optional[DMRSPorts] = None
+
+    def __post_init__(self):
+        if self.dmrs is not None:
+            if self.dmrs.num_tx != self.num_tx:
+                raise ValueError(f"dmrs holds {self.dmrs.num_tx} ports, num_tx is {self.num_tx}")
+            self.dmrs.validate(self.num_subcarriers, self.dmrs_symbols)
+            self.cdm_group = tuple(self.dmrs.cdm_group)
 
     @classmethod
     def from_config(cls, cfg: NRXConfig | str, num_tx: Optional[int] = None, num_prbs: Optional[int] = None,
@@ -220,6 +235,7 @@ class SlotBatch:
     h_ls_real: "object" = None
     h_ls_imag: "object" = None
     cfo_eps: "object" = None   # [B, U] f64: the carrier frequency offset in subcarrier spacings, or None
+    pilots: "object" = None    # [2, Pmax, nd, 2] f32: the DMRS base sequence (GenParams.dmrs), or None
 
 
 class SlotGenerator:
@@ -254,11 +270,22 @@ class SlotGenerator:
                 c.cfo_hz[u] = hz
             c.constant, c.fft_size, c.h_with_phase = int(params.cfo_constant), int(params.fft_size), int(params.h_with_phase)
             self._cfo = c
+        self._dmrs = None
+        if params.dmrs is not None:
+            m = _lib.nrx_gen_dmrs()
+            for u in range(params.num_tx):
+                m.focc[u], m.tocc[u] = params.dmrs.focc[u], params.dmrs.tocc[u]
+            m.despread_f, m.despread_t = int(params.dmrs.despread_f), int(params.dmrs.despread_t)
+            self._dmrs = m
 
     def workspace_bytes(self, batch: int) -> int:
         n = ctypes.c_size_t()
         d = self.p.desc(batch, 0.0)
-        if self._cfo is not None:
+        if self._dmrs is not None:
+            _lib.check(self._lib.nrx_gen_workspace_size_dmrs(
+                ctypes.byref(d), ctypes.byref(self._cfo) if self._cfo is not None else None, ctypes.byref(self._dmrs),
+                ctypes.byref(n)))
+        elif self._cfo is not None:
             _lib.check(self._lib.nrx_gen_workspace_size_cfo(ctypes.byref(d), ctypes.byref(self._cfo), ctypes.byref(n)))
         else:
             _lib.check(self._lib.nrx_gen_workspace_size(ctypes.byref(d), ctypes.byref(n)))
@@ -288,6 +315,8 @@ class SlotGenerator:
             sb.h_ls_imag = torch.empty_like(sb.h_ls_real)
         if self._cfo is not None:      # zeros: an all-zero cfo_hz is the generator without it, which writes no eps
             sb.cfo_eps = torch.zeros((batch, U), dtype=torch.float64, device=dev)
+        if self._dmrs is not None:
+            sb.pilots = torch.empty((2, (F + 1) // 2, len(p.dmrs_symbols), 2), **f32)
         self._bufs = {key: sb}
         return sb
 
@@ -317,6 +346,13 @@ class SlotGenerator:
             stream = torch.cuda.current_stream(sb.y.device).cuda_stream
         if self._cfo is not None:
             self._cfo.eps_out = ptr(sb.cfo_eps)
+        if self._dmrs is not None:
+            self._dmrs.pilots_out = ptr(sb.pilots)
+            _lib.check(self._lib.nrx_generate_slots_dmrs(
+                ctypes.byref(d), ctypes.byref(self._chan) if self._chan is not None else None,
+                ctypes.byref(self._cfo) if self._cfo is not None else None, ctypes.byref(self._dmrs), ctypes.byref(o),
+                ws.data_ptr(), ws.numel(), stream))
+        elif self._cfo is not None:
             _lib.check(self._lib.nrx_generate_slots_cfo(
                 ctypes.byref(d), ctypes.byref(self._chan) if self._chan is not None else None,
                 ctypes.byref(self._cfo), ctypes.byref(o), ws.data_ptr(), ws.numel(), stream))
