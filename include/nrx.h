@@ -463,6 +463,62 @@ int nrx_generate_slots_dmrs(const nrx_gen_desc* desc, const nrx_gen_chan* chan, 
                             const nrx_gen_dmrs* dmrs, const nrx_gen_out* out, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- channel impulse response replay
+ * The slot generator on a caller-supplied set of channel impulse responses (CIRs) instead of its own
+ * tapped-delay line: the reference's channel_type = "Dataset" (utils/channel_models.py:163-321, the
+ * site-specific evaluation).  tests/cir_ref.py states it in numpy f64.
+ *   dataset   a [E][A][L][Ta][2] f32 (re, im) path coefficients and tau [E][L] f32 path delays in
+ *             seconds, device arrays of the caller: E examples, A = desc.num_rx_ant, L paths, Ta = 1
+ *             (static over the slot) or 14 (one coefficient per OFDM symbol).
+ *   example   of (slot b, user u), by `select`:
+ *             0  e = index[b][u] (int32 device [B][U]); a value outside 0..E-1 gives that user a zero
+ *                channel and reads nothing of the dataset
+ *             1  e = w mod E, w = word 0 of the Philox draw (slot, stream 8, element u): a stream of
+ *                its own, so no other draw moves
+ *             2  n = E / U, e = U (w mod n) + u: user u stays on the examples that are u modulo U (the
+ *                reference's evaluation rule, two interleaved trajectories)
+ *   channel   H_u[a, f, t] = sum_{l < L} g_l(t) exp(-j 2 pi ((f + f_offset) subcarrier_spacing) tau[e][l]),
+ *             g_l(t) = a[e][a][l][Ta == 1 ? 0 : t]; f64, l ascending, the f32 inputs widened exactly.
+ *             f_offset = 0 is the built-in generator's convention, -F / 2 the centred one.
+ *   normalize c[b][u] = mean over (a, f, t) of |H_u|^2;  H_u <- H_u / sqrt(c), zeros where c = 0: unit
+ *             mean energy per (slot, user) over the grid.  Fixed-order f64 sums, no atomics.
+ * Everything behind H is the generator's: y = sum_u H_u x_u + noise with the same noise and x, h for
+ * every user, h_hat / the Aerial lists, the CFO (which acts on x) and the cover-coded ports.  bits, mcs
+ * and active are bit-equal to a built-in run of the same seed, so curves on the two channels are paired.
+ * cir == NULL is exactly nrx_generate_slots_dmrs: the same launches, workspace and bits.  With a cir,
+ * chan must be NULL (a dataset brings its own delay, Doppler and antenna structure); the desc's
+ * num_taps, num_sinusoids, max_delay_s and max_doppler_hz are validated as always and have no effect.
+ * The workspace grows by H in f64 and the energy sums (nrx_gen_workspace_size_cir).  Slot
+ * slot_offset + b stays a pure function of the global slot index and the dataset; every output element
+ * has one writer; the same bits on every call and for every split of the slots over calls.
+ * NRX_ERR_INVALID_ARG: a NULL or not 8-byte aligned a, a NULL tau, a NULL index with select == 0, select
+ * outside 0..2, a non-finite f_offset, chan != NULL.  NRX_ERR_SHAPE: num_examples outside 1..2^24,
+ * num_paths outside 1..1024 (a validation limit, not a hardware one), num_time_steps not 1 or 14,
+ * select == 2 with num_examples < num_tx.  The other checks are those of nrx_generate_slots_dmrs, all
+ * before the first HIP call. */
+typedef struct nrx_gen_cir {
+  int32_t num_examples, num_paths, num_time_steps, select;   /* E, L, Ta (1|14), 0|1|2 */
+  int32_t normalize, pad_;
+  double  f_offset;
+  const float*   a;      /* [E][A][L][Ta][2], 8-byte aligned */
+  const float*   tau;    /* [E][L] */
+  const int32_t* index;  /* [B][U], select == 0 only */
+} nrx_gen_cir;
+
+int nrx_gen_workspace_size_cir(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
+                               const nrx_gen_cir* cir, size_t* bytes);
+int nrx_generate_slots_cir(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                           const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_out* out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* The built-in channel in the dataset's format, to be replayed here or elsewhere: the finished taps of
+ * nrx_generate_slots_ex (PDP scaling and rx_mix included) and their delays, rounded once to f32.
+ * a_out [B][U][A][L][14][2], tau_out [B][U][L], L = desc.num_taps: a dataset of E = B U examples with
+ * Ta = 14, example b U + u.  The workspace is that of nrx_gen_workspace_size; the checks are those of
+ * nrx_generate_slots_ex, and a NULL a_out or tau_out is NRX_ERR_INVALID_ARG. */
+int nrx_generate_taps(const nrx_gen_desc* desc, const nrx_gen_chan* chan, float* a_out, float* tau_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* Uncoded error counters of one batch (sim_ber's counting, scripts/evaluate.py:193-202,
  * with the active-port masking of E2E_Model._mask_active_dmrs, e2e_model.py:195-209):
  * counts[u][0..3] += (bit errors, bits, block errors, blocks) over the active (slot, user)

@@ -38,6 +38,7 @@ EXPORTS = [
     "nrx_ldpc_create", "nrx_ldpc_destroy", "nrx_ldpc_workspace_size", "nrx_ldpc_decode", "nrx_ldpc_gather",
     "nrx_ldpc_count", "nrx_gen_workspace_size_cfo", "nrx_generate_slots_cfo", "nrx_cfo_estimate", "nrx_cfo_rotate",
     "nrx_ls_estimate", "nrx_gen_workspace_size_dmrs", "nrx_generate_slots_dmrs",
+    "nrx_gen_workspace_size_cir", "nrx_generate_slots_cir", "nrx_generate_taps",
 ]
 # nrx_cfo_io.ref_mode (NRX_CFO_REF_*)
 CFO_REF_NEAREST_DMRS = 0
@@ -230,6 +231,21 @@ class nrx_gen_dmrs(ctypes.Structure):
         ("despread_f", ctypes.c_int32),
         ("despread_t", ctypes.c_int32),
         ("pilots_out", ctypes.c_void_p),
+    ]
+
+
+class nrx_gen_cir(ctypes.Structure):
+    _fields_ = [
+        ("num_examples", ctypes.c_int32),
+        ("num_paths", ctypes.c_int32),
+        ("num_time_steps", ctypes.c_int32),
+        ("select", ctypes.c_int32),
+        ("normalize", ctypes.c_int32),
+        ("pad_", ctypes.c_int32),
+        ("f_offset", ctypes.c_double),
+        ("a", ctypes.c_void_p),
+        ("tau", ctypes.c_void_p),
+        ("index", ctypes.c_void_p),
     ]
 
 
@@ -569,6 +585,15 @@ def load(path: str = LIB_PATH):
     lib.nrx_generate_slots_dmrs.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo), P(nrx_gen_dmrs),
                                             P(nrx_gen_out), c.c_void_p, c.c_size_t, c.c_void_p]
     lib.nrx_generate_slots_dmrs.restype = c.c_int
+    lib.nrx_gen_workspace_size_cir.argtypes = [P(nrx_gen_desc), P(nrx_gen_cfo), P(nrx_gen_dmrs), P(nrx_gen_cir),
+                                               P(c.c_size_t)]
+    lib.nrx_gen_workspace_size_cir.restype = c.c_int
+    lib.nrx_generate_slots_cir.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo), P(nrx_gen_dmrs),
+                                           P(nrx_gen_cir), P(nrx_gen_out), c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.nrx_generate_slots_cir.restype = c.c_int
+    lib.nrx_generate_taps.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t,
+                                      c.c_void_p]
+    lib.nrx_generate_taps.restype = c.c_int
     lib.nrx_cov_space_workspace_size.argtypes = [P(nrx_cov_space_io), P(c.c_size_t)]
     lib.nrx_cov_space_workspace_size.restype = c.c_int
     lib.nrx_cov_space_accumulate.argtypes = [P(nrx_cov_space_io), c.c_void_p, c.c_size_t, c.c_void_p]

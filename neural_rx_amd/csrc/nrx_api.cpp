@@ -760,44 +760,94 @@ static int check_gen_dmrs(const nrx_gen_desc* d, const nrx_gen_dmrs* dmrs) {
 
 int nrx_gen_workspace_size_dmrs(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
                                 size_t* bytes) {
-  if (int rc = check_gen(desc)) return rc;
-  GenCfo g{};
-  bool on;
-  if (int rc = check_gen_cfo(desc, cfo, &g, &on)) return rc;
-  if (int rc = check_gen_dmrs(desc, dmrs)) return rc;
-  return store_size(bytes, gen_workspace_bytes(*desc, nullptr, nullptr) + (on ? cfo_workspace_bytes(*desc) : 0) +
-                               (dmrs ? dmrs_workspace_bytes(*desc) : 0));
+  return nrx_gen_workspace_size_cir(desc, cfo, dmrs, nullptr, bytes);
 }
 
 int nrx_generate_slots_dmrs(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
                             const nrx_gen_dmrs* dmrs, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
                             void* stream) {
+  return nrx_generate_slots_cir(desc, chan, cfo, dmrs, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+// a replayed channel (nrx_generate_slots_cir), after check_gen
+static int check_gen_cir(const nrx_gen_desc* d, const nrx_gen_cir* cir) {
+  if (!cir) return NRX_OK;
+  if (int rc = check_range("num_examples", cir->num_examples, 1, 1 << 24)) return rc;
+  if (int rc = check_range("num_paths", cir->num_paths, 1, 1024)) return rc;
+  if (cir->num_time_steps != 1 && cir->num_time_steps != kT)
+    return fail(NRX_ERR_SHAPE, "num_time_steps must be 1 or 14");
+  if (int rc = check_range("cir select", cir->select, 0, 2, NRX_ERR_INVALID_ARG)) return rc;
+  if (cir->select == 2 && cir->num_examples < d->num_tx)
+    return fail(NRX_ERR_SHAPE, "select 2 needs num_examples >= num_tx (one example per trajectory)");
+  if (!std::isfinite(cir->f_offset)) return fail(NRX_ERR_INVALID_ARG, "f_offset must be finite");
+  if (!cir->a || !cir->tau) return fail(NRX_ERR_INVALID_ARG, "null cir dataset pointer");
+  if ((uintptr_t)cir->a & 7) return fail(NRX_ERR_INVALID_ARG, "cir a must be 8-byte aligned");
+  if (cir->select == 0 && !cir->index) return fail(NRX_ERR_INVALID_ARG, "select 0 needs the cir index");
+  return NRX_OK;
+}
+
+// the generator's workspace: its own, then the x' of a CFO, the pilot table, the replayed H
+static size_t gen_need(const nrx_gen_desc* d, bool cfo_on, const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir) {
+  return gen_workspace_bytes(*d, nullptr, nullptr) + (cfo_on ? cfo_workspace_bytes(*d) : 0) +
+         (dmrs ? dmrs_workspace_bytes(*d) : 0) + (cir ? cir_workspace_bytes(*d) : 0);
+}
+
+int nrx_gen_workspace_size_cir(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
+                               const nrx_gen_cir* cir, size_t* bytes) {
   if (int rc = check_gen(desc)) return rc;
-  nrx_gen_chan c{};                          // NULL chan: every port has the desc's scalars, no mixing
+  GenCfo g{};
+  bool on;
+  if (int rc = check_gen_cfo(desc, cfo, &g, &on)) return rc;
+  if (int rc = check_gen_dmrs(desc, dmrs)) return rc;
+  if (int rc = check_gen_cir(desc, cir)) return rc;
+  return store_size(bytes, gen_need(desc, on, dmrs, cir));
+}
+
+// NULL chan: every port has the desc's scalars, no mixing
+static int check_gen_chan(const nrx_gen_desc* desc, const nrx_gen_chan* chan, nrx_gen_chan* c) {
   for (int u = 0; u < desc->num_tx; ++u) {
-    c.max_delay_s[u] = chan ? chan->max_delay_s[u] : desc->max_delay_s;
-    c.max_doppler_hz[u] = chan ? chan->max_doppler_hz[u] : desc->max_doppler_hz;
+    c->max_delay_s[u] = chan ? chan->max_delay_s[u] : desc->max_delay_s;
+    c->max_doppler_hz[u] = chan ? chan->max_doppler_hz[u] : desc->max_doppler_hz;
     if (!chan) continue;
-    if (int rc = check_nonneg("per-port delay spread", c.max_delay_s[u])) return rc;
-    if (int rc = check_nonneg("per-port Doppler spread", c.max_doppler_hz[u])) return rc;
+    if (int rc = check_nonneg("per-port delay spread", c->max_delay_s[u])) return rc;
+    if (int rc = check_nonneg("per-port Doppler spread", c->max_doppler_hz[u])) return rc;
   }
   if (chan && ((uintptr_t)chan->rx_mix & 7)) return fail(NRX_ERR_INVALID_ARG, "rx_mix must be 8-byte aligned");
-  c.rx_mix = chan ? chan->rx_mix : nullptr;
+  c->rx_mix = chan ? chan->rx_mix : nullptr;
+  return NRX_OK;
+}
+
+int nrx_generate_slots_cir(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                           const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_out* out, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  if (int rc = check_gen(desc)) return rc;
+  if (cir && chan) return fail(NRX_ERR_INVALID_ARG, "chan must be NULL with a cir: the dataset is the channel");
+  nrx_gen_chan c{};
+  if (int rc = check_gen_chan(desc, chan, &c)) return rc;
   GenCfo g{};
   bool cfo_on;
   if (int rc = check_gen_cfo(desc, cfo, &g, &cfo_on)) return rc;
   if (int rc = check_gen_dmrs(desc, dmrs)) return rc;
+  if (int rc = check_gen_cir(desc, cir)) return rc;
   if (!out || !out->y) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (out->bits)
     if (int rc = check_bits_stride(out->bits_stride, desc->mcs_bits, desc->num_mcs)) return rc;
   if ((out->y_real == nullptr) != (out->y_imag == nullptr))
     return fail(NRX_ERR_INVALID_ARG, "Aerial outputs come in (real, imag) pairs");
   if (int rc = check_aerial_list(out->h_ls_real, out->h_ls_imag, desc->num_subcarriers)) return rc;
-  const size_t need = gen_workspace_bytes(*desc, nullptr, nullptr) + (cfo_on ? cfo_workspace_bytes(*desc) : 0) +
-                      (dmrs ? dmrs_workspace_bytes(*desc) : 0);
-  if (int rc = check_workspace(workspace, workspace_bytes, need, 1)) return rc;
-  return launched(launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr, dmrs),
+  if (int rc = check_workspace(workspace, workspace_bytes, gen_need(desc, cfo_on, dmrs, cir), 1)) return rc;
+  return launched(launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr, dmrs, cir),
                   "slot generator launch");
+}
+
+int nrx_generate_taps(const nrx_gen_desc* desc, const nrx_gen_chan* chan, float* a_out, float* tau_out,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_gen(desc)) return rc;
+  nrx_gen_chan c{};
+  if (int rc = check_gen_chan(desc, chan, &c)) return rc;
+  if (!a_out || !tau_out) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (int rc = check_workspace(workspace, workspace_bytes, gen_workspace_bytes(*desc, nullptr, nullptr), 1)) return rc;
+  return launched(launch_export_taps(*desc, c, a_out, tau_out, workspace, (hipStream_t)stream), "tap export launch");
 }
 
 int nrx_ls_estimate(const nrx_ls_io* io, void* stream) {

@@ -175,9 +175,21 @@ size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base);
 struct GenCfo;
 // dmrs (optional, nrx_generate_slots_dmrs): cover-coded ports; the pilot table (dmrs_workspace_bytes) lies
 // behind everything else, and h_hat / the Aerial list come from launch_ls_estimate
+// cir (optional, nrx_generate_slots_cir): the channel is replayed from the caller's impulse responses;
+// H in f64 and its energy sums (cir_workspace_bytes) lie behind the pilot table
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
-                           hipStream_t st, const GenCfo* cfo = nullptr, const nrx_gen_dmrs* dmrs = nullptr);
+                           hipStream_t st, const GenCfo* cfo = nullptr, const nrx_gen_dmrs* dmrs = nullptr,
+                           const nrx_gen_cir* cir = nullptr);
 size_t dmrs_workspace_bytes(const nrx_gen_desc& d);
+// nrx_generate_taps: the finished taps and delays of the built-in channel, rounded to f32
+hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, float* a_out, float* tau_out, void* ws,
+                              hipStream_t st);
+
+// Channel impulse response replay (nrx_cir.hip); cir validated by nrx_generate_slots_cir.  x: [B][U][F][14]
+// complex f64, the grid the channel acts on; ws: cir_workspace_bytes of the caller's workspace
+size_t cir_workspace_bytes(const nrx_gen_desc& d);
+hipError_t launch_cir_rx(const nrx_gen_desc& d, const nrx_gen_cir& c, const double* x, void* ws, float* y, float* h,
+                         float* y_re, float* y_im, hipStream_t st);
 
 // Despreading LS estimator (nrx_ls.hip); io validated by nrx_ls_estimate / nrx_generate_slots_dmrs
 hipError_t launch_ls_estimate(const nrx_ls_io& io, hipStream_t st);

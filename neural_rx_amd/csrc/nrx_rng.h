@@ -10,8 +10,10 @@
 namespace nrx {
 
 // stream ids of the counter word c3 (oracle/synth_ref.py STREAM_*; ST_CFO: tests/cfo_ref.py;
-// ST_DMRS: tests/dmrs_ref.py)
-enum { ST_RE = 0, ST_ACTIVE = 1, ST_MCS = 2, ST_DELAY = 3, ST_TAP = 4, ST_NOISE = 5, ST_CFO = 6, ST_DMRS = 7 };
+// ST_DMRS: tests/dmrs_ref.py; ST_CIR: tests/cir_ref.py)
+enum {
+  ST_RE = 0, ST_ACTIVE = 1, ST_MCS = 2, ST_DELAY = 3, ST_TAP = 4, ST_NOISE = 5, ST_CFO = 6, ST_DMRS = 7, ST_CIR = 8
+};
 
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kCP = 1.07;      // symbol time = 1.07 / scs (normal cyclic prefix)
@@ -46,5 +48,11 @@ __device__ __forceinline__ U4 draw(const nrx_gen_desc& d, int64_t b, int stream,
 }
 
 __device__ __forceinline__ double uni(uint32_t w) { return ((double)w + 0.5) * 0x1p-32; }
+
+__device__ __forceinline__ double2 box_muller(uint32_t w0, uint32_t w1) {
+  const double r = sqrt(-2.0 * log(uni(w0)));
+  const double th = 2.0 * kPi * uni(w1);
+  return make_double2(r * cos(th), r * sin(th));
+}
 
 }  // namespace nrx

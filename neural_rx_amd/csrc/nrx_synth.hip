@@ -14,7 +14,9 @@
 //                  tests/dmrs_ref.py states it), whose h_hat / Aerial list come from nrx_ls.hip
 //   k_gen_tx       per (slot, user, RE): Philox bits, Gray QAM / DMRS QPSK x sqrt(2), x *= active
 //   k_gen_rx       per (slot, subcarrier): the user/tap phasors of that subcarrier in LDS,
-//                  then y[a][t] = sum_u H_u x_u + AWGN (and the true channel, optional)
+//                  then y[a][t] = sum_u H_u x_u + AWGN (and the true channel, optional); with a replayed
+//                  channel (nrx_generate_slots_cir) the kernels of nrx_cir.hip take its place and k_gen_taps's
+//   k_export_taps  per tap / delay: the finished taps and delays rounded to f32 (nrx_generate_taps)
 //   k_gen_ls       per (slot, user, RE, antenna): LS at the nearest own pilot (closed form
 //                  of the Manhattan argmin), and the Aerial pilot list (optional)
 //   k_count_errors per (slot group, user): hard decisions of the LLR head vs the sent bits on
@@ -46,12 +48,6 @@ struct GenWs {
 namespace {
 
 constexpr double kPDP = 3.0;      // PDP decay constant = max_delay / 3
-
-__device__ __forceinline__ double2 box_muller(uint32_t w0, uint32_t w1) {
-  const double r = sqrt(-2.0 * log(uni(w0)));
-  const double th = 2.0 * kPi * uni(w1);
-  return make_double2(r * cos(th), r * sin(th));
-}
 
 // Gray QAM of TS 38.211 5.1 (unit energy): bit k of `w`, k < m
 __device__ __forceinline__ double2 qam(uint32_t w, int m) {
@@ -583,16 +579,48 @@ size_t dmrs_workspace_bytes(const nrx_gen_desc& d) {
   return al((size_t)2 * ((d.num_subcarriers + 1) / 2) * d.num_dmrs_symbols * 2 * sizeof(float));
 }
 
+// the taps of the built-in channel into w.gt / w.tau (and active / mcs, which k_gen_params draws with them)
+static void launch_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, const GenWs& w, const nrx_gen_out& o,
+                        bool taps, hipStream_t st) {
+  const int64_t B = d.batch, U = d.num_tx, A = d.num_rx_ant, L = d.num_taps;
+  k_gen_params<<<(unsigned)B, 64, 0, st>>>(d, c, w, o.active, o.mcs_mask, o.mcs);
+  if (!taps) return;
+  k_gen_taps<<<(unsigned)((B * U * A * L + kTapGroups - 1) / kTapGroups), kTapGroups * kT, 0, st>>>(d, c, w);
+  if (c.rx_mix)
+    k_gen_mix<<<(unsigned)((B * U * L * kT + 255) / 256), 256, 0, st>>>(w, c.rx_mix, (int)A, (int)(L * kT),
+                                                                        B * U * L * kT);
+}
+
+// one thread per complex tap (a_out has the layout of w.gt) and per delay
+__global__ __launch_bounds__(256) void k_export_taps(GenWs w, int64_t ntap, int64_t ntau, float* __restrict__ a_out,
+                                                     float* __restrict__ tau_out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < ntap) {
+    const double2 g = w.gt[i];
+    a_out[2 * i] = (float)g.x;
+    a_out[2 * i + 1] = (float)g.y;
+  }
+  if (i < ntau) tau_out[i] = (float)w.tau[i];
+}
+
+hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, float* a_out, float* tau_out, void* ws,
+                              hipStream_t st) {
+  GenWs w;
+  gen_workspace_bytes(d, &w, (char*)ws);
+  const nrx_gen_out none{};
+  launch_taps(d, c, w, none, true, st);
+  const int64_t ntau = (int64_t)d.batch * d.num_tx * d.num_taps, ntap = ntau * d.num_rx_ant * kT;
+  k_export_taps<<<(unsigned)((ntap + 255) / 256), 256, 0, st>>>(w, ntap, ntau, a_out, tau_out);
+  return hipGetLastError();
+}
+
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
-                           hipStream_t st, const GenCfo* cfo, const nrx_gen_dmrs* dmrs) {
+                           hipStream_t st, const GenCfo* cfo, const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir) {
   GenWs w;
   const size_t own = gen_workspace_bytes(d, &w, (char*)ws);
-  const int64_t B = d.batch, U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols, A = d.num_rx_ant,
-                L = d.num_taps;
+  const int64_t B = d.batch, U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols, A = d.num_rx_ant;
   auto blocks = [](int64_t n) { return (unsigned)((n + 255) / 256); };
-  k_gen_params<<<(unsigned)B, 64, 0, st>>>(d, c, w, o.active, o.mcs_mask, o.mcs);
-  k_gen_taps<<<(unsigned)((B * U * A * L + kTapGroups - 1) / kTapGroups), kTapGroups * kT, 0, st>>>(d, c, w);
-  if (c.rx_mix) k_gen_mix<<<blocks(B * U * L * kT), 256, 0, st>>>(w, c.rx_mix, (int)A, (int)(L * kT), B * U * L * kT);
+  launch_taps(d, c, w, o, /*taps=*/!cir, st);      // a replayed channel keeps the active ports and the MCS
   GenDmrs dm{};
   if (dmrs) {
     dm.ptab = reinterpret_cast<float*>((char*)ws + own + (cfo ? cfo_workspace_bytes(d) : 0));
@@ -617,8 +645,15 @@ hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const n
                                         reinterpret_cast<double*>(wr.x), st))
       return e;
   }
-  k_gen_rx<<<dim3((unsigned)((F + FB - 1) / FB), (unsigned)B), FB * at, 0, st>>>(d, wr, FB, o.y, o.h, o.y_real,
-                                                                                 o.y_imag);
+  if (cir) {
+    char* cws = (char*)ws + own + (cfo ? cfo_workspace_bytes(d) : 0) + (dmrs ? dmrs_workspace_bytes(d) : 0);
+    if (hipError_t e = launch_cir_rx(d, *cir, reinterpret_cast<const double*>(wr.x), cws, o.y, o.h, o.y_real,
+                                     o.y_imag, st))
+      return e;
+  } else {
+    k_gen_rx<<<dim3((unsigned)((F + FB - 1) / FB), (unsigned)B), FB * at, 0, st>>>(d, wr, FB, o.y, o.h, o.y_real,
+                                                                                   o.y_imag);
+  }
   if (cfo && cfo->h_with_phase && o.h)
     if (hipError_t e = launch_cfo_h_phase(d, *cfo, o.h, st)) return e;
   if (dmrs) {      // one definition: the receiver-side estimator, on this call's y, pilot table and active mask

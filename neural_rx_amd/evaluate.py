@@ -380,7 +380,15 @@ def main(argv=None):
                          "JSON gains \"coded\" next to every result")
     ap.add_argument("-ldpc_iter", type=int, default=20, help="decoder iterations (1..100), with early stop")
     ap.add_argument("-ldpc_cn", default="boxplus", choices=["boxplus", "minsum"], help="check-node update")
-    ap.add_argument("-channel", default="iid", choices=["iid"] + list(SCENARIOS),
+    ap.add_argument("-cir_file", default=None, metavar="PATH",
+                    help="-channel dataset: the .npz of channel impulse responses to replay (cir.CIRDataset: 'a' "
+                         "complex64 [E, A, L, 1 | 14], 'tau' float32 [E, L] in seconds)")
+    ap.add_argument("-cir_select", default="random", choices=["random", "trajectory"],
+                    help="example of a (slot, user): any, or user u on the examples that are u modulo the users")
+    ap.add_argument("-cir_no_norm", action="store_true", help="keep the dataset's energy (default: unit mean energy "
+                                                              "per (slot, user) over the grid)")
+    ap.add_argument("-cir_f_zero", action="store_true", help="subcarrier 0 at frequency 0 (default: centred grid)")
+    ap.add_argument("-channel", default="iid", choices=["iid", "dataset"] + list(SCENARIOS),
                     help="iid: one delay / Doppler profile for every user and uncorrelated receive antennas; "
                          "double_tdl_low / double_tdl_high: the two-user profiles of the reference's evaluation "
                          "channel with gNB antenna correlation alpha = 0 / 0.9 (generator.scenario; needs a "
@@ -411,6 +419,10 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.cfo_hz is not None and a.cfo_ppm is not None:
         ap.error("-cfo_hz and -cfo_ppm are two ways to say the same thing: give one")
+    if (a.channel == "dataset") != (a.cir_file is not None):
+        ap.error("-channel dataset and -cir_file PATH go together")
+    if a.channel == "dataset" and a.rx_corr is not None:
+        ap.error("-rx_corr does not apply to -channel dataset: the dataset brings its own antenna structure")
 
     import torch
     import torch.distributed as dist
@@ -432,7 +444,12 @@ def main(argv=None):
     if a.dmrs_cover:
         params = dataclasses.replace(params, dmrs=DMRSPorts.for_config(cfg, u))
     params.num_active = a.num_tx_eval or u
-    if a.channel != "iid":
+    if a.channel == "dataset":
+        from .cir import CIRChannel, CIRDataset
+        params = dataclasses.replace(params, cir=CIRChannel(
+            CIRDataset.load(a.cir_file), select=a.cir_select, normalize=not a.cir_no_norm,
+            f_offset="zero" if a.cir_f_zero else "centered"))
+    elif a.channel != "iid":
         params = scenario(a.channel, params)
     if a.rx_corr is not None:
         params = dataclasses.replace(params, rx_corr=rx_correlation(params.num_rx_ant, a.rx_corr))
@@ -441,7 +458,8 @@ def main(argv=None):
     if cfo_hz is not None:
         params = dataclasses.replace(params, cfo_hz=cfo_hz, cfo_constant=a.cfo_constant, h_with_phase=True)
     # a correlated channel: the LMMSE estimator takes the spatial covariance unless -chest_2d keeps it out
-    chest3 = params.rx_corr is not None and not a.chest_2d
+    # (a replayed dataset counts as one: its antennas are as correlated as its geometry makes them)
+    chest3 = (params.rx_corr is not None or params.cir is not None) and not a.chest_2d
     systems = {n: "baseline_" + n for n in a.baselines}
     needs_h = {"perf_csi_lmmse", "lmmse_lmmse", "perf_csi_kbest", "lmmse_kbest"}
     gen = SlotGenerator(params, device=device, want_h=bool(needs_h & set(systems)) or a.soft_metrics)
@@ -509,6 +527,12 @@ def main(argv=None):
             d.update(channel=a.channel, user_profiles=[list(x) for x in params.profiles()],
                      rx_corr=a.rx_corr if a.rx_corr is not None else SCENARIOS.get(a.channel),
                      chest="lmmse3" if chest3 else "lmmse")
+        if params.cir is not None:
+            ds = params.cir.dataset
+            d.update(channel=a.channel, chest="lmmse3" if chest3 else "lmmse",
+                     cir=dict(file=a.cir_file, select=a.cir_select, normalize=not a.cir_no_norm,
+                              f_offset=params.cir.offset(params.num_subcarriers), num_examples=ds.num_examples,
+                              num_paths=ds.num_paths, num_time_steps=ds.num_time_steps))
         if cfo_hz is not None or a.cfo_comp:       # a run without either keeps the keys it always had
             d["cfo"] = dict(cfo_hz=cfo_hz, cfo_ppm=a.cfo_ppm, carrier_frequency_hz=a.carrier_frequency_hz,
                             constant=a.cfo_constant, comp=a.cfo_comp, h_with_phase=cfo_hz is not None,

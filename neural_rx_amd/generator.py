@@ -22,6 +22,10 @@ receiver-side remedy is ``neural_rx_amd/cfo.py``.
 ``GenParams.dmrs`` (an ``ls.DMRSPorts``) gives the ports orthogonal cover codes, through
 ``nrx_generate_slots_dmrs``: ``h_hat`` and the Aerial pilot list are then the despreading LS estimate
 of ``neural_rx_amd/ls.py`` and ``SlotBatch.pilots`` is the pilot table an external caller of it needs.
+
+``GenParams.cir`` (a ``cir.CIRChannel``) replaces the tapped-delay line by a replayed set of channel impulse
+responses, through ``nrx_generate_slots_cir``; ``SlotGenerator.export_taps`` writes the built-in channel in
+that format (``nrx_generate_taps``).
 """
 from __future__ import annotations
 
@@ -32,6 +36,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
+from .cir import SELECT, CIRChannel, CIRDataset
 from .config import NRXConfig, dmrs_symbols, get_config, user_cdm_groups
 from .ls import DMRSPorts
 
@@ -81,8 +86,19 @@ class GenParams:
     # cover-coded DMRS ports (ls.DMRSPorts; its cdm_group replaces the one above); None = the generator
     # without cover codes, where every port draws its own pilots
     dmrs: Optional[DMRSPorts] = None
+    # a replayed channel-impulse-response dataset (cir.CIRChannel) in place of the tapped-delay line; None =
+    # the built-in channel.  Excludes user_profiles / rx_corr: a dataset brings its own structure.
+    cir: Optional[CIRChannel] = None
 
     def __post_init__(self):
+        if self.cir is not None:
+            if self.user_profiles is not None or self.rx_corr is not None:
+                raise ValueError("a cir dataset is the channel: user_profiles and rx_corr do not apply to it")
+            if self.cir.dataset.num_rx_ant != self.num_rx_ant:
+                raise ValueError(f"the cir dataset has {self.cir.dataset.num_rx_ant} antennas, num_rx_ant is "
+                                 f"{self.num_rx_ant}")
+            if self.cir.select == "trajectory" and self.cir.dataset.num_examples < self.num_tx:
+                raise ValueError("select='trajectory' needs at least one example per user")
         if self.dmrs is not None:
             if self.dmrs.num_tx != self.num_tx:
                 raise ValueError(f"dmrs holds {self.dmrs.num_tx} ports, num_tx is {self.num_tx}")
@@ -277,11 +293,31 @@ class SlotGenerator:
                 m.focc[u], m.tocc[u] = params.dmrs.focc[u], params.dmrs.tocc[u]
             m.despread_f, m.despread_t = int(params.dmrs.despread_f), int(params.dmrs.despread_t)
             self._dmrs = m
+        self._cir = None
+        if params.cir is not None:
+            ch = params.cir
+            self._cir_data = ch.dataset.to(f"cuda:{device}")       # kept alive: the struct holds its pointers
+            r = _lib.nrx_gen_cir()
+            r.num_examples, r.num_paths = self._cir_data.num_examples, self._cir_data.num_paths
+            r.num_time_steps, r.select = self._cir_data.num_time_steps, SELECT[ch.select]
+            r.normalize, r.f_offset = int(bool(ch.normalize)), ch.offset(params.num_subcarriers)
+            torch = _torch()
+            self._cir_a = torch.view_as_real(self._cir_data.a.contiguous())
+            self._cir_tau = self._cir_data.tau.contiguous()
+            r.a, r.tau = self._cir_a.data_ptr(), self._cir_tau.data_ptr()
+            self._cir = r
 
     def workspace_bytes(self, batch: int) -> int:
         n = ctypes.c_size_t()
         d = self.p.desc(batch, 0.0)
-        if self._dmrs is not None:
+        ref = lambda s: ctypes.byref(s) if s is not None else None  # noqa: E731
+        if self._cir is not None:
+            if self._cir.select == SELECT["index"] and not self._cir.index:
+                # the size is no function of the index, which comes with every call: any address passes the check
+                self._cir.index = self._cir_tau.data_ptr()
+            _lib.check(self._lib.nrx_gen_workspace_size_cir(ctypes.byref(d), ref(self._cfo), ref(self._dmrs),
+                                                            ctypes.byref(self._cir), ctypes.byref(n)))
+        elif self._dmrs is not None:
             _lib.check(self._lib.nrx_gen_workspace_size_dmrs(
                 ctypes.byref(d), ctypes.byref(self._cfo) if self._cfo is not None else None, ctypes.byref(self._dmrs),
                 ctypes.byref(n)))
@@ -321,9 +357,10 @@ class SlotGenerator:
         return sb
 
     def __call__(self, batch: int, no: float, slot_offset: int = 0, stream=None, out: Optional[SlotBatch] = None,
-                 workspace=None) -> SlotBatch:
+                 workspace=None, cir_index=None) -> SlotBatch:
         """``workspace``: a uint8 device tensor of at least ``workspace_bytes(batch)`` bytes, any
-        content, to run this call in instead of the generator's own."""
+        content, to run this call in instead of the generator's own.  ``cir_index``: the examples
+        ``[batch, U]`` int32 (device) of a ``CIRChannel(select="index")``."""
         torch = _torch()
         sb = out if out is not None else self._alloc(batch)
         if workspace is not None:
@@ -348,6 +385,17 @@ class SlotGenerator:
             self._cfo.eps_out = ptr(sb.cfo_eps)
         if self._dmrs is not None:
             self._dmrs.pilots_out = ptr(sb.pilots)
+        if self._cir is not None:
+            if self._cir.select == SELECT["index"]:
+                if (cir_index is None or not cir_index.is_cuda or cir_index.dtype != torch.int32
+                        or tuple(cir_index.shape) != (batch, self.p.num_tx) or not cir_index.is_contiguous()):
+                    raise ValueError(f"select='index' needs cir_index: a contiguous int32 CUDA tensor {(batch, self.p.num_tx)}")
+                self._cir.index = cir_index.data_ptr()
+            ref = lambda s: ctypes.byref(s) if s is not None else None  # noqa: E731
+            _lib.check(self._lib.nrx_generate_slots_cir(
+                ctypes.byref(d), None, ref(self._cfo), ref(self._dmrs), ctypes.byref(self._cir), ctypes.byref(o),
+                ws.data_ptr(), ws.numel(), stream))
+        elif self._dmrs is not None:
             _lib.check(self._lib.nrx_generate_slots_dmrs(
                 ctypes.byref(d), ctypes.byref(self._chan) if self._chan is not None else None,
                 ctypes.byref(self._cfo) if self._cfo is not None else None, ctypes.byref(self._dmrs), ctypes.byref(o),
@@ -363,6 +411,29 @@ class SlotGenerator:
             _lib.check(self._lib.nrx_generate_slots(ctypes.byref(d), ctypes.byref(o), ws.data_ptr(), ws.numel(),
                                                     stream))
         return sb
+
+    def export_taps(self, batch: int, slot_offset: int = 0, stream=None) -> CIRDataset:
+        """The built-in channel of slots ``slot_offset .. slot_offset + batch - 1`` as a device ``CIRDataset``
+        (``nrx_generate_taps``): ``E = batch * U`` examples of ``num_taps`` paths and 14 time steps, example
+        ``b * U + u``, taps and delays rounded once to float32.  Replaying it with ``select="index"``,
+        ``f_offset="zero"`` and no normalisation gives this generator's channel again."""
+        torch = _torch()
+        if self._cir is not None:
+            raise ValueError("export_taps exports the built-in channel; this generator replays a dataset")
+        p, dev = self.p, f"cuda:{self.device}"
+        E = batch * p.num_tx
+        a = torch.empty((E, p.num_rx_ant, p.num_taps, NUM_SYMBOLS), dtype=torch.complex64, device=dev)
+        tau = torch.empty((E, p.num_taps), dtype=torch.float32, device=dev)
+        d = p.desc(batch, 0.0, slot_offset)
+        n = ctypes.c_size_t()
+        _lib.check(self._lib.nrx_gen_workspace_size(ctypes.byref(d), ctypes.byref(n)))
+        if self._ws is None or self._ws.numel() < n.value:
+            self._ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(a.device).cuda_stream
+        _lib.check(self._lib.nrx_generate_taps(ctypes.byref(d), ctypes.byref(self._chan) if self._chan is not None else None,
+                                               a.data_ptr(), tau.data_ptr(), self._ws.data_ptr(), self._ws.numel(), stream))
+        return CIRDataset(a, tau)
 
 
 def count_errors(llr, bits, active, mcs, mcs_bits: Sequence[int], dmrs_syms: Sequence[int], counts=None,
