@@ -3,6 +3,11 @@
 There is deliberately no fallback: if the HIP library is missing or fails to load,
 every engine entry point raises ``NRXLibraryError``.  Build it with
 ``python -m neural_rx_amd.build`` (or ``__graft_entry__.build()``).
+
+The ABI is stated once each way: the ``Structure`` classes (built from the field runs the
+descriptors share; tests/test_abi_layout.py holds every size and offset against the header) and
+``SIGNATURES``, which ``load()`` applies and ``EXPORTS`` lists (tests/test_abi.py holds it against
+the header).  What the wrappers do with them is in ``_call.py``.
 """
 from __future__ import annotations
 
@@ -23,23 +28,6 @@ NRX_PREC_F32X = 1
 PRECISIONS = {"f16": NRX_PREC_F16, "fp16": NRX_PREC_F16, "f32x": NRX_PREC_F32X,
               "parity": NRX_PREC_F32X}
 
-# Every exported symbol of include/nrx.h (checked by tests/test_abi.py).
-EXPORTS = [
-    "nrx_create", "nrx_weight_layout", "nrx_workspace_size", "nrx_forward", "nrx_destroy",
-    "nrx_compute_pe", "nrx_flops_per_re_user", "nrx_last_error", "nrx_api_version",
-    "nrx_profile_enable", "nrx_profile_read", "nrx_aerial_workspace_size", "nrx_forward_aerial",
-    "nrx_llr_demap", "nrx_gen_workspace_size", "nrx_generate_slots", "nrx_count_errors",
-    "nrx_workspace_size_ex", "nrx_forward_ex", "nrx_fused_status", "nrx_fused_config",
-    "nrx_build_id", "nrx_update_schedule", "nrx_lmmse_detect", "nrx_cov_workspace_size", "nrx_cov_accumulate",
-    "nrx_chest_lmmse", "nrx_chest_lin", "nrx_kbest_workspace_size", "nrx_kbest_detect",
-    "nrx_llr_stats_workspace_size", "nrx_llr_stats", "nrx_nmse_workspace_size", "nrx_chest_nmse",
-    "nrx_generate_slots_ex", "nrx_cov_space_workspace_size", "nrx_cov_space_accumulate",
-    "nrx_chest3_workspace_size", "nrx_chest_lmmse3", "nrx_aerial_preprocess",
-    "nrx_ldpc_create", "nrx_ldpc_destroy", "nrx_ldpc_workspace_size", "nrx_ldpc_decode", "nrx_ldpc_gather",
-    "nrx_ldpc_count", "nrx_gen_workspace_size_cfo", "nrx_generate_slots_cfo", "nrx_cfo_estimate", "nrx_cfo_rotate",
-    "nrx_ls_estimate", "nrx_gen_workspace_size_dmrs", "nrx_generate_slots_dmrs",
-    "nrx_gen_workspace_size_cir", "nrx_generate_slots_cir", "nrx_generate_taps",
-]
 # nrx_cfo_io.ref_mode (NRX_CFO_REF_*)
 CFO_REF_NEAREST_DMRS = 0
 CFO_REF_ZERO = 1
@@ -59,439 +47,219 @@ class NRXError(RuntimeError):
         self.code = code
 
 
+I32, F64, PTR = ctypes.c_int32, ctypes.c_double, ctypes.c_void_p
+
+
+def _i32(*names):
+    return [(n, I32) for n in names]
+
+
+def _f64(*names):
+    return [(n, F64) for n in names]
+
+
+def _ptr(*names):
+    return [(n, PTR) for n in names]
+
+
+# The field runs the descriptors of include/nrx.h share, under the same names everywhere (which is what lets
+# _call.fill_grid / fill_mcs / fill_dmrs take any of them): the grid, the grid with its antennas, the MCS
+# block, the DMRS block and the cover codes.
+GRID = _i32("batch", "num_tx", "num_subcarriers", "num_symbols")
+GRID_ANT = GRID + _i32("num_rx_ant")
+MCS = _i32("bits_stride", "num_mcs") + [("mcs_bits", I32 * 8)] + _i32("dmrs_symbol_mask")
+DMRS = _i32("num_dmrs_symbols") + [("dmrs_symbols", I32 * 4), ("cdm_group", I32 * 16)]
+COVERS = [("focc", I32 * 16), ("tocc", I32 * 16)] + _i32("despread_f", "despread_t")
+
+
 class nrx_desc(ctypes.Structure):
-    _fields_ = [
-        ("num_rx_ant", ctypes.c_int32),
-        ("d_s", ctypes.c_int32),
-        ("num_it", ctypes.c_int32),
-        ("num_mcs", ctypes.c_int32),
-        ("bits", ctypes.c_int32 * 8),
-        ("var_mcs_masking", ctypes.c_int32),
-        ("init_units", ctypes.c_int32 * 2),
-        ("agg_units", ctypes.c_int32),
-        ("state_units", ctypes.c_int32 * 2),
-        ("readout_units", ctypes.c_int32),
-        ("use_h_hat", ctypes.c_int32),
-    ]
+    _fields_ = (_i32("num_rx_ant", "d_s", "num_it", "num_mcs") + [("bits", I32 * 8)] + _i32("var_mcs_masking")
+                + [("init_units", I32 * 2)] + _i32("agg_units") + [("state_units", I32 * 2)]
+                + _i32("readout_units", "use_h_hat"))
 
 
 class nrx_shape(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-    ]
+    _fields_ = GRID
 
 
 class nrx_io(ctypes.Structure):
-    _fields_ = [
-        ("shape", nrx_shape),
-        ("num_it", ctypes.c_int32),
-        ("precision", ctypes.c_int32),
-        ("y", ctypes.c_void_p),
-        ("pe", ctypes.c_void_p),
-        ("h_hat", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("mcs_mask", ctypes.c_void_p),
-        ("llr", ctypes.c_void_p),
-        ("h_ref", ctypes.c_void_p),
-    ]
+    _fields_ = ([("shape", nrx_shape)] + _i32("num_it", "precision")
+                + _ptr("y", "pe", "h_hat", "active", "mcs_mask", "llr", "h_ref"))
 
 
 class nrx_aerial_io(ctypes.Structure):
-    _fields_ = [
-        ("shape", nrx_shape),
-        ("num_it", ctypes.c_int32),
-        ("precision", ctypes.c_int32),
-        ("num_dmrs_symbols", ctypes.c_int32),
-        ("num_dmrs_subcarriers", ctypes.c_int32),
-        ("y_real", ctypes.c_void_p),
-        ("y_imag", ctypes.c_void_p),
-        ("h_ls_real", ctypes.c_void_p),
-        ("h_ls_imag", ctypes.c_void_p),
-        ("dmrs_port_mask", ctypes.c_void_p),
-        ("dmrs_ofdm_pos", ctypes.c_void_p),
-        ("dmrs_subcarrier_pos", ctypes.c_void_p),
-        ("llr", ctypes.c_void_p),
-        ("h_hat", ctypes.c_void_p),
-    ]
+    _fields_ = ([("shape", nrx_shape)] + _i32("num_it", "precision", "num_dmrs_symbols", "num_dmrs_subcarriers")
+                + _ptr("y_real", "y_imag", "h_ls_real", "h_ls_imag", "dmrs_port_mask", "dmrs_ofdm_pos",
+                       "dmrs_subcarrier_pos", "llr", "h_hat"))
 
 
 class nrx_gen_desc(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("num_dmrs_symbols", ctypes.c_int32),
-        ("dmrs_symbols", ctypes.c_int32 * 4),
-        ("dmrs_symbol_mask", ctypes.c_int32),
-        ("cdm_group", ctypes.c_int32 * 16),
-        ("num_mcs", ctypes.c_int32),
-        ("mcs_bits", ctypes.c_int32 * 8),
-        ("mcs_of_user", ctypes.c_int32 * 16),
-        ("num_active", ctypes.c_int32),
-        ("num_taps", ctypes.c_int32),
-        ("num_sinusoids", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
-        ("max_delay_s", ctypes.c_double),
-        ("max_doppler_hz", ctypes.c_double),
-        ("subcarrier_spacing", ctypes.c_double),
-        ("no", ctypes.c_double),
-        ("seed", ctypes.c_uint64),
-        ("slot_offset", ctypes.c_int64),
-    ]
+    _fields_ = (GRID_ANT + _i32("num_dmrs_symbols") + [("dmrs_symbols", I32 * 4)] + _i32("dmrs_symbol_mask")
+                + [("cdm_group", I32 * 16)] + _i32("num_mcs") + [("mcs_bits", I32 * 8), ("mcs_of_user", I32 * 16)]
+                + _i32("num_active", "num_taps", "num_sinusoids", "pad_")
+                + _f64("max_delay_s", "max_doppler_hz", "subcarrier_spacing", "no")
+                + [("seed", ctypes.c_uint64), ("slot_offset", ctypes.c_int64)])
 
 
 class nrx_gen_out(ctypes.Structure):
-    _fields_ = [
-        ("y", ctypes.c_void_p),
-        ("h_hat", ctypes.c_void_p),
-        ("h", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("mcs_mask", ctypes.c_void_p),
-        ("mcs", ctypes.c_void_p),
-        ("bits", ctypes.c_void_p),
-        ("bits_stride", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
-        ("y_real", ctypes.c_void_p),
-        ("y_imag", ctypes.c_void_p),
-        ("h_ls_real", ctypes.c_void_p),
-        ("h_ls_imag", ctypes.c_void_p),
-    ]
+    _fields_ = (_ptr("y", "h_hat", "h", "active", "mcs_mask", "mcs", "bits") + _i32("bits_stride", "pad_")
+                + _ptr("y_real", "y_imag", "h_ls_real", "h_ls_imag"))
 
 
 class nrx_gen_chan(ctypes.Structure):
-    _fields_ = [
-        ("max_delay_s", ctypes.c_double * 16),
-        ("max_doppler_hz", ctypes.c_double * 16),
-        ("rx_mix", ctypes.c_void_p),
-    ]
+    _fields_ = [("max_delay_s", F64 * 16), ("max_doppler_hz", F64 * 16)] + _ptr("rx_mix")
 
 
 class nrx_gen_cfo(ctypes.Structure):
-    _fields_ = [
-        ("cfo_hz", ctypes.c_double * 16),
-        ("constant", ctypes.c_int32),
-        ("fft_size", ctypes.c_int32),
-        ("h_with_phase", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
-        ("eps_out", ctypes.c_void_p),
-    ]
+    _fields_ = [("cfo_hz", F64 * 16)] + _i32("constant", "fft_size", "h_with_phase", "pad_") + _ptr("eps_out")
 
 
 class nrx_cfo_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("num_dmrs_symbols", ctypes.c_int32),
-        ("dmrs_symbols", ctypes.c_int32 * 4),
-        ("cdm_group", ctypes.c_int32 * 16),
-        ("ref_mode", ctypes.c_int32),
-        ("sign", ctypes.c_int32),
-        ("h_in", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("eps", ctypes.c_void_p),
-        ("h_out", ctypes.c_void_p),
-    ]
+    _fields_ = GRID_ANT + DMRS + _i32("ref_mode", "sign") + _ptr("h_in", "active", "eps", "h_out")
 
 
 class nrx_ls_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("num_dmrs_symbols", ctypes.c_int32),
-        ("dmrs_symbols", ctypes.c_int32 * 4),
-        ("cdm_group", ctypes.c_int32 * 16),
-        ("focc", ctypes.c_int32 * 16),
-        ("tocc", ctypes.c_int32 * 16),
-        ("despread_f", ctypes.c_int32),
-        ("despread_t", ctypes.c_int32),
-        ("y", ctypes.c_void_p),
-        ("pilots", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("h_hat", ctypes.c_void_p),
-        ("h_ls_real", ctypes.c_void_p),
-        ("h_ls_imag", ctypes.c_void_p),
-    ]
+    _fields_ = GRID_ANT + DMRS + COVERS + _ptr("y", "pilots", "active", "h_hat", "h_ls_real", "h_ls_imag")
 
 
 class nrx_gen_dmrs(ctypes.Structure):
-    _fields_ = [
-        ("focc", ctypes.c_int32 * 16),
-        ("tocc", ctypes.c_int32 * 16),
-        ("despread_f", ctypes.c_int32),
-        ("despread_t", ctypes.c_int32),
-        ("pilots_out", ctypes.c_void_p),
-    ]
+    _fields_ = COVERS + _ptr("pilots_out")
 
 
 class nrx_gen_cir(ctypes.Structure):
-    _fields_ = [
-        ("num_examples", ctypes.c_int32),
-        ("num_paths", ctypes.c_int32),
-        ("num_time_steps", ctypes.c_int32),
-        ("select", ctypes.c_int32),
-        ("normalize", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
-        ("f_offset", ctypes.c_double),
-        ("a", ctypes.c_void_p),
-        ("tau", ctypes.c_void_p),
-        ("index", ctypes.c_void_p),
-    ]
+    _fields_ = (_i32("num_examples", "num_paths", "num_time_steps", "select", "normalize", "pad_") + _f64("f_offset")
+                + _ptr("a", "tau", "index"))
 
 
 class nrx_count_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_heads", ctypes.c_int32),
-        ("bits_stride", ctypes.c_int32),
-        ("num_mcs", ctypes.c_int32),
-        ("mcs_bits", ctypes.c_int32 * 8),
-        ("dmrs_symbol_mask", ctypes.c_int32),
-        ("llr", ctypes.c_void_p),
-        ("bits", ctypes.c_void_p),
-        ("mcs", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("counts", ctypes.c_void_p),
-    ]
+    _fields_ = GRID + _i32("num_heads") + MCS + _ptr("llr", "bits", "mcs", "active", "counts")
 
 
 class nrx_lmmse_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("bits_stride", ctypes.c_int32),
-        ("num_mcs", ctypes.c_int32),
-        ("mcs_bits", ctypes.c_int32 * 8),
-        ("dmrs_symbol_mask", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
-        ("no", ctypes.c_double),
-        ("err_var", ctypes.c_double),
-        ("y", ctypes.c_void_p),
-        ("h", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("mcs", ctypes.c_void_p),
-        ("llr", ctypes.c_void_p),
-    ]
+    _fields_ = GRID_ANT + MCS + _i32("pad_") + _f64("no", "err_var") + _ptr("y", "h", "active", "mcs", "llr")
 
 
 class nrx_kbest_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("bits_stride", ctypes.c_int32),
-        ("num_mcs", ctypes.c_int32),
-        ("mcs_bits", ctypes.c_int32 * 8),
-        ("dmrs_symbol_mask", ctypes.c_int32),
-        ("k", ctypes.c_int32),
-        ("no", ctypes.c_double),
-        ("err_var", ctypes.c_double),
-        ("llr_clip", ctypes.c_double),
-        ("y", ctypes.c_void_p),
-        ("h", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("mcs", ctypes.c_void_p),
-        ("llr", ctypes.c_void_p),
-    ]
+    _fields_ = (GRID_ANT + MCS + _i32("k") + _f64("no", "err_var", "llr_clip")
+                + _ptr("y", "h", "active", "mcs", "llr"))
 
 
 class nrx_cov_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
-        ("h", ctypes.c_void_p),
-        ("acc", ctypes.c_void_p),
-    ]
+    _fields_ = GRID_ANT + _i32("pad_") + _ptr("h", "acc")
 
 
 class nrx_cov_space_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
-        ("h", ctypes.c_void_p),
-        ("acc", ctypes.c_void_p),
-    ]
+    _fields_ = nrx_cov_io._fields_
 
 
 class nrx_chest_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("num_dmrs_symbols", ctypes.c_int32),
-        ("dmrs_symbols", ctypes.c_int32 * 4),
-        ("cdm_group", ctypes.c_int32 * 16),
-        ("no", ctypes.c_double),
-        ("h_hat", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("filt", ctypes.c_void_p),
-        ("tcoef", ctypes.c_void_p),
-        ("vconj", ctypes.c_void_p),
-        ("h_out", ctypes.c_void_p),
-    ]
+    _fields_ = GRID_ANT + DMRS + _f64("no") + _ptr("h_hat", "active", "filt", "tcoef", "vconj", "h_out")
 
 
 class nrx_chest3_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("num_dmrs_symbols", ctypes.c_int32),
-        ("dmrs_symbols", ctypes.c_int32 * 4),
-        ("cdm_group", ctypes.c_int32 * 16),
-        ("no", ctypes.c_double),
-        ("h_hat", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("qh", ctypes.c_void_p),
-        ("gf", ctypes.c_void_p),
-        ("nu", ctypes.c_void_p),
-        ("tcoef", ctypes.c_void_p),
-        ("vconj", ctypes.c_void_p),
-        ("lam", ctypes.c_void_p),
-        ("vs", ctypes.c_void_p),
-        ("mu", ctypes.c_void_p),
-        ("h_out", ctypes.c_void_p),
-    ]
+    _fields_ = (GRID_ANT + DMRS + _f64("no")
+                + _ptr("h_hat", "active", "qh", "gf", "nu", "tcoef", "vconj", "lam", "vs", "mu", "h_out"))
 
 
 class nrx_llr_stats_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_heads", ctypes.c_int32),
-        ("bits_stride", ctypes.c_int32),
-        ("num_mcs", ctypes.c_int32),
-        ("mcs_bits", ctypes.c_int32 * 8),
-        ("dmrs_symbol_mask", ctypes.c_int32),
-        ("num_scales", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
-        ("scales", ctypes.c_double * 16),
-        ("llr", ctypes.c_void_p),
-        ("bits", ctypes.c_void_p),
-        ("mcs", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("loss", ctypes.c_void_p),
-        ("cnt", ctypes.c_void_p),
-        ("nonfinite", ctypes.c_void_p),
-    ]
+    _fields_ = (GRID + _i32("num_heads") + MCS + _i32("num_scales", "pad_") + [("scales", F64 * 16)]
+                + _ptr("llr", "bits", "mcs", "active", "loss", "cnt", "nonfinite"))
 
 
 class nrx_nmse_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_rx_ant", ctypes.c_int32),
-        ("symbol_mask", ctypes.c_int32),
-        ("h_est", ctypes.c_void_p),
-        ("h_true", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("err", ctypes.c_void_p),
-        ("ref", ctypes.c_void_p),
-        ("items", ctypes.c_void_p),
-    ]
+    _fields_ = GRID_ANT + _i32("symbol_mask") + _ptr("h_est", "h_true", "active", "err", "ref", "items")
 
 
 class nrx_ldpc_code(ctypes.Structure):
-    _fields_ = [
-        ("mb", ctypes.c_int32),
-        ("nb", ctypes.c_int32),
-        ("z", ctypes.c_int32),
-        ("kb", ctypes.c_int32),
-        ("shifts", ctypes.c_void_p),
-    ]
+    _fields_ = _i32("mb", "nb", "z", "kb") + _ptr("shifts")
 
 
 class nrx_ldpc_io(ctypes.Structure):
-    _fields_ = [
-        ("num_cw", ctypes.c_int32),
-        ("num_iter", ctypes.c_int32),
-        ("cn_type", ctypes.c_int32),
-        ("early_stop", ctypes.c_int32),
-        ("ms_scale", ctypes.c_float),
-        ("llr_clip", ctypes.c_float),
-        ("llr_in", ctypes.c_void_p),
-        ("skip", ctypes.c_void_p),
-        ("hard", ctypes.c_void_p),
-        ("app", ctypes.c_void_p),
-        ("iters", ctypes.c_void_p),
-        ("parity_ok", ctypes.c_void_p),
-    ]
+    _fields_ = (_i32("num_cw", "num_iter", "cn_type", "early_stop")
+                + [("ms_scale", ctypes.c_float), ("llr_clip", ctypes.c_float)]
+                + _ptr("llr_in", "skip", "hard", "app", "iters", "parity_ok"))
 
 
 class nrx_ldpc_gather_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_subcarriers", ctypes.c_int32),
-        ("num_symbols", ctypes.c_int32),
-        ("num_heads", ctypes.c_int32),
-        ("bits_stride", ctypes.c_int32),
-        ("num_mcs", ctypes.c_int32),
-        ("mcs_bits", ctypes.c_int32 * 8),
-        ("dmrs_symbol_mask", ctypes.c_int32),
-        ("num_cw_per_user", ctypes.c_int32),
-        ("n_tx", ctypes.c_int32),
-        ("n", ctypes.c_int32),
-        ("llr", ctypes.c_void_p),
-        ("bits", ctypes.c_void_p),
-        ("mcs", ctypes.c_void_p),
-        ("active", ctypes.c_void_p),
-        ("tx_col", ctypes.c_void_p),
-        ("col_prior", ctypes.c_void_p),
-        ("llr_in", ctypes.c_void_p),
-        ("skip", ctypes.c_void_p),
-    ]
+    _fields_ = (GRID + _i32("num_heads") + MCS + _i32("num_cw_per_user", "n_tx", "n")
+                + _ptr("llr", "bits", "mcs", "active", "tx_col", "col_prior", "llr_in", "skip"))
 
 
 class nrx_ldpc_count_io(ctypes.Structure):
-    _fields_ = [
-        ("batch", ctypes.c_int32),
-        ("num_tx", ctypes.c_int32),
-        ("num_cw_per_user", ctypes.c_int32),
-        ("n", ctypes.c_int32),
-        ("num_info", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
-        ("hard", ctypes.c_void_p),
-        ("skip", ctypes.c_void_p),
-        ("iters", ctypes.c_void_p),
-        ("counts", ctypes.c_void_p),
-        ("iter_counts", ctypes.c_void_p),
-    ]
+    _fields_ = (_i32("batch", "num_tx", "num_cw_per_user", "n", "num_info", "pad_")
+                + _ptr("hard", "skip", "iters", "counts", "iter_counts"))
 
+
+def _signatures():
+    c = ctypes
+    P = c.POINTER
+    RC, I, V, Z, PZ = c.c_int, c.c_int32, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)
+    desc, gen, chan, cfo, dmrs, cir, out = (P(nrx_desc), P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo),
+                                            P(nrx_gen_dmrs), P(nrx_gen_cir), P(nrx_gen_out))
+    run = [V, Z, V]          # workspace, workspace_bytes, stream
+    return {
+        "nrx_create": (RC, [desc, P(V), P(c.c_int64), I, I, P(V)]),
+        "nrx_weight_layout": (RC, [desc, P(I), P(c.c_int64), I]),
+        "nrx_workspace_size": (RC, [V, P(nrx_shape), I, PZ]),
+        "nrx_forward": (RC, [V, P(nrx_io)] + run),
+        "nrx_workspace_size_ex": (RC, [V, P(nrx_shape), I, I, PZ]),
+        "nrx_forward_ex": (RC, [V, P(nrx_io), I, V] + run),
+        "nrx_destroy": (None, [V]),
+        "nrx_compute_pe": (RC, [I, I, I, P(I), I, P(I), P(c.c_float)]),
+        "nrx_flops_per_re_user": (c.c_double, [desc, I]),
+        "nrx_last_error": (c.c_char_p, []),
+        "nrx_api_version": (I, []),
+        "nrx_build_id": (c.c_char_p, []),
+        "nrx_profile_enable": (RC, [V, I]),
+        "nrx_profile_read": (RC, [V, I, P(c.c_int64), P(c.c_double)]),
+        "nrx_fused_status": (RC, [V, V, I]),
+        "nrx_fused_config": (RC, [V, I, I, I]),
+        "nrx_update_schedule": (RC, [V, I]),
+        "nrx_aerial_workspace_size": (RC, [V, P(nrx_aerial_io), PZ]),
+        "nrx_forward_aerial": (RC, [V, P(nrx_aerial_io)] + run),
+        "nrx_aerial_preprocess": (RC, [V, P(nrx_aerial_io), V, V, V, V, V]),
+        "nrx_llr_demap": (RC, [V, I, I, I, I, I, I, V, I, V, V]),
+        "nrx_gen_workspace_size": (RC, [gen, PZ]),
+        "nrx_generate_slots": (RC, [gen, out] + run),
+        "nrx_generate_slots_ex": (RC, [gen, chan, out] + run),
+        "nrx_gen_workspace_size_cfo": (RC, [gen, cfo, PZ]),
+        "nrx_generate_slots_cfo": (RC, [gen, chan, cfo, out] + run),
+        "nrx_gen_workspace_size_dmrs": (RC, [gen, cfo, dmrs, PZ]),
+        "nrx_generate_slots_dmrs": (RC, [gen, chan, cfo, dmrs, out] + run),
+        "nrx_gen_workspace_size_cir": (RC, [gen, cfo, dmrs, cir, PZ]),
+        "nrx_generate_slots_cir": (RC, [gen, chan, cfo, dmrs, cir, out] + run),
+        "nrx_generate_taps": (RC, [gen, chan, V, V] + run),
+        "nrx_count_errors": (RC, [P(nrx_count_io), V]),
+        "nrx_cfo_estimate": (RC, [P(nrx_cfo_io), V]),
+        "nrx_cfo_rotate": (RC, [P(nrx_cfo_io), V]),
+        "nrx_ls_estimate": (RC, [P(nrx_ls_io), V]),
+        "nrx_lmmse_detect": (RC, [P(nrx_lmmse_io), V]),
+        "nrx_kbest_workspace_size": (RC, [P(nrx_kbest_io), PZ]),
+        "nrx_kbest_detect": (RC, [P(nrx_kbest_io)] + run),
+        "nrx_cov_workspace_size": (RC, [P(nrx_cov_io), PZ]),
+        "nrx_cov_accumulate": (RC, [P(nrx_cov_io)] + run),
+        "nrx_cov_space_workspace_size": (RC, [P(nrx_cov_space_io), PZ]),
+        "nrx_cov_space_accumulate": (RC, [P(nrx_cov_space_io)] + run),
+        "nrx_chest_lmmse": (RC, [P(nrx_chest_io), V]),
+        "nrx_chest_lin": (RC, [P(nrx_chest_io), V]),
+        "nrx_chest3_workspace_size": (RC, [P(nrx_chest3_io), PZ]),
+        "nrx_chest_lmmse3": (RC, [P(nrx_chest3_io)] + run),
+        "nrx_llr_stats_workspace_size": (RC, [P(nrx_llr_stats_io), PZ]),
+        "nrx_llr_stats": (RC, [P(nrx_llr_stats_io)] + run),
+        "nrx_nmse_workspace_size": (RC, [P(nrx_nmse_io), PZ]),
+        "nrx_chest_nmse": (RC, [P(nrx_nmse_io)] + run),
+        "nrx_ldpc_create": (RC, [P(nrx_ldpc_code), I, P(V)]),
+        "nrx_ldpc_destroy": (None, [V]),
+        "nrx_ldpc_workspace_size": (RC, [V, P(nrx_ldpc_io), PZ]),
+        "nrx_ldpc_decode": (RC, [V, P(nrx_ldpc_io)] + run),
+        "nrx_ldpc_gather": (RC, [P(nrx_ldpc_gather_io), V]),
+        "nrx_ldpc_count": (RC, [P(nrx_ldpc_count_io), V]),
+    }
+
+
+# {export: (restype, argtypes)}: every symbol of include/nrx.h (checked by tests/test_abi.py)
+SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)
 
 # subcarriers per work item of nrx_llr_stats / nrx_chest_nmse (NRX_SOFT_STRIP of include/nrx.h)
 SOFT_STRIP = 16
@@ -519,131 +287,9 @@ def load(path: str = LIB_PATH):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the box
         raise NRXLibraryError(f"failed to load {path}: {e}") from e
-    c = ctypes
-    P = c.POINTER
-    lib.nrx_create.argtypes = [P(nrx_desc), P(c.c_void_p), P(c.c_int64), c.c_int32, c.c_int32,
-                               P(c.c_void_p)]
-    lib.nrx_create.restype = c.c_int
-    lib.nrx_weight_layout.argtypes = [P(nrx_desc), P(c.c_int32), P(c.c_int64), c.c_int32]
-    lib.nrx_weight_layout.restype = c.c_int
-    lib.nrx_workspace_size.argtypes = [c.c_void_p, P(nrx_shape), c.c_int32, P(c.c_size_t)]
-    lib.nrx_workspace_size.restype = c.c_int
-    lib.nrx_forward.argtypes = [c.c_void_p, P(nrx_io), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_forward.restype = c.c_int
-    lib.nrx_workspace_size_ex.argtypes = [c.c_void_p, P(nrx_shape), c.c_int32, c.c_int32, P(c.c_size_t)]
-    lib.nrx_workspace_size_ex.restype = c.c_int
-    lib.nrx_forward_ex.argtypes = [c.c_void_p, P(nrx_io), c.c_int32, c.c_void_p, c.c_void_p, c.c_size_t,
-                                   c.c_void_p]
-    lib.nrx_forward_ex.restype = c.c_int
-    lib.nrx_destroy.argtypes = [c.c_void_p]
-    lib.nrx_destroy.restype = None
-    lib.nrx_compute_pe.argtypes = [c.c_int32, c.c_int32, c.c_int32, P(c.c_int32), c.c_int32,
-                                   P(c.c_int32), P(c.c_float)]
-    lib.nrx_compute_pe.restype = c.c_int
-    lib.nrx_flops_per_re_user.argtypes = [P(nrx_desc), c.c_int32]
-    lib.nrx_flops_per_re_user.restype = c.c_double
-    lib.nrx_last_error.argtypes = []
-    lib.nrx_last_error.restype = c.c_char_p
-    lib.nrx_profile_enable.argtypes = [c.c_void_p, c.c_int32]
-    lib.nrx_profile_enable.restype = c.c_int
-    lib.nrx_profile_read.argtypes = [c.c_void_p, c.c_int32, P(c.c_int64), P(c.c_double)]
-    lib.nrx_profile_read.restype = c.c_int
-    lib.nrx_fused_status.argtypes = [c.c_void_p, c.c_void_p, c.c_int32]
-    lib.nrx_fused_status.restype = c.c_int
-    lib.nrx_fused_config.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32]
-    lib.nrx_fused_config.restype = c.c_int
-    lib.nrx_aerial_workspace_size.argtypes = [c.c_void_p, P(nrx_aerial_io), P(c.c_size_t)]
-    lib.nrx_aerial_workspace_size.restype = c.c_int
-    lib.nrx_forward_aerial.argtypes = [c.c_void_p, P(nrx_aerial_io), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_forward_aerial.restype = c.c_int
-    lib.nrx_aerial_preprocess.argtypes = [c.c_void_p, P(nrx_aerial_io), c.c_void_p, c.c_void_p, c.c_void_p,
-                                          c.c_void_p, c.c_void_p]
-    lib.nrx_aerial_preprocess.restype = c.c_int
-    lib.nrx_llr_demap.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.c_int32,
-                                  c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p]
-    lib.nrx_llr_demap.restype = c.c_int
-    lib.nrx_gen_workspace_size.argtypes = [P(nrx_gen_desc), P(c.c_size_t)]
-    lib.nrx_gen_workspace_size.restype = c.c_int
-    lib.nrx_generate_slots.argtypes = [P(nrx_gen_desc), P(nrx_gen_out), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_generate_slots.restype = c.c_int
-    lib.nrx_generate_slots_ex.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_out), c.c_void_p, c.c_size_t,
-                                          c.c_void_p]
-    lib.nrx_generate_slots_ex.restype = c.c_int
-    lib.nrx_gen_workspace_size_cfo.argtypes = [P(nrx_gen_desc), P(nrx_gen_cfo), P(c.c_size_t)]
-    lib.nrx_gen_workspace_size_cfo.restype = c.c_int
-    lib.nrx_generate_slots_cfo.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo), P(nrx_gen_out), c.c_void_p,
-                                           c.c_size_t, c.c_void_p]
-    lib.nrx_generate_slots_cfo.restype = c.c_int
-    lib.nrx_cfo_estimate.argtypes = [P(nrx_cfo_io), c.c_void_p]
-    lib.nrx_cfo_estimate.restype = c.c_int
-    lib.nrx_cfo_rotate.argtypes = [P(nrx_cfo_io), c.c_void_p]
-    lib.nrx_cfo_rotate.restype = c.c_int
-    lib.nrx_ls_estimate.argtypes = [P(nrx_ls_io), c.c_void_p]
-    lib.nrx_ls_estimate.restype = c.c_int
-    lib.nrx_gen_workspace_size_dmrs.argtypes = [P(nrx_gen_desc), P(nrx_gen_cfo), P(nrx_gen_dmrs), P(c.c_size_t)]
-    lib.nrx_gen_workspace_size_dmrs.restype = c.c_int
-    lib.nrx_generate_slots_dmrs.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo), P(nrx_gen_dmrs),
-                                            P(nrx_gen_out), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_generate_slots_dmrs.restype = c.c_int
-    lib.nrx_gen_workspace_size_cir.argtypes = [P(nrx_gen_desc), P(nrx_gen_cfo), P(nrx_gen_dmrs), P(nrx_gen_cir),
-                                               P(c.c_size_t)]
-    lib.nrx_gen_workspace_size_cir.restype = c.c_int
-    lib.nrx_generate_slots_cir.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo), P(nrx_gen_dmrs),
-                                           P(nrx_gen_cir), P(nrx_gen_out), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_generate_slots_cir.restype = c.c_int
-    lib.nrx_generate_taps.argtypes = [P(nrx_gen_desc), P(nrx_gen_chan), c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t,
-                                      c.c_void_p]
-    lib.nrx_generate_taps.restype = c.c_int
-    lib.nrx_cov_space_workspace_size.argtypes = [P(nrx_cov_space_io), P(c.c_size_t)]
-    lib.nrx_cov_space_workspace_size.restype = c.c_int
-    lib.nrx_cov_space_accumulate.argtypes = [P(nrx_cov_space_io), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_cov_space_accumulate.restype = c.c_int
-    lib.nrx_count_errors.argtypes = [P(nrx_count_io), c.c_void_p]
-    lib.nrx_count_errors.restype = c.c_int
-    lib.nrx_lmmse_detect.argtypes = [P(nrx_lmmse_io), c.c_void_p]
-    lib.nrx_lmmse_detect.restype = c.c_int
-    lib.nrx_kbest_workspace_size.argtypes = [P(nrx_kbest_io), P(c.c_size_t)]
-    lib.nrx_kbest_workspace_size.restype = c.c_int
-    lib.nrx_kbest_detect.argtypes = [P(nrx_kbest_io), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_kbest_detect.restype = c.c_int
-    lib.nrx_cov_workspace_size.argtypes = [P(nrx_cov_io), P(c.c_size_t)]
-    lib.nrx_cov_workspace_size.restype = c.c_int
-    lib.nrx_cov_accumulate.argtypes = [P(nrx_cov_io), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_cov_accumulate.restype = c.c_int
-    lib.nrx_chest_lmmse.argtypes = [P(nrx_chest_io), c.c_void_p]
-    lib.nrx_chest_lmmse.restype = c.c_int
-    lib.nrx_chest_lin.argtypes = [P(nrx_chest_io), c.c_void_p]
-    lib.nrx_chest_lin.restype = c.c_int
-    lib.nrx_chest3_workspace_size.argtypes = [P(nrx_chest3_io), P(c.c_size_t)]
-    lib.nrx_chest3_workspace_size.restype = c.c_int
-    lib.nrx_chest_lmmse3.argtypes = [P(nrx_chest3_io), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_chest_lmmse3.restype = c.c_int
-    lib.nrx_llr_stats_workspace_size.argtypes = [P(nrx_llr_stats_io), P(c.c_size_t)]
-    lib.nrx_llr_stats_workspace_size.restype = c.c_int
-    lib.nrx_llr_stats.argtypes = [P(nrx_llr_stats_io), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_llr_stats.restype = c.c_int
-    lib.nrx_nmse_workspace_size.argtypes = [P(nrx_nmse_io), P(c.c_size_t)]
-    lib.nrx_nmse_workspace_size.restype = c.c_int
-    lib.nrx_chest_nmse.argtypes = [P(nrx_nmse_io), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_chest_nmse.restype = c.c_int
-    lib.nrx_ldpc_create.argtypes = [P(nrx_ldpc_code), c.c_int32, P(c.c_void_p)]
-    lib.nrx_ldpc_create.restype = c.c_int
-    lib.nrx_ldpc_destroy.argtypes = [c.c_void_p]
-    lib.nrx_ldpc_destroy.restype = None
-    lib.nrx_ldpc_workspace_size.argtypes = [c.c_void_p, P(nrx_ldpc_io), P(c.c_size_t)]
-    lib.nrx_ldpc_workspace_size.restype = c.c_int
-    lib.nrx_ldpc_decode.argtypes = [c.c_void_p, P(nrx_ldpc_io), c.c_void_p, c.c_size_t, c.c_void_p]
-    lib.nrx_ldpc_decode.restype = c.c_int
-    lib.nrx_ldpc_gather.argtypes = [P(nrx_ldpc_gather_io), c.c_void_p]
-    lib.nrx_ldpc_gather.restype = c.c_int
-    lib.nrx_ldpc_count.argtypes = [P(nrx_ldpc_count_io), c.c_void_p]
-    lib.nrx_ldpc_count.restype = c.c_int
-    lib.nrx_api_version.argtypes = []
-    lib.nrx_api_version.restype = c.c_int32
-    lib.nrx_update_schedule.argtypes = [c.c_void_p, c.c_int32]
-    lib.nrx_update_schedule.restype = c.c_int
-    lib.nrx_build_id.argtypes = []
-    lib.nrx_build_id.restype = c.c_char_p
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

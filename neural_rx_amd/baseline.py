@@ -21,72 +21,123 @@ is therefore meaningful for at most one active port per CDM group (U <= 2 with g
 """
 from __future__ import annotations
 
-import ctypes
-from typing import Optional, Sequence
+from typing import Sequence
 
 from . import _lib
+from ._call import fill_grid, fill_mcs, ptr, ref, require, stream_of, torch as _torch
 from .generator import NUM_SYMBOLS, GenParams, SlotBatch
 
 SYSTEMS = ("baseline_lsnn_lmmse", "baseline_perf_csi_lmmse")
 MAX_TX = 8
 
 
-def _torch():
-    import torch
-    return torch
+class Detector:
+    """What the detectors share: ``det(y, h, active, mcs, mcs_bits, no, dmrs_symbols) -> llr
+    [1, B, U, F, T, max(mcs_bits)]`` on y [B, F, T, 2A], h [B, U, F, T, 2A] (an estimate or the true
+    channel), active [B, U] f32, mcs [B, U] u8 or None (= MCS 0): contiguous tensors on the
+    detector's device, in the generator's layouts.  ``err_var`` is added to ``no`` (channel-estimation
+    error power seen at a data RE).  Every element of ``out`` is written, so a reused buffer needs no
+    clearing.  A subclass names its descriptor (``IO``), adds its own fields and makes the call."""
 
-
-class LMMSEDetector:
-    """``det(y, h, active, mcs, mcs_bits, no, dmrs_symbols) -> llr [1, B, U, F, T, max(mcs_bits)]``.
-
-    y [B, F, T, 2A], h [B, U, F, T, 2A] (an estimate or the true channel), active [B, U] f32,
-    mcs [B, U] u8 or None (= MCS 0): contiguous device tensors in the generator's layouts.
-    ``err_var`` is added to ``no`` (channel-estimation error power seen at a data RE).  Every
-    element of ``out`` is written, so a reused buffer needs no clearing."""
+    IO = None
 
     def __init__(self, device: int = 0):
         self.device = device
         self._lib = _lib.load()
 
-    def __call__(self, y, h, active, mcs, mcs_bits: Sequence[int], no: float, dmrs_symbols: Sequence[int],
-                 err_var: float = 0.0, out=None, stream=None):
+    def _io(self, y, h, active, mcs, mcs_bits, no, dmrs_symbols, err_var, out):
+        """the arguments checked and the part of the descriptor that ``nrx_lmmse_io`` and
+        ``nrx_kbest_io`` share filled: ``(io, out)``"""
         torch = _torch()
         B, U, F, T, A2 = h.shape
-        if h.device != torch.device(f"cuda:{self.device}"):
-            raise ValueError(f"tensors must be on cuda:{self.device}, h is on {h.device}")
-        if tuple(y.shape) != (B, F, T, A2):
-            raise ValueError(f"y must be {(B, F, T, A2)}, got {tuple(y.shape)}")
-        if tuple(active.shape) != (B, U) or (mcs is not None and tuple(mcs.shape) != (B, U)):
-            raise ValueError(f"active / mcs must be {(B, U)}")
-        if y.dtype != torch.float32 or h.dtype != torch.float32 or active.dtype != torch.float32:
-            raise ValueError("y, h and active must be float32")
-        if mcs is not None and mcs.dtype != torch.uint8:
-            raise ValueError("mcs must be uint8")
-        for t in (y, h, active, mcs):
-            if t is not None and not t.is_contiguous():
-                raise ValueError("tensors must be contiguous")
+        dev = torch.device("cuda", self.device)
+        require("h", h, dtype=torch.float32, device=dev)
+        require("y", y, (B, F, T, A2), torch.float32, dev)
+        require("active", active, (B, U), torch.float32, dev)
+        if mcs is not None:
+            require("mcs", mcs, (B, U), torch.uint8, dev)
         bs = max(mcs_bits)
         if out is None:
             out = torch.empty((1, B, U, F, T, bs), dtype=torch.float32, device=h.device)
         elif tuple(out.shape[:5]) != (1, B, U, F, T) or out.shape[5] < bs or out.dtype != torch.float32 \
                 or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous float32 {(1, B, U, F, T)} x >= {bs}")
-        io = _lib.nrx_lmmse_io()
-        io.batch, io.num_tx, io.num_subcarriers, io.num_symbols = B, U, F, T
-        io.num_rx_ant, io.bits_stride, io.num_mcs = A2 // 2, out.shape[5], len(mcs_bits)
-        for m, b in enumerate(mcs_bits[:8]):
-            io.mcs_bits[m] = b
-        io.dmrs_symbol_mask = sum(1 << t for t in dmrs_symbols)
+        io = self.IO()
+        fill_grid(io, B, U, F, T, A2 // 2)
+        fill_mcs(io, mcs_bits, dmrs_symbols, bits_stride=out.shape[5])
         io.no, io.err_var = float(no), float(err_var)
-        io.y, io.h, io.active, io.llr = y.data_ptr(), h.data_ptr(), active.data_ptr(), out.data_ptr()
-        io.mcs = mcs.data_ptr() if mcs is not None else None
-        if stream is None:
-            stream = torch.cuda.current_stream(h.device).cuda_stream
-        _lib.check(self._lib.nrx_lmmse_detect(ctypes.byref(io), stream))
+        io.y, io.h, io.active, io.mcs, io.llr = ptr(y), ptr(h), ptr(active), ptr(mcs), ptr(out)
+        return io, out
+
+
+class LMMSEDetector(Detector):
+    """The LMMSE detector with max-log demapping (``nrx_lmmse_detect``); arguments in ``Detector``."""
+
+    IO = _lib.nrx_lmmse_io
+
+    def __call__(self, y, h, active, mcs, mcs_bits: Sequence[int], no: float, dmrs_symbols: Sequence[int],
+                 err_var: float = 0.0, out=None, stream=None):
+        io, out = self._io(y, h, active, mcs, mcs_bits, no, dmrs_symbols, err_var, out)
+        _lib.check(self._lib.nrx_lmmse_detect(ref(io), stream_of(h, stream)))
         return out
 
 
-class BaselineReceiver:
+class Receiver:
+    """What the baseline receivers share: ``rx(sb, no, out=None, stream=None) -> llr [1, B, U, F, T,
+    bits_max]`` (``out=None``: the receiver's own buffer, overwritten by the next call of the same batch
+    size).  With perfect CSI the detector gets ``sb.h``; otherwise a subclass says which estimate
+    (``_estimate``), kept in ``last_h``, and with which ``err_var``."""
+
+    SYSTEMS = ()
+    DETECTOR = LMMSEDetector
+    KERNEL = "LMMSE kernel is"
+    perfect_csi = False
+
+    def __init__(self, system: str, params: GenParams, device: int = 0, **detector_kw):
+        if system not in self.SYSTEMS:
+            raise ValueError(f"system must be one of {self.SYSTEMS}, got {system!r}")
+        if params.num_tx > MAX_TX:
+            raise ValueError(f"the {self.KERNEL} built for at most {MAX_TX} users, got {params.num_tx}")
+        self.system = system
+        self.p = params
+        self.detector = self.DETECTOR(device)
+        self._detector_kw = detector_kw     # what the subclass passes to every detector call
+        self._out = None
+        # the channel estimate the last call detected with; None with perfect CSI
+        self.last_h = None
+
+    @property
+    def _num_active(self) -> int:
+        return self.p.num_tx if self.p.num_active is None else self.p.num_active
+
+    @property
+    def contaminated(self) -> bool:
+        """the LS estimates can be pilot-contaminated: two active ports may share a CDM group"""
+        groups = list(self.p.cdm_group[:self.p.num_tx])
+        return not self.perfect_csi and self.p.dmrs is None and self._num_active > 1 \
+            and max(groups.count(g) for g in set(groups)) > 1
+
+    def __call__(self, sb: SlotBatch, no: float, out=None, stream=None):
+        p = self.p
+        ev = self.err_var(no)
+        if self.perfect_csi:
+            h = sb.h
+            if h is None:
+                raise ValueError(f"{self.system} needs the true channel: SlotGenerator(want_h=True)")
+        else:
+            h = self.last_h = self._estimate(sb, no, stream)
+        if out is None:
+            B = h.shape[0]
+            if self._out is None or self._out.shape[1] != B:
+                torch = _torch()
+                self._out = torch.empty((1, B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS, p.bits_max),
+                                        dtype=torch.float32, device=h.device)
+            out = self._out
+        return self.detector(sb.y, h, sb.active, sb.mcs, p.mcs_bits, no, p.dmrs_symbols, err_var=ev, out=out,
+                             stream=stream, **self._detector_kw)
+
+
+class BaselineReceiver(Receiver):
     """``rx(sb, no) -> llr``: a ``SlotBatch`` and its noise variance to LLRs
     ``[1, B, U, F, T, bits_max]`` with one of the reference's baseline systems.
 
@@ -99,47 +150,19 @@ class BaselineReceiver:
     ``baseline_perf_csi_lmmse``: ``sb.h`` (the generator must run with ``want_h=True``) and
     ``err_var = 0``."""
 
-    def __init__(self, system: str, params: GenParams, device: int = 0):
-        if system not in SYSTEMS:
-            raise ValueError(f"system must be one of {SYSTEMS}, got {system!r}")
-        if params.num_tx > MAX_TX:
-            raise ValueError(f"the LMMSE kernel is built for at most {MAX_TX} users, got {params.num_tx}")
-        self.system = system
-        self.p = params
-        self.perfect_csi = system == "baseline_perf_csi_lmmse"
-        self.detector = LMMSEDetector(device)
-        self._out = None
-        # the channel estimate the last call detected with (sb.h_hat); None with perfect CSI
-        self.last_h = None
+    SYSTEMS = SYSTEMS
 
-    @property
-    def contaminated(self) -> bool:
-        """the LS estimate can be pilot-contaminated: two active ports may share a CDM group"""
-        p = self.p
-        na = p.num_tx if p.num_active is None else p.num_active
-        groups = list(p.cdm_group[:p.num_tx])
-        return not self.perfect_csi and p.dmrs is None and na > 1 and max(groups.count(g) for g in set(groups)) > 1
+    def __init__(self, system: str, params: GenParams, device: int = 0):
+        super().__init__(system, params, device)
+        self.perfect_csi = system == "baseline_perf_csi_lmmse"
 
     def err_var(self, no: float) -> float:
         if self.perfect_csi:
             return 0.0
-        na = self.p.num_tx if self.p.num_active is None else self.p.num_active
         n = 1 if self.p.dmrs is None else self.p.dmrs.block
-        return na * float(no) / (2.0 * n)
+        return self._num_active * float(no) / (2.0 * n)
 
-    def __call__(self, sb: SlotBatch, no: float, out=None, stream=None):
-        p = self.p
-        h = sb.h if self.perfect_csi else sb.h_hat
-        if h is None:
-            raise ValueError("baseline_perf_csi_lmmse needs the true channel: SlotGenerator(want_h=True)"
-                             if self.perfect_csi else "the slot batch has no h_hat")
-        self.last_h = None if self.perfect_csi else h
-        if out is None:
-            B = h.shape[0]
-            if self._out is None or self._out.shape[1] != B:
-                torch = _torch()
-                self._out = torch.empty((1, B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS, p.bits_max),
-                                        dtype=torch.float32, device=h.device)
-            out = self._out
-        return self.detector(sb.y, h, sb.active, sb.mcs, p.mcs_bits, no, p.dmrs_symbols,
-                             err_var=self.err_var(no), out=out, stream=stream)
+    def _estimate(self, sb: SlotBatch, no: float, stream):
+        if sb.h_hat is None:
+            raise ValueError("the slot batch has no h_hat")
+        return sb.h_hat

@@ -19,16 +19,11 @@ is estimated (and compensated) with it; it is unambiguous for ``|eps| < 1 / (2 *
 """
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 
 from . import _lib
+from ._call import fill_dmrs, fill_grid, ref, require, stream_of, torch as _torch
 from .generator import NUM_SYMBOLS, GenParams, SlotBatch
-
-
-def _torch():
-    import torch
-    return torch
 
 
 class CFOCompensator:
@@ -48,24 +43,13 @@ class CFOCompensator:
         p = self.p
         B = h.shape[0]
         shape = (B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS, 2 * p.num_rx_ant)
-        if tuple(h.shape) != shape or h.dtype != torch.float32 or not h.is_contiguous() \
-                or h.device != torch.device(f"cuda:{self.device}"):
-            raise ValueError(f"the channel tensor must be a contiguous float32 {shape} tensor on cuda:{self.device}")
-        if tuple(eps.shape) != (B, p.num_tx) or eps.dtype != torch.float64 or not eps.is_contiguous() \
-                or eps.device != h.device:
-            raise ValueError(f"eps must be a contiguous float64 {(B, p.num_tx)} tensor on cuda:{self.device}")
+        require("the channel tensor", h, shape, torch.float32, f"cuda:{self.device}")
+        require("eps", eps, (B, p.num_tx), torch.float64, h.device)
         io = _lib.nrx_cfo_io()
-        io.batch, io.num_tx, io.num_subcarriers, io.num_symbols = shape[:4]
-        io.num_rx_ant, io.num_dmrs_symbols = p.num_rx_ant, len(p.dmrs_symbols)
-        for k, t in enumerate(list(p.dmrs_symbols)[:4]):
-            io.dmrs_symbols[k] = t
-        for u in range(min(p.num_tx, 16)):
-            io.cdm_group[u] = p.cdm_group[u]
+        fill_grid(io, *shape[:4], p.num_rx_ant)
+        fill_dmrs(io, p.dmrs_symbols, p.cdm_group, p.num_tx)
         io.h_in, io.eps = h.data_ptr(), eps.data_ptr()
         return io
-
-    def _stream(self, h, stream):
-        return _torch().cuda.current_stream(h.device).cuda_stream if stream is None else stream
 
     def estimate(self, sb: SlotBatch, out=None, stream=None):
         """``eps_hat [B, U]`` float64 from ``sb.h_hat`` at the own pilots; 0 for inactive users and
@@ -81,11 +65,9 @@ class CFOCompensator:
                 self._eps = torch.empty((B, self.p.num_tx), dtype=torch.float64, device=hh.device)
             out = self._eps
         io = self._io(hh, out)
-        if tuple(sb.active.shape) != (B, self.p.num_tx) or sb.active.dtype != torch.float32 \
-                or not sb.active.is_contiguous():
-            raise ValueError(f"active must be a contiguous float32 {(B, self.p.num_tx)} tensor")
+        require("active", sb.active, (B, self.p.num_tx), torch.float32)
         io.active = sb.active.data_ptr()
-        _lib.check(self._lib.nrx_cfo_estimate(ctypes.byref(io), self._stream(hh, stream)))
+        _lib.check(self._lib.nrx_cfo_estimate(ref(io), stream_of(hh, stream)))
         return out
 
     def rotate(self, h, eps, ref_mode: int, sign: int, out=None, stream=None):
@@ -93,11 +75,9 @@ class CFOCompensator:
         rotates in place."""
         io = self._io(h, eps)
         out = h if out is None else out
-        if tuple(out.shape) != tuple(h.shape) or out.dtype != h.dtype or not out.is_contiguous() \
-                or out.device != h.device:
-            raise ValueError("out must match the channel tensor")
+        require("out", out, h.shape, h.dtype, h.device)
         io.ref_mode, io.sign, io.h_out = int(ref_mode), int(sign), out.data_ptr()
-        _lib.check(self._lib.nrx_cfo_rotate(ctypes.byref(io), self._stream(h, stream)))
+        _lib.check(self._lib.nrx_cfo_rotate(ref(io), stream_of(h, stream)))
         return out
 
     def apply_nn(self, sb: SlotBatch, eps=None, stream=None) -> SlotBatch:

@@ -34,24 +34,18 @@ Three stated departures from the reference (Sionna):
 """
 from __future__ import annotations
 
-import ctypes
 import dataclasses
-from typing import Optional
 
 import numpy as np
 
 from . import _lib
-from .baseline import MAX_TX, LMMSEDetector
+from ._call import Workspace, fill_dmrs, fill_grid, ptr, ref, require, stream_of, torch as _torch
+from .baseline import Receiver
 from .generator import NUM_SYMBOLS, GenParams, SlotBatch
 
 SYSTEMS = ("baseline_lslin_lmmse", "baseline_lmmse_lmmse")
 KINDS = ("lin", "lmmse", "lmmse3")
 COV_SLOT_OFFSET = 1 << 40        # covariance slots start here: disjoint from every Monte-Carlo offset
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def toeplitz(lags: np.ndarray) -> np.ndarray:
@@ -87,53 +81,33 @@ class CovarianceEstimator:
         self.acc_s = torch.zeros((params.num_rx_ant, params.num_rx_ant, 2), dtype=torch.float64,
                                  device=f"cuda:{device}")
         self.slots = 0
-        self._ws = None
-        self._ws_s = None
+        self._ws = (Workspace(), Workspace())
         self.last_workspace_bytes = (0, 0)
 
     def accumulate(self, sb: SlotBatch, stream=None, workspace=None) -> None:
-        torch = _torch()
-        if workspace is not None:
-            for w in workspace:
-                if w.device != self.acc.device or w.dtype != torch.uint8 or not w.is_contiguous():
-                    raise ValueError(f"workspace must be two contiguous uint8 tensors on {self.acc.device}")
         h = sb.h
         if h is None:
             raise ValueError("the covariance needs the true channel: SlotGenerator(want_h=True)")
-        p = self.p
+        p, lib, dev = self.p, self._lib, self.acc.device
         B = h.shape[0]
-        if tuple(h.shape) != (B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS, 2 * p.num_rx_ant) \
-                or h.dtype != torch.float32 or not h.is_contiguous() or h.device != self.acc.device:
-            raise ValueError("h must be a contiguous float32 [B, U, F, 14, 2A] tensor on the estimator's device")
-        io = _lib.nrx_cov_io()
-        io.batch, io.num_tx, io.num_subcarriers, io.num_symbols = B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS
-        io.num_rx_ant = p.num_rx_ant
-        io.h, io.acc = h.data_ptr(), self.acc.data_ptr()
-        n = ctypes.c_size_t()
-        _lib.check(self._lib.nrx_cov_workspace_size(ctypes.byref(io), ctypes.byref(n)))
-        need = n.value
-        if workspace is not None:
-            ws = workspace[0]
-        else:
-            if self._ws is None or self._ws.numel() < n.value:
-                self._ws = torch.empty(n.value, dtype=torch.uint8, device=self.acc.device)
-            ws = self._ws
-        if stream is None:
-            stream = torch.cuda.current_stream(self.acc.device).cuda_stream
-        _lib.check(self._lib.nrx_cov_accumulate(ctypes.byref(io), ws.data_ptr(), ws.numel(), stream))
-        so = _lib.nrx_cov_space_io()
-        so.batch, so.num_tx, so.num_subcarriers, so.num_symbols = B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS
-        so.num_rx_ant = p.num_rx_ant
-        so.h, so.acc = h.data_ptr(), self.acc_s.data_ptr()
-        _lib.check(self._lib.nrx_cov_space_workspace_size(ctypes.byref(so), ctypes.byref(n)))
-        self.last_workspace_bytes = (need, n.value)
-        if workspace is not None:
-            ws = workspace[1]
-        else:
-            if self._ws_s is None or self._ws_s.numel() < n.value:
-                self._ws_s = torch.empty(n.value, dtype=torch.uint8, device=self.acc.device)
-            ws = self._ws_s
-        _lib.check(self._lib.nrx_cov_space_accumulate(ctypes.byref(so), ws.data_ptr(), ws.numel(), stream))
+        require("h", h, (B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS, 2 * p.num_rx_ant), _torch().float32, dev)
+
+        def plan(ws, cls, acc, size_fn, given):
+            """(descriptor, bytes asked, buffer) of one of the two launches: their descriptors are field for
+            field the same"""
+            d = cls()
+            fill_grid(d, B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS, p.num_rx_ant)
+            d.h, d.acc = h.data_ptr(), acc.data_ptr()
+            n = ws.size(size_fn, ref(d))
+            return d, n, ws.get(n, dev, given)
+
+        given = workspace if workspace is not None else (None, None)
+        lag = plan(self._ws[0], _lib.nrx_cov_io, self.acc, lib.nrx_cov_workspace_size, given[0])
+        spc = plan(self._ws[1], _lib.nrx_cov_space_io, self.acc_s, lib.nrx_cov_space_workspace_size, given[1])
+        self.last_workspace_bytes = (lag[1], spc[1])
+        stream = stream_of(dev, stream)
+        for (d, _, ws), run in ((lag, lib.nrx_cov_accumulate), (spc, lib.nrx_cov_space_accumulate)):
+            _lib.check(run(ref(d), ws.data_ptr(), ws.numel(), stream))
         self.slots += B
 
     def lags(self):
@@ -369,7 +343,7 @@ class ChannelEstimator:
         self._pinned = tables is not None
         self._dev = None
         self._out = None
-        self._ws = None
+        self._ws = Workspace()
         self.last_workspace_bytes = 0      # what nrx_chest3_workspace_size asked for the last call
         if tables is not None:
             self._set_design(tables)
@@ -426,77 +400,42 @@ class ChannelEstimator:
             raise ValueError("the slot batch has no h_hat")
         B = hh.shape[0]
         shape = (B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS, 2 * p.num_rx_ant)
-        if tuple(hh.shape) != shape or hh.dtype != torch.float32 or not hh.is_contiguous() \
-                or hh.device != torch.device(f"cuda:{self.device}"):
-            raise ValueError(f"h_hat must be a contiguous float32 {shape} tensor on cuda:{self.device}")
-        if tuple(sb.active.shape) != (B, p.num_tx) or sb.active.dtype != torch.float32 \
-                or not sb.active.is_contiguous():
-            raise ValueError(f"active must be a contiguous float32 {(B, p.num_tx)} tensor")
+        require("h_hat", hh, shape, torch.float32, f"cuda:{self.device}")
+        require("active", sb.active, (B, p.num_tx), torch.float32)
         if out is None:
             if self._out is None or self._out.shape[0] != B:
                 self._out = torch.empty(shape, dtype=torch.float32, device=hh.device)
             out = self._out
-        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 {shape} tensor")
-        io = _lib.nrx_chest_io()
-        io.batch, io.num_tx, io.num_subcarriers, io.num_symbols = shape[:4]
-        io.num_rx_ant, io.num_dmrs_symbols = p.num_rx_ant, len(p.dmrs_symbols)
-        for k, t in enumerate(list(p.dmrs_symbols)[:4]):
-            io.dmrs_symbols[k] = t
-        for u in range(min(p.num_tx, 16)):
-            io.cdm_group[u] = p.cdm_group[u]
-        io.no = float(no)
-        io.h_hat, io.active, io.h_out = hh.data_ptr(), sb.active.data_ptr(), out.data_ptr()
-        if stream is None:
-            stream = torch.cuda.current_stream(hh.device).cuda_stream
-        if self.kind == "lmmse3":
-            return self._lmmse3(io, no, out, stream, workspace)
-        if workspace is not None:
+        else:
+            require("out", out, shape, torch.float32)
+        if workspace is not None and self.kind != "lmmse3":
             raise ValueError(f"the {self.kind} estimator takes no workspace")
-        if self.kind == "lmmse":
-            d = self.prepare(no)
-            if self._dev is None:
-                self._dev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(hh.device)
-                                  for a in (d.filt, d.tcoef, d.vconj))
-            io.filt, io.tcoef, io.vconj = (t.data_ptr() for t in self._dev)
-            _lib.check(self._lib.nrx_chest_lmmse(ctypes.byref(io), stream))
-        else:
-            _lib.check(self._lib.nrx_chest_lin(ctypes.byref(io), stream))
-        return out
-
-
-    def _lmmse3(self, io2, no, out, stream, workspace=None):
-        torch = _torch()
+        # nrx_chest_io and nrx_chest3_io differ in their tables only
+        io = _lib.nrx_chest3_io() if self.kind == "lmmse3" else _lib.nrx_chest_io()
+        fill_grid(io, *shape[:4], p.num_rx_ant)
+        fill_dmrs(io, p.dmrs_symbols, p.cdm_group, p.num_tx)
+        io.no = float(no)
+        io.h_hat, io.active, io.h_out = ptr(hh), ptr(sb.active), ptr(out)
+        stream = stream_of(hh, stream)
+        if self.kind == "lin":
+            _lib.check(self._lib.nrx_chest_lin(ref(io), stream))
+            return out
         d = self.prepare(no)
+        tables = LMMSE3_TABLES if self.kind == "lmmse3" else ("filt", "tcoef", "vconj")
         if self._dev is None:
-            self._dev = {k: torch.from_numpy(np.ascontiguousarray(getattr(d, k))).to(out.device)
-                         for k in LMMSE3_TABLES}
-        io = _lib.nrx_chest3_io()
-        for f in ("batch", "num_tx", "num_subcarriers", "num_symbols", "num_rx_ant", "num_dmrs_symbols", "no",
-                  "h_hat", "active", "h_out"):
-            setattr(io, f, getattr(io2, f))
-        for k in range(4):
-            io.dmrs_symbols[k] = io2.dmrs_symbols[k]
-        for u in range(16):
-            io.cdm_group[u] = io2.cdm_group[u]
-        for k in LMMSE3_TABLES:
+            self._dev = {k: torch.from_numpy(np.ascontiguousarray(getattr(d, k))).to(hh.device) for k in tables}
+        for k in tables:
             setattr(io, k, self._dev[k].data_ptr())
-        n = ctypes.c_size_t()
-        _lib.check(self._lib.nrx_chest3_workspace_size(ctypes.byref(io), ctypes.byref(n)))
-        self.last_workspace_bytes = n.value
-        if workspace is not None:
-            if workspace.device != out.device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-                raise ValueError(f"workspace must be a contiguous uint8 tensor on {out.device}")
-            ws = workspace
-        else:
-            if self._ws is None or self._ws.numel() < n.value:
-                self._ws = torch.empty(n.value, dtype=torch.uint8, device=out.device)
-            ws = self._ws
-        _lib.check(self._lib.nrx_chest_lmmse3(ctypes.byref(io), ws.data_ptr(), ws.numel(), stream))
+        if self.kind == "lmmse":
+            _lib.check(self._lib.nrx_chest_lmmse(ref(io), stream))
+            return out
+        self.last_workspace_bytes = self._ws.size(self._lib.nrx_chest3_workspace_size, ref(io))
+        ws = self._ws.get(self.last_workspace_bytes, out.device, workspace)
+        _lib.check(self._lib.nrx_chest_lmmse3(ref(io), ws.data_ptr(), ws.numel(), stream))
         return out
 
 
-class EstimatorBaselineReceiver:
+class EstimatorBaselineReceiver(Receiver):
     """``rx(sb, no) -> llr [1, B, U, F, T, bits_max]`` for ``baseline_lslin_lmmse`` (linear
     interpolation) and ``baseline_lmmse_lmmse`` (2-D LMMSE estimation; needs ``R_f`` / ``R_t`` from
     a ``CovarianceEstimator``, here or through ``set_covariance``), both followed by the LMMSE
@@ -512,21 +451,12 @@ class EstimatorBaselineReceiver:
     symbols of the theoretical error map of the design; lin passes ``num_active * no / 2``, the LS
     error at a pilot, as ``baseline_lsnn_lmmse`` does."""
 
-    perfect_csi = False
     SYSTEMS = SYSTEMS
 
     def __init__(self, system: str, params: GenParams, device: int = 0, R_f=None, R_t=None, R_s=None, cfo=None):
-        if system not in SYSTEMS:
-            raise ValueError(f"system must be one of {SYSTEMS}, got {system!r}")
-        if params.num_tx > MAX_TX:
-            raise ValueError(f"the LMMSE kernel is built for at most {MAX_TX} users, got {params.num_tx}")
-        self.system = system
-        self.p = params
+        super().__init__(system, params, device)
         self._device = device
         self.cfo = cfo          # a cfo.CFOCompensator the estimator runs through, or None
-        self.detector = LMMSEDetector(device)
-        self._out = None
-        self.last_h = None      # the estimate the last call detected with
         self.estimator = None
         self._ev3 = None
         self.set_covariance(R_f, R_t, R_s)
@@ -541,16 +471,6 @@ class EstimatorBaselineReceiver:
         else:
             self.estimator.set_covariance(R_f, R_t)
 
-    @property
-    def _num_active(self) -> int:
-        return self.p.num_tx if self.p.num_active is None else self.p.num_active
-
-    @property
-    def contaminated(self) -> bool:
-        """the LS estimates can be pilot-contaminated: two active ports may share a CDM group"""
-        groups = list(self.p.cdm_group[:self.p.num_tx])
-        return self.p.dmrs is None and self._num_active > 1 and max(groups.count(g) for g in set(groups)) > 1
-
     def err_var(self, no: float) -> float:
         if self.estimator.kind == "lin":     # the LS error at a pilot, over the despreading block
             return self._num_active * float(no) / (2.0 * (2 if self.estimator.despread_f else 1))
@@ -564,19 +484,8 @@ class EstimatorBaselineReceiver:
             return self._ev3[2]
         return self._num_active * float(np.mean([d.err_var[g][:, data].mean() for g in groups]))
 
-    def __call__(self, sb: SlotBatch, no: float, out=None, stream=None):
-        p = self.p
-        ev = self.err_var(no)
-        h = self.last_h = self.estimator(sb, no, stream=stream)
-        if out is None:
-            B = h.shape[0]
-            if self._out is None or self._out.shape[1] != B:
-                torch = _torch()
-                self._out = torch.empty((1, B, p.num_tx, p.num_subcarriers, NUM_SYMBOLS, p.bits_max),
-                                        dtype=torch.float32, device=h.device)
-            out = self._out
-        return self.detector(sb.y, h, sb.active, sb.mcs, p.mcs_bits, no, p.dmrs_symbols, err_var=ev, out=out,
-                             stream=stream)
+    def _estimate(self, sb: SlotBatch, no: float, stream):
+        return self.estimator(sb, no, stream=stream)
 
 
 def estimate_covariance(gen, num_slots: int, batch_size: int, no: float = 1.0,

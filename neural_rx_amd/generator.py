@@ -29,23 +29,18 @@ that format (``nrx_generate_taps``).
 """
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib
+from ._call import Workspace, fill_dmrs, fill_grid, fill_mcs, ptr, ref, require, stream_of, torch as _torch
 from .cir import SELECT, CIRChannel, CIRDataset
 from .config import NRXConfig, dmrs_symbols, get_config, user_cdm_groups
 from .ls import DMRSPorts
 
 NUM_SYMBOLS = 14
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def ebno_to_no(ebno_db: float, num_dmrs_symbols: int = 2, num_symbols: int = NUM_SYMBOLS) -> float:
@@ -126,20 +121,12 @@ class GenParams:
 
     def desc(self, batch: int, no: float, slot_offset: int = 0) -> _lib.nrx_gen_desc:
         d = _lib.nrx_gen_desc()
-        d.batch, d.num_tx, d.num_subcarriers, d.num_symbols = batch, self.num_tx, self.num_subcarriers, NUM_SYMBOLS
-        d.num_rx_ant = self.num_rx_ant
-        d.num_dmrs_symbols = len(self.dmrs_symbols)
-        mask = 0
-        for k, t in enumerate(self.dmrs_symbols):
-            d.dmrs_symbols[k] = t
-            mask |= 1 << t
-        d.dmrs_symbol_mask = mask
-        for u in range(self.num_tx):
-            d.cdm_group[u] = self.cdm_group[u]
-            d.mcs_of_user[u] = self.mcs_of_user[u] if self.mcs_of_user is not None else 0
-        d.num_mcs = len(self.mcs_bits)
-        for m, b in enumerate(self.mcs_bits):
-            d.mcs_bits[m] = b
+        fill_grid(d, batch, self.num_tx, self.num_subcarriers, NUM_SYMBOLS, self.num_rx_ant)
+        fill_dmrs(d, self.dmrs_symbols, self.cdm_group, self.num_tx)
+        fill_mcs(d, self.mcs_bits, self.dmrs_symbols)
+        if self.mcs_of_user is not None:
+            for u in range(min(self.num_tx, 16)):
+                d.mcs_of_user[u] = self.mcs_of_user[u]
         d.num_active = self.num_tx if self.num_active is None else self.num_active
         d.num_taps, d.num_sinusoids = self.num_taps, self.num_sinusoids
         d.max_delay_s, d.max_doppler_hz = self.max_delay_s, self.max_doppler_hz
@@ -264,7 +251,7 @@ class SlotGenerator:
         self.want_h = want_h
         self.aerial = aerial
         self._lib = _lib.load()
-        self._ws = None
+        self._ws = Workspace()
         self._bufs = {}
         self._chan = None
         self._mix = None        # device copy of rx_mix(), uploaded once
@@ -308,24 +295,13 @@ class SlotGenerator:
             self._cir = r
 
     def workspace_bytes(self, batch: int) -> int:
-        n = ctypes.c_size_t()
-        d = self.p.desc(batch, 0.0)
-        ref = lambda s: ctypes.byref(s) if s is not None else None  # noqa: E731
-        if self._cir is not None:
-            if self._cir.select == SELECT["index"] and not self._cir.index:
-                # the size is no function of the index, which comes with every call: any address passes the check
-                self._cir.index = self._cir_tau.data_ptr()
-            _lib.check(self._lib.nrx_gen_workspace_size_cir(ctypes.byref(d), ref(self._cfo), ref(self._dmrs),
-                                                            ctypes.byref(self._cir), ctypes.byref(n)))
-        elif self._dmrs is not None:
-            _lib.check(self._lib.nrx_gen_workspace_size_dmrs(
-                ctypes.byref(d), ctypes.byref(self._cfo) if self._cfo is not None else None, ctypes.byref(self._dmrs),
-                ctypes.byref(n)))
-        elif self._cfo is not None:
-            _lib.check(self._lib.nrx_gen_workspace_size_cfo(ctypes.byref(d), ctypes.byref(self._cfo), ctypes.byref(n)))
-        else:
-            _lib.check(self._lib.nrx_gen_workspace_size(ctypes.byref(d), ctypes.byref(n)))
-        return n.value
+        """what ``nrx_gen_workspace_size_cir`` asks for with whichever blocks this generator has (NULL for
+        the absent ones: the older ``nrx_gen_workspace_size*`` are that call with fewer blocks)"""
+        if self._cir is not None and self._cir.select == SELECT["index"] and not self._cir.index:
+            # the size is no function of the index, which comes with every call: any address passes the check
+            self._cir.index = self._cir_tau.data_ptr()
+        return self._ws.size(self._lib.nrx_gen_workspace_size_cir, ref(self.p.desc(batch, 0.0)), ref(self._cfo),
+                             ref(self._dmrs), ref(self._cir))
 
     def _alloc(self, batch: int) -> SlotBatch:
         torch = _torch()
@@ -363,53 +339,28 @@ class SlotGenerator:
         ``[batch, U]`` int32 (device) of a ``CIRChannel(select="index")``."""
         torch = _torch()
         sb = out if out is not None else self._alloc(batch)
-        if workspace is not None:
-            if not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-                raise ValueError("workspace must be a contiguous uint8 CUDA tensor")
-            ws = workspace
-        else:
-            nbytes = self.workspace_bytes(batch)
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{self.device}")
-            ws = self._ws
+        nbytes = self.workspace_bytes(batch) if workspace is None else 0      # the C call sizes a caller's
+        ws = self._ws.get(nbytes, f"cuda:{self.device}", workspace)
         d = self.p.desc(batch, no, slot_offset)
         o = _lib.nrx_gen_out()
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         o.y, o.h_hat, o.h, o.active = ptr(sb.y), ptr(sb.h_hat), ptr(sb.h), ptr(sb.active)
         o.mcs_mask, o.mcs, o.bits, o.bits_stride = ptr(sb.mcs_mask), ptr(sb.mcs), ptr(sb.bits), self.p.bits_max
         o.y_real, o.y_imag = ptr(sb.y_real), ptr(sb.y_imag)
         o.h_ls_real, o.h_ls_imag = ptr(sb.h_ls_real), ptr(sb.h_ls_imag)
-        if stream is None:
-            stream = torch.cuda.current_stream(sb.y.device).cuda_stream
         if self._cfo is not None:
             self._cfo.eps_out = ptr(sb.cfo_eps)
         if self._dmrs is not None:
             self._dmrs.pilots_out = ptr(sb.pilots)
-        if self._cir is not None:
-            if self._cir.select == SELECT["index"]:
-                if (cir_index is None or not cir_index.is_cuda or cir_index.dtype != torch.int32
-                        or tuple(cir_index.shape) != (batch, self.p.num_tx) or not cir_index.is_contiguous()):
-                    raise ValueError(f"select='index' needs cir_index: a contiguous int32 CUDA tensor {(batch, self.p.num_tx)}")
-                self._cir.index = cir_index.data_ptr()
-            ref = lambda s: ctypes.byref(s) if s is not None else None  # noqa: E731
-            _lib.check(self._lib.nrx_generate_slots_cir(
-                ctypes.byref(d), None, ref(self._cfo), ref(self._dmrs), ctypes.byref(self._cir), ctypes.byref(o),
-                ws.data_ptr(), ws.numel(), stream))
-        elif self._dmrs is not None:
-            _lib.check(self._lib.nrx_generate_slots_dmrs(
-                ctypes.byref(d), ctypes.byref(self._chan) if self._chan is not None else None,
-                ctypes.byref(self._cfo) if self._cfo is not None else None, ctypes.byref(self._dmrs), ctypes.byref(o),
-                ws.data_ptr(), ws.numel(), stream))
-        elif self._cfo is not None:
-            _lib.check(self._lib.nrx_generate_slots_cfo(
-                ctypes.byref(d), ctypes.byref(self._chan) if self._chan is not None else None,
-                ctypes.byref(self._cfo), ctypes.byref(o), ws.data_ptr(), ws.numel(), stream))
-        elif self._chan is not None:
-            _lib.check(self._lib.nrx_generate_slots_ex(ctypes.byref(d), ctypes.byref(self._chan), ctypes.byref(o),
-                                                       ws.data_ptr(), ws.numel(), stream))
-        else:
-            _lib.check(self._lib.nrx_generate_slots(ctypes.byref(d), ctypes.byref(o), ws.data_ptr(), ws.numel(),
-                                                    stream))
+        if self._cir is not None and self._cir.select == SELECT["index"]:
+            if cir_index is None:
+                raise ValueError("select='index' needs cir_index")
+            require("cir_index", cir_index, (batch, self.p.num_tx), torch.int32, sb.y.device)
+            self._cir.index = cir_index.data_ptr()
+        # one entry point: the older nrx_generate_slots* are this call with NULL for the blocks they lack.
+        # A dataset is the channel, so chan stays NULL with it (GenParams refuses the two together).
+        _lib.check(self._lib.nrx_generate_slots_cir(
+            ref(d), ref(self._chan), ref(self._cfo), ref(self._dmrs), ref(self._cir), ref(o), ws.data_ptr(), ws.numel(),
+            stream_of(sb.y, stream)))
         return sb
 
     def export_taps(self, batch: int, slot_offset: int = 0, stream=None) -> CIRDataset:
@@ -425,14 +376,9 @@ class SlotGenerator:
         a = torch.empty((E, p.num_rx_ant, p.num_taps, NUM_SYMBOLS), dtype=torch.complex64, device=dev)
         tau = torch.empty((E, p.num_taps), dtype=torch.float32, device=dev)
         d = p.desc(batch, 0.0, slot_offset)
-        n = ctypes.c_size_t()
-        _lib.check(self._lib.nrx_gen_workspace_size(ctypes.byref(d), ctypes.byref(n)))
-        if self._ws is None or self._ws.numel() < n.value:
-            self._ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(a.device).cuda_stream
-        _lib.check(self._lib.nrx_generate_taps(ctypes.byref(d), ctypes.byref(self._chan) if self._chan is not None else None,
-                                               a.data_ptr(), tau.data_ptr(), self._ws.data_ptr(), self._ws.numel(), stream))
+        ws = self._ws.get(self._ws.size(self._lib.nrx_gen_workspace_size, ref(d)), dev)
+        _lib.check(self._lib.nrx_generate_taps(ref(d), ref(self._chan), a.data_ptr(), tau.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), stream_of(a, stream)))
         return CIRDataset(a, tau)
 
 
@@ -449,14 +395,8 @@ def count_errors(llr, bits, active, mcs, mcs_bits: Sequence[int], dmrs_syms: Seq
     if tuple(bits.shape) != (B, U, F, T, bs):
         raise ValueError(f"bits must be {(B, U, F, T, bs)}, got {tuple(bits.shape)}")
     c = _lib.nrx_count_io()
-    c.batch, c.num_tx, c.num_subcarriers, c.num_symbols = B, U, F, T
-    c.num_heads, c.bits_stride, c.num_mcs = H, bs, len(mcs_bits)
-    for m, b in enumerate(mcs_bits):
-        c.mcs_bits[m] = b
-    c.dmrs_symbol_mask = sum(1 << t for t in dmrs_syms)
-    c.llr, c.bits, c.active, c.counts = llr.data_ptr(), bits.data_ptr(), active.data_ptr(), counts.data_ptr()
-    c.mcs = mcs.data_ptr() if mcs is not None else None
-    if stream is None:
-        stream = torch.cuda.current_stream(llr.device).cuda_stream
-    _lib.check(lib.nrx_count_errors(ctypes.byref(c), stream))
+    fill_grid(c, B, U, F, T)
+    fill_mcs(c, mcs_bits, dmrs_syms, bits_stride=bs, num_heads=H)
+    c.llr, c.bits, c.active, c.counts, c.mcs = ptr(llr), ptr(bits), ptr(active), ptr(counts), ptr(mcs)
+    _lib.check(lib.nrx_count_errors(ref(c), stream_of(llr, stream)))
     return counts

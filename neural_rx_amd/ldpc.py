@@ -27,6 +27,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
+from ._call import Workspace, fill_grid, fill_mcs, ptr, ref, stream_of, torch as _torch
 
 MAX_Z = 384
 CN_TYPES = {"boxplus": 0, "minsum": 1}
@@ -34,11 +35,6 @@ CN_TYPES = {"boxplus": 0, "minsum": 1}
 NAMED = {"r12": (3, 6, 24), "r23": (3, 9, 36), "r34": (3, 12, 24), "r13": (4, 6, 24)}
 SEED = 2024
 TABLES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ldpc_tables.json")
-
-
-def _torch():
-    import torch
-    return torch
 
 
 @dataclasses.dataclass
@@ -175,7 +171,7 @@ class Decoder:
         h = ctypes.c_void_p()
         _lib.check(self._lib.nrx_ldpc_create(ctypes.byref(c), device, ctypes.byref(h)))
         self._h = h
-        self._ws = None
+        self._ws = Workspace()
         self.last_workspace_bytes = 0
 
     def __del__(self):
@@ -204,18 +200,12 @@ class Decoder:
         io.num_cw, io.num_iter, io.early_stop = n, int(num_iter), int(bool(early_stop))
         io.cn_type = CN_TYPES[cn_type] if isinstance(cn_type, str) else int(cn_type)
         io.ms_scale, io.llr_clip = float(ms_scale), float(llr_clip)
-        io.llr_in = llr_in.data_ptr()
-        io.skip = skip.data_ptr() if skip is not None else None
-        io.hard, io.iters, io.parity_ok = out["hard"].data_ptr(), out["iters"].data_ptr(), out["parity_ok"].data_ptr()
-        io.app = out["app"].data_ptr() if want_app else None
-        nbytes = ctypes.c_size_t()
-        _lib.check(self._lib.nrx_ldpc_workspace_size(self._h, ctypes.byref(io), ctypes.byref(nbytes)))
-        self.last_workspace_bytes = nbytes.value
-        if self._ws is None or self._ws.numel() * 4 < nbytes.value or self._ws.device != dev:
-            self._ws = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(self._lib.nrx_ldpc_decode(self._h, ctypes.byref(io), self._ws.data_ptr(), self._ws.numel() * 4, stream))
+        io.llr_in, io.skip = ptr(llr_in), ptr(skip)
+        io.hard, io.iters, io.parity_ok = ptr(out["hard"]), ptr(out["iters"]), ptr(out["parity_ok"])
+        io.app = ptr(out["app"]) if want_app else None
+        self.last_workspace_bytes = self._ws.size(self._lib.nrx_ldpc_workspace_size, self._h, ref(io))
+        ws = self._ws.get(self.last_workspace_bytes, dev)
+        _lib.check(self._lib.nrx_ldpc_decode(self._h, ref(io), ws.data_ptr(), ws.numel(), stream_of(dev, stream)))
         return out
 
 
@@ -244,20 +234,13 @@ def gather(llr, bits, active, mcs, mcs_bits: Sequence[int], dmrs_symbols: Sequen
         out = (torch.empty((B * U * C, N), dtype=torch.float32, device=dev),
                torch.empty(B * U * C, dtype=torch.uint8, device=dev))
     io = _lib.nrx_ldpc_gather_io()
-    io.batch, io.num_tx, io.num_subcarriers, io.num_symbols = B, U, F, T
-    io.num_heads, io.bits_stride, io.num_mcs = H, bs, len(mcs_bits)
-    for m, b in enumerate(mcs_bits):
-        io.mcs_bits[m] = int(b)
-    io.dmrs_symbol_mask = sum(1 << t for t in dmrs_symbols)
+    fill_grid(io, B, U, F, T)
+    fill_mcs(io, mcs_bits, dmrs_symbols, bits_stride=bs, num_heads=H)
     io.num_cw_per_user, io.n_tx, io.n = int(C), int(n_tx), int(N)
-    io.llr, io.bits, io.active = llr.data_ptr(), bits.data_ptr(), active.data_ptr()
-    io.mcs = mcs.data_ptr() if mcs is not None else None
-    io.tx_col = tx_col.data_ptr() if tx_col is not None else None
-    io.col_prior = col_prior.data_ptr() if col_prior is not None else None
-    io.llr_in, io.skip = out[0].data_ptr(), out[1].data_ptr()
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.nrx_ldpc_gather(ctypes.byref(io), stream))
+    io.llr, io.bits, io.active, io.mcs = ptr(llr), ptr(bits), ptr(active), ptr(mcs)
+    io.tx_col, io.col_prior = ptr(tx_col), ptr(col_prior)
+    io.llr_in, io.skip = ptr(out[0]), ptr(out[1])
+    _lib.check(lib.nrx_ldpc_gather(ref(io), stream_of(dev, stream)))
     return out
 
 
@@ -279,9 +262,7 @@ def count(hard, skip, B: int, U: int, C: int, num_info: int, counts, iters=None,
         if iters.dtype != torch.int32 or tuple(iter_counts.shape) != (U, 2) or iter_counts.dtype != torch.int64:
             raise ValueError(f"iters must be int32 and iter_counts int64 [{U}, 2]")
         io.iters, io.iter_counts = iters.data_ptr(), iter_counts.data_ptr()
-    if stream is None:
-        stream = torch.cuda.current_stream(hard.device).cuda_stream
-    _lib.check(lib.nrx_ldpc_count(ctypes.byref(io), stream))
+    _lib.check(lib.nrx_ldpc_count(ref(io), stream_of(hard, stream)))
     return counts
 
 

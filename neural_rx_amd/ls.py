@@ -16,19 +16,14 @@ The base sequence is the project's own seeded QPSK, not the Gold sequence of TS 
 """
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 from typing import Sequence
 
 from . import _lib
+from ._call import fill_dmrs, fill_grid, ptr, ref, require, stream_of, torch as _torch
 
 NUM_SYMBOLS = 14
 MAX_PORTS = 8       # 2 CDM groups x 2 frequency covers x 2 time covers
-
-
-def _torch():
-    import torch
-    return torch
 
 
 @dataclasses.dataclass(frozen=True)
@@ -126,12 +121,10 @@ class LSEstimator:
     def io(self, batch: int) -> _lib.nrx_ls_io:
         p = self.ports
         io = _lib.nrx_ls_io()
-        io.batch, io.num_tx, io.num_subcarriers, io.num_symbols = batch, p.num_tx, self.F, NUM_SYMBOLS
-        io.num_rx_ant, io.num_dmrs_symbols = self.A, len(self.dmrs_symbols)
-        for k, t in enumerate(self.dmrs_symbols[:4]):
-            io.dmrs_symbols[k] = t
-        for u in range(p.num_tx):
-            io.cdm_group[u], io.focc[u], io.tocc[u] = p.cdm_group[u], p.focc[u], p.tocc[u]
+        fill_grid(io, batch, p.num_tx, self.F, NUM_SYMBOLS, self.A)
+        fill_dmrs(io, self.dmrs_symbols, p.cdm_group, p.num_tx)
+        for u in range(p.num_tx):       # DMRSPorts holds at most 16
+            io.focc[u], io.tocc[u] = p.focc[u], p.tocc[u]
         io.despread_f, io.despread_t = int(p.despread_f), int(p.despread_t)
         return io
 
@@ -141,10 +134,10 @@ class LSEstimator:
         want = {"y": (y, (B, F, NUM_SYMBOLS, 2 * A)), "pilots": (pilots, (2, (F + 1) // 2, nd, 2))}
         if active is not None:
             want["active"] = (active, (B, U))
+        if not y.is_cuda:
+            raise ValueError("y must be on the GPU")
         for name, (t, shape) in want.items():
-            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != y.device \
-                    or not t.is_cuda:
-                raise ValueError(f"{name} must be a contiguous float32 {shape} tensor on the GPU")
+            require(name, t, shape, torch.float32, y.device)
         if self._out is None or self._out[0].shape[0] != B or self._out[0].device != y.device:
             f32 = dict(dtype=torch.float32, device=y.device)
             out = [torch.empty((B, U, F, NUM_SYMBOLS, 2 * A), **f32)]
@@ -152,12 +145,8 @@ class LSEstimator:
                 out += [torch.empty((B, nd * (F // 2), U, A), **f32) for _ in range(2)]
             self._out = out
         io = self.io(B)
-        io.y, io.pilots = y.data_ptr(), pilots.data_ptr()
-        io.active = active.data_ptr() if active is not None else None
-        io.h_hat = self._out[0].data_ptr()
+        io.y, io.pilots, io.active, io.h_hat = ptr(y), ptr(pilots), ptr(active), ptr(self._out[0])
         if self.aerial:
-            io.h_ls_real, io.h_ls_imag = self._out[1].data_ptr(), self._out[2].data_ptr()
-        if stream is None:
-            stream = torch.cuda.current_stream(y.device).cuda_stream
-        _lib.check(self._lib.nrx_ls_estimate(ctypes.byref(io), stream))
+            io.h_ls_real, io.h_ls_imag = ptr(self._out[1]), ptr(self._out[2])
+        _lib.check(self._lib.nrx_ls_estimate(ref(io), stream_of(y, stream)))
         return tuple(self._out) if self.aerial else self._out[0]

@@ -24,16 +24,12 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from ._call import Workspace, ptr, stream_of, torch as _torch
 from .config import (ModelSpec, NRXConfig, data_re_indices, dmrs_symbols, get_config, spec_from_config,
                      user_cdm_groups)
 from . import weights as _weights
 
 NUM_SYMBOLS = 14
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def compute_pe(num_tx: int, num_subcarriers: int, dmrs_syms: Sequence[int],
@@ -74,7 +70,8 @@ class CGNNEngine:
         _lib.check(lib.nrx_create(ctypes.byref(self._desc), ptrs, sizes, n.value, device,
                                   ctypes.byref(h)))
         self._h = h
-        self._ws = {}
+        self._dev = _torch().device("cuda", device)
+        self._ws = Workspace()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -155,10 +152,8 @@ class CGNNEngine:
 
     def workspace_bytes(self, batch, num_tx, num_subcarriers, precision="f16", y_layout="cgnn") -> int:
         shape = _lib.nrx_shape(batch, num_tx, num_subcarriers, NUM_SYMBOLS)
-        out = ctypes.c_size_t()
-        _lib.check(self._lib.nrx_workspace_size_ex(self._h, ctypes.byref(shape), _lib.PRECISIONS[precision],
-                                                   _lib.Y_LAYOUTS[y_layout], ctypes.byref(out)))
-        return out.value
+        return self._ws.size(self._lib.nrx_workspace_size_ex, self._h, ctypes.byref(shape),
+                             _lib.PRECISIONS[precision], _lib.Y_LAYOUTS[y_layout])
 
     def aerial_workspace_bytes(self, batch, num_tx, num_subcarriers, num_dmrs_symbols=2, num_dmrs_subcarriers=6,
                                precision="f16") -> int:
@@ -167,23 +162,7 @@ class CGNNEngine:
         io.shape = _lib.nrx_shape(batch, num_tx, num_subcarriers, NUM_SYMBOLS)
         io.num_dmrs_symbols, io.num_dmrs_subcarriers = num_dmrs_symbols, num_dmrs_subcarriers
         io.precision = _lib.PRECISIONS[precision]
-        out = ctypes.c_size_t()
-        _lib.check(self._lib.nrx_aerial_workspace_size(self._h, ctypes.byref(io), ctypes.byref(out)))
-        return out.value
-
-    def _workspace(self, nbytes: int, given=None):
-        """The cached buffer, grown to ``nbytes`` -- or the caller's ``workspace=`` tensor, passed
-        on as it is: the C call checks its size (NRX_ERR_WORKSPACE when it is too small)."""
-        torch = _torch()
-        if given is not None:
-            if not given.is_cuda or given.dtype != torch.uint8 or not given.is_contiguous():
-                raise ValueError("workspace must be a contiguous uint8 CUDA tensor")
-            return given
-        ws = self._ws.get("buf")
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{self.device}")
-            self._ws["buf"] = ws
-        return ws
+        return self._ws.size(self._lib.nrx_aerial_workspace_size, self._h, ctypes.byref(io))
 
     def alloc_outputs(self, batch, num_tx, num_subcarriers, want_h=True):
         torch = _torch()
@@ -247,21 +226,15 @@ class CGNNEngine:
             out = self.alloc_outputs(B, U, F, want_h)
         llr, h_ref = out
         prec = _lib.PRECISIONS[precision]
-        nbytes = self.workspace_bytes(B, U, F, precision, y_layout)
-        ws = self._workspace(nbytes, workspace)
+        ws = self._ws.get(self.workspace_bytes(B, U, F, precision, y_layout), self._dev, workspace)
         io = _lib.nrx_io()
         io.shape = _lib.nrx_shape(B, U, F, NUM_SYMBOLS)
         io.num_it = sp.num_it if num_it is None else num_it
         io.precision = prec
         io.y, io.pe, io.active, io.llr = y.data_ptr(), pe.data_ptr(), active.data_ptr(), llr.data_ptr()
-        io.h_hat = h_hat.data_ptr() if h_hat is not None else None
-        io.mcs_mask = mcs_mask.data_ptr() if mcs_mask is not None else None
-        io.h_ref = h_ref.data_ptr() if h_ref is not None else None
-        if stream is None:
-            stream = torch.cuda.current_stream(y.device).cuda_stream
-        _lib.check(self._lib.nrx_forward_ex(self._h, ctypes.byref(io), _lib.Y_LAYOUTS[y_layout],
-                                            y_im.data_ptr() if y_im is not None else None, ws.data_ptr(),
-                                            ws.numel(), stream))
+        io.h_hat, io.mcs_mask, io.h_ref = ptr(h_hat), ptr(mcs_mask), ptr(h_ref)
+        _lib.check(self._lib.nrx_forward_ex(self._h, ctypes.byref(io), _lib.Y_LAYOUTS[y_layout], ptr(y_im),
+                                            ws.data_ptr(), ws.numel(), stream_of(y, stream)))
         # keep inputs alive until the stream consumed them
         self._last_inputs = tensors
         return llr, h_ref
@@ -276,10 +249,8 @@ class CGNNEngine:
             raise ValueError("llr_head must be contiguous (a head slice of the forward output)")
         B, U, F, T, stride = llr_head.shape
         out = torch.empty((B, U, data_re.numel() * bits), dtype=torch.float32, device=llr_head.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(llr_head.device).cuda_stream
         _lib.check(self._lib.nrx_llr_demap(llr_head.data_ptr(), B, U, F, T, stride, bits, data_re.data_ptr(),
-                                           data_re.numel(), out.data_ptr(), stream))
+                                           data_re.numel(), out.data_ptr(), stream_of(llr_head, stream)))
         return out
 
     # -------------------------------------------------------------- Aerial contract
@@ -334,10 +305,8 @@ class CGNNEngine:
         h = torch.empty((B, U, F, NUM_SYMBOLS, 2 * A), dtype=torch.float32, device=dev)
         pe = torch.empty((U, F, NUM_SYMBOLS, 2), dtype=torch.float32, device=dev)
         nn = torch.empty((U, NUM_SYMBOLS, 12), dtype=torch.int32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(self._lib.nrx_aerial_preprocess(self._h, ctypes.byref(io), y.data_ptr(), h.data_ptr(),
-                                                   pe.data_ptr(), nn.data_ptr(), stream))
+                                                   pe.data_ptr(), nn.data_ptr(), stream_of(dev, stream)))
         self._last_inputs = kept
         return y, h, pe, nn
 
@@ -371,13 +340,11 @@ class CGNNEngine:
         io.precision = _lib.PRECISIONS[precision]
         io.dmrs_port_mask = mask.data_ptr()
         io.llr = llr.data_ptr()
-        io.h_hat = h.data_ptr() if h is not None else None
-        nbytes = ctypes.c_size_t()
-        _lib.check(self._lib.nrx_aerial_workspace_size(self._h, ctypes.byref(io), ctypes.byref(nbytes)))
-        ws = self._workspace(nbytes.value, workspace)
-        if stream is None:
-            stream = torch.cuda.current_stream(y_real.device).cuda_stream
-        _lib.check(self._lib.nrx_forward_aerial(self._h, ctypes.byref(io), ws.data_ptr(), ws.numel(), stream))
+        io.h_hat = ptr(h)
+        nbytes = self._ws.size(self._lib.nrx_aerial_workspace_size, self._h, ctypes.byref(io))
+        ws = self._ws.get(nbytes, self._dev, workspace)
+        _lib.check(self._lib.nrx_forward_aerial(self._h, ctypes.byref(io), ws.data_ptr(), ws.numel(),
+                                                stream_of(y_real, stream)))
         self._last_inputs = [y_real, y_imag, h_ls_real, h_ls_imag, mask, ofdm, scp]
         return llr, h
 

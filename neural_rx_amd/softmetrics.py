@@ -18,23 +18,18 @@ caller that fills them itself and only wants ``reduce`` / ``result``.
 """
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 from typing import List, Optional, Sequence
 
 import numpy as np
 
 from . import _lib
+from ._call import Workspace, fill_grid, fill_mcs, ptr, ref, stream_of, torch as _torch
 
 DEFAULT_SCALES = (0.25, 0.354, 0.5, 0.707, 1.0, 1.414, 2.0, 2.828, 4.0)
 MAX_SCALES = 16
 MAX_BITS = 8
 STRIP_SUBCARRIERS = _lib.SOFT_STRIP
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def ebno_at_rate(curve, rate: float) -> Optional[float]:
@@ -156,29 +151,18 @@ class SoftAccumulator:
         self.loss = self.f64[:n * S].view(U, M, MAX_BITS, S)
         self.err = self.f64[n * S:n * S + U]
         self.ref = self.f64[n * S + U:]
-        self._ws = None
-        self._ws_bytes = {}
+        self._ws = Workspace()
         self.last_workspace_bytes = 0      # what the *_workspace_size call asked for the last add_*
         self._total = None         # (i64, f64) of the last reduce, dropped by the next add
         self._lib = _lib.load() if device is not None else None
 
-    def _workspace(self, size_fn, io, key, given=None):
-        """(pointer, bytes) of the workspace, grown to what ``size_fn(io)`` asks for (asked once per
-        shape ``key``) -- or of the caller's ``workspace=`` (a uint8 tensor on the device, any content)"""
-        torch = _torch()
-        nbytes = self._ws_bytes.get(key)
-        if nbytes is None:
-            n = ctypes.c_size_t()
-            _lib.check(size_fn(ctypes.byref(io), ctypes.byref(n)))
-            nbytes = self._ws_bytes[key] = n.value
-        self.last_workspace_bytes = nbytes
-        if given is not None:
-            if given.device != self.i64.device or given.dtype != torch.uint8 or not given.is_contiguous():
-                raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.i64.device}")
-            return given.data_ptr(), given.numel()
-        if self._ws is None or self._ws.numel() * 8 < nbytes:
-            self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=self.i64.device)
-        return self._ws.data_ptr(), self._ws.numel() * 8
+    def _run(self, size_fn, fn, io, key, given, stream):
+        """``fn(io)`` in the workspace, grown to what ``size_fn(io)`` asks for (asked once per shape
+        ``key``) -- or in the caller's ``workspace=`` (a uint8 tensor on the device, any content)"""
+        self.last_workspace_bytes = self._ws.size(size_fn, ref(io), key=key)
+        ws = self._ws.get(self.last_workspace_bytes, self.i64.device, given)
+        _lib.check(fn(ref(io), ws.data_ptr(), ws.numel(), stream))
+        self._total = None
 
     def _on_device(self, **tensors):
         if self._lib is None:
@@ -202,22 +186,15 @@ class SoftAccumulator:
         if mcs is not None and (tuple(mcs.shape) != (B, U) or mcs.dtype != torch.uint8):
             raise ValueError(f"mcs must be uint8 {(B, U)}")
         io = _lib.nrx_llr_stats_io()
-        io.batch, io.num_tx, io.num_subcarriers, io.num_symbols = B, U, F, T
-        io.num_heads, io.bits_stride, io.num_mcs = H, bs, len(self.mcs_bits)
-        for m, b in enumerate(self.mcs_bits):
-            io.mcs_bits[m] = b
-        io.dmrs_symbol_mask = sum(1 << t for t in dmrs_symbols)
+        fill_grid(io, B, U, F, T)
+        fill_mcs(io, self.mcs_bits, dmrs_symbols, bits_stride=bs, num_heads=H)
         io.num_scales = len(self.scales)
         for s, v in enumerate(self.scales):
             io.scales[s] = v
-        io.llr, io.bits, io.active = llr.data_ptr(), bits.data_ptr(), active.data_ptr()
-        io.mcs = mcs.data_ptr() if mcs is not None else None
-        io.loss, io.cnt, io.nonfinite = self.loss.data_ptr(), self.cnt.data_ptr(), self.nonfinite.data_ptr()
-        ws, ws_bytes = self._workspace(self._lib.nrx_llr_stats_workspace_size, io, ("llr", B, F), workspace)
-        if stream is None:
-            stream = torch.cuda.current_stream(llr.device).cuda_stream
-        _lib.check(self._lib.nrx_llr_stats(ctypes.byref(io), ws, ws_bytes, stream))
-        self._total = None
+        io.llr, io.bits, io.active, io.mcs = ptr(llr), ptr(bits), ptr(active), ptr(mcs)
+        io.loss, io.cnt, io.nonfinite = ptr(self.loss), ptr(self.cnt), ptr(self.nonfinite)
+        self._run(self._lib.nrx_llr_stats_workspace_size, self._lib.nrx_llr_stats, io, ("llr", B, F), workspace,
+                  stream_of(llr, stream))
 
     def add_channel(self, h_est, h_true, active, symbol_mask: int = 0, stream=None, workspace=None):
         """h_est, h_true [B, U, F, T, 2A] f32, active [B, U] f32; ``symbol_mask`` bit t selects symbol t
@@ -232,15 +209,12 @@ class SoftAccumulator:
         if tuple(active.shape) != (B, U) or active.dtype != torch.float32:
             raise ValueError(f"active must be float32 {(B, U)}")
         io = _lib.nrx_nmse_io()
-        io.batch, io.num_tx, io.num_subcarriers, io.num_symbols = B, U, F, T
-        io.num_rx_ant, io.symbol_mask = A2 // 2, int(symbol_mask)
-        io.h_est, io.h_true, io.active = h_est.data_ptr(), h_true.data_ptr(), active.data_ptr()
-        io.err, io.ref, io.items = self.err.data_ptr(), self.ref.data_ptr(), self.items.data_ptr()
-        ws, ws_bytes = self._workspace(self._lib.nrx_nmse_workspace_size, io, ("nmse", B, F), workspace)
-        if stream is None:
-            stream = torch.cuda.current_stream(h_true.device).cuda_stream
-        _lib.check(self._lib.nrx_chest_nmse(ctypes.byref(io), ws, ws_bytes, stream))
-        self._total = None
+        fill_grid(io, B, U, F, T, A2 // 2)
+        io.symbol_mask = int(symbol_mask)
+        io.h_est, io.h_true, io.active = ptr(h_est), ptr(h_true), ptr(active)
+        io.err, io.ref, io.items = ptr(self.err), ptr(self.ref), ptr(self.items)
+        self._run(self._lib.nrx_nmse_workspace_size, self._lib.nrx_chest_nmse, io, ("nmse", B, F), workspace,
+                  stream_of(h_true, stream))
 
     def reduce(self, dist=None):
         """Sum the accumulators over the ranks of ``dist`` (``torch.distributed``, or None: this rank

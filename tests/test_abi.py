@@ -35,6 +35,15 @@ def test_exports_every_header_symbol(lib):
     assert lib.nrx_api_version() == 7
 
 
+def test_signatures_cover_every_header_symbol(lib):
+    assert set(_lib.SIGNATURES) == set(header_symbols())
+    assert _lib.EXPORTS == list(_lib.SIGNATURES)
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes), name
+        assert fn.restype is restype, name
+
+
 @pytest.mark.parametrize("name", sorted(BUILTIN))
 def test_weight_layout_matches_keras_order(lib, name):
     spec = spec_from_config(get_config(name))

@@ -52,7 +52,7 @@ def test_gz_last_strip_last_slot_f_not_multiple_of_24_u1():
     eng = CGNNEngine(case.spec, case.weights)          # fresh: workspace allocated at the exact size
     try:
         got = run_engine(case, "f16", eng)
-        assert eng._ws["buf"].numel() == eng.workspace_bytes(160, 1, 36)
+        assert eng._ws.buf.numel() == eng.workspace_bytes(160, 1, 36)
     finally:
         eng.close()
     ref = run_oracle(case)

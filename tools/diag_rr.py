@@ -27,7 +27,7 @@ def run(rr, num_it):
     eng.update_schedule(rr)
     llr, h = eng.forward(*args, num_it=num_it, precision="f16")
     torch.cuda.synchronize()
-    ws = eng._ws["buf"].clone().cpu().numpy()
+    ws = eng._ws.buf.clone().cpu().numpy()
     off = ((B * 8 + 255) // 256) * 256
     pl = []
     for k in range(5):
