@@ -519,6 +519,107 @@ int nrx_generate_slots_cir(const nrx_gen_desc* desc, const nrx_gen_chan* chan, c
 int nrx_generate_taps(const nrx_gen_desc* desc, const nrx_gen_chan* chan, float* a_out, float* tau_out,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- OFDM modulation and demodulation
+ * The step between time-domain samples and the resource grid that everything else here consumes: the
+ * reference's OFDMModulator / OFDMDemodulator (utils/siona_tf.py:4407-4643) with its unitary fft / ifft
+ * (4331-4402, scale 1 / sqrt(N) each way).  tests/ofdm_ref.py states both in numpy.
+ *
+ * N = fft_size, F = grid_subcarriers, bin(f) = (f + first_bin - N/2) mod N: first_bin is the position of
+ * grid subcarrier 0 on the fftshifted axis (DC in the middle), the default N/2 - F/2 centres the grid.
+ * The sample row of stream (b, s) holds the symbols back to back, symbol t at
+ * start[t] = sum over t' < t of (cp_length[t'] + N); entries of cp_length at t >= T are not read.
+ *
+ * nrx_ofdm_modulate, per (b, s, t): grid subcarrier f goes to bin(f), the other bins are zero; the unitary
+ * IDFT; the last cp_length[t] samples are prepended; the symbols are concatenated.  With pa_asat = A > 0
+ * a sample v is stored as the Rapp curve v / (1 + (|v| / A)^(2p))^(1 / (2p)), p = pa_smoothness, evaluated
+ * in f64; pa_asat <= 0 is the linear amplifier.  Samples from the end of symbol T - 1 up to L are written
+ * zero: every element of `samples` is written.  timing_advance and offset are not read.
+ *
+ * nrx_ofdm_demodulate: the window of symbol t of stream s starts at sample
+ *   offset[s] + start[t] + cp_length[t] - timing_advance;
+ * samples outside [0, L) read as zero.  The unitary DFT; bin k (unshifted, 0..N-1) is multiplied by
+ * e^{+j 2 pi k timing_advance / N}; bin(f) is written to grid subcarrier f.  With F = N, first_bin = 0, a
+ * uniform cyclic prefix and zero offsets this is OFDMDemodulator(N, l_min = -timing_advance, cp) on a
+ * sequence that already starts at l_min.  Every element of `grid` is written.  pa_* are not read; entries
+ * of offset at s >= S are not read.
+ *
+ * One launch each: a transform lives in LDS between its one global read and its one global write
+ * (csrc/nrx_ofdm.hip).  Asynchronous on `stream`; no workspace, no atomics; the same bits on every call
+ * and for every split of the batch.  (The F of this struct is grid_subcarriers, not num_subcarriers: that name
+ * belongs to the slot grids [batch][num_tx][num_subcarriers][14], and this one has streams and 1..14 symbols.)
+ *
+ * Checks, all before the first HIP call.  NRX_ERR_INVALID_ARG: a NULL io / grid / samples, an unknown
+ * precision or grid_layout, a grid or samples pointer not aligned to its complex element (8 bytes f32, 16
+ * bytes f64; a CGNN grid to its real element), modulate with pa_asat > 0 and a pa_smoothness that is not
+ * finite and > 0.  NRX_ERR_SHAPE: fft_size not a power of two in 64..4096, B outside 1..65535, S outside
+ * 1..16, T outside 1..14, F outside 1..N, first_bin outside -1..N-F, a cp_length outside 0..N, demodulate
+ * with timing_advance outside 0..min cp_length, num_samples < start[T]. */
+#define NRX_OFDM_F32 0
+#define NRX_OFDM_F64 1
+#define NRX_OFDM_GRID_PLANAR 0   /* [B][S][F][T] complex (re, im): the generator's x / x' layout */
+#define NRX_OFDM_GRID_CGNN   1   /* [B][F][T][2S], Re s0..s(S-1) then Im s0..: nrx_io.y */
+typedef struct nrx_ofdm_io {
+  int32_t batch, num_streams, grid_subcarriers, num_symbols; /* B 1..65535, S 1..16, F 1..N, T 1..14 */
+  int32_t fft_size;        /* N: a power of two, 64..4096 */
+  int32_t first_bin;       /* fftshifted index of grid subcarrier 0, 0..N-F; -1 = N/2 - F/2 (floor) */
+  int32_t cp_length[14];   /* per symbol, 0..N */
+  int32_t precision;       /* NRX_OFDM_F32 / _F64: element type of grid AND samples */
+  int32_t grid_layout;
+  int32_t timing_advance;  /* demodulate: d = -l_min, 0..min(cp_length) */
+  int32_t offset[16];      /* demodulate, per stream: added to every window start; may be negative */
+  int64_t num_samples;     /* L: samples per (b, s) row, >= sum_t (cp_length[t] + N) */
+  double  pa_asat;         /* modulate: Rapp saturation amplitude; <= 0 = linear */
+  double  pa_smoothness;   /* modulate: p > 0, read only when pa_asat > 0 */
+  void*   grid;
+  void*   samples;         /* [B][S][L] complex (re, im) */
+} nrx_ofdm_io;
+
+int nrx_ofdm_modulate(const nrx_ofdm_io* io, void* stream);
+int nrx_ofdm_demodulate(const nrx_ofdm_io* io, void* stream);
+
+/* The slot generator with a time-domain transmit stage: x' = demodulate(impair(modulate(x))) between the
+ * transmit grid and the channel, the construction of the reference's hardware-impairment layer
+ * (utils/impairments.py:67-108), for the two transmit-side effects without a closed form on the grid:
+ *   - a power-amplifier non-linearity: the Rapp curve above with A = sqrt(F / N) 10^(pa_ibo_db / 20), an
+ *     input back-off over the nominal mean sample power F / N of the unit-energy grid; no
+ *     re-normalisation after compression, as with an amplifier at a fixed drive;
+ *   - a timing error per port: delay[u] >= 0 samples, that user's signal arrives this late.  The receive
+ *     windows stay where they are (offset[u] = -delay[u], timing_advance = 0), so a delay inside the
+ *     cyclic prefix is the frequency ramp e^{-j 2 pi delay k_f / N}, k_f = f + first_bin - N/2 (signed), and
+ *     one beyond it adds inter-symbol and inter-carrier interference; symbol 0 reads zeros before the row.
+ * All of it in f64 (NRX_OFDM_F64, the PLANAR layout).  The channel acts on x'; y, h_hat and the Aerial
+ * outputs follow from it; the LS step still divides by the clean pilot; bits, active ports, MCS and noise
+ * keep their draws, so curves with and without the stage are paired.
+ *   - h_with_delay = 1 multiplies h[b,u,f,t] by e^{-j 2 pi delay[u] k_f / N}: the exact effective channel for
+ *     a delay inside the cyclic prefix and the dominant term beyond it (f64 arithmetic on the f32 h,
+ *     rounded once more).  0 leaves h the channel alone.
+ *   - x_out (optional, device [B][U][F][14] complex f64, 8-byte aligned) receives x' of every (slot, user).
+ * td == NULL is exactly nrx_generate_slots_cir: nothing new is launched, the workspace and the bits are the
+ * same.  Otherwise the workspace grows by x' and the sample buffer [B][U][L] complex f64, L = sum_t
+ * (cp_length[t] + N) (nrx_gen_workspace_size_td): about 250 MB at B = 128, U = 2, N = 4096.  Slot
+ * slot_offset + b stays a pure function of the global slot index; no atomics, the same bits on every call.
+ * NRX_ERR_INVALID_ARG: a td together with a cfo that has a non-zero offset (one transmit-side stage per
+ * call), a negative delay of a port < U, pa_enable or h_with_delay outside {0, 1}, with pa_enable a
+ * non-finite pa_ibo_db or a pa_smoothness that is not finite and > 0, an x_out that is not 8-byte aligned.
+ * NRX_ERR_SHAPE: fft_size, first_bin and cp_length as for nrx_ofdm_io with F = num_subcarriers.  The other
+ * checks are those of nrx_generate_slots_cir, all before the first HIP call. */
+typedef struct nrx_gen_td {
+  int32_t fft_size, first_bin;   /* as nrx_ofdm_io; F <= N */
+  int32_t cp_length[14];
+  int32_t delay[16];             /* per port, samples, >= 0: that user's signal arrives this late */
+  int32_t pa_enable;             /* 0 / 1 */
+  int32_t h_with_delay;          /* 0 / 1 */
+  double  pa_ibo_db;             /* input back-off over the nominal mean sample power F/N */
+  double  pa_smoothness;
+  double* x_out;                 /* optional, device [B][U][F][14] complex f64: x' of every (slot, user) */
+} nrx_gen_td;
+
+int nrx_gen_workspace_size_td(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
+                              const nrx_gen_cir* cir, const nrx_gen_td* td, size_t* bytes);
+int nrx_generate_slots_td(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                          const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
+                          const nrx_gen_out* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Uncoded error counters of one batch (sim_ber's counting, scripts/evaluate.py:193-202,
  * with the active-port masking of E2E_Model._mask_active_dmrs, e2e_model.py:195-209):
  * counts[u][0..3] += (bit errors, bits, block errors, blocks) over the active (slot, user)

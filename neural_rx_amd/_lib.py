@@ -31,6 +31,9 @@ PRECISIONS = {"f16": NRX_PREC_F16, "fp16": NRX_PREC_F16, "f32x": NRX_PREC_F32X,
 # nrx_cfo_io.ref_mode (NRX_CFO_REF_*)
 CFO_REF_NEAREST_DMRS = 0
 CFO_REF_ZERO = 1
+# nrx_ofdm_io.precision / grid_layout (NRX_OFDM_*)
+OFDM_PRECISIONS = {"f32": 0, "f64": 1}
+OFDM_LAYOUTS = {"planar": 0, "cgnn": 1}
 # enum nrx_y_layout
 Y_LAYOUTS = {"cgnn": 0, "sionna": 1, "split": 2}
 KERNELS = ["norm", "state_init", "state_update", "forward", "state_update_rr", "combine", "state_update_col",
@@ -131,6 +134,18 @@ class nrx_gen_cir(ctypes.Structure):
                 + _ptr("a", "tau", "index"))
 
 
+class nrx_ofdm_io(ctypes.Structure):
+    _fields_ = (_i32("batch", "num_streams", "grid_subcarriers", "num_symbols", "fft_size", "first_bin")
+                + [("cp_length", I32 * 14)] + _i32("precision", "grid_layout", "timing_advance")
+                + [("offset", I32 * 16), ("num_samples", ctypes.c_int64)] + _f64("pa_asat", "pa_smoothness")
+                + _ptr("grid", "samples"))
+
+
+class nrx_gen_td(ctypes.Structure):
+    _fields_ = (_i32("fft_size", "first_bin") + [("cp_length", I32 * 14), ("delay", I32 * 16)]
+                + _i32("pa_enable", "h_with_delay") + _f64("pa_ibo_db", "pa_smoothness") + _ptr("x_out"))
+
+
 class nrx_count_io(ctypes.Structure):
     _fields_ = GRID + _i32("num_heads") + MCS + _ptr("llr", "bits", "mcs", "active", "counts")
 
@@ -196,6 +211,7 @@ def _signatures():
     RC, I, V, Z, PZ = c.c_int, c.c_int32, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)
     desc, gen, chan, cfo, dmrs, cir, out = (P(nrx_desc), P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo),
                                             P(nrx_gen_dmrs), P(nrx_gen_cir), P(nrx_gen_out))
+    td = P(nrx_gen_td)
     run = [V, Z, V]          # workspace, workspace_bytes, stream
     return {
         "nrx_create": (RC, [desc, P(V), P(c.c_int64), I, I, P(V)]),
@@ -229,6 +245,10 @@ def _signatures():
         "nrx_gen_workspace_size_cir": (RC, [gen, cfo, dmrs, cir, PZ]),
         "nrx_generate_slots_cir": (RC, [gen, chan, cfo, dmrs, cir, out] + run),
         "nrx_generate_taps": (RC, [gen, chan, V, V] + run),
+        "nrx_ofdm_modulate": (RC, [P(nrx_ofdm_io), V]),
+        "nrx_ofdm_demodulate": (RC, [P(nrx_ofdm_io), V]),
+        "nrx_gen_workspace_size_td": (RC, [gen, cfo, dmrs, cir, td, PZ]),
+        "nrx_generate_slots_td": (RC, [gen, chan, cfo, dmrs, cir, td, out] + run),
         "nrx_count_errors": (RC, [P(nrx_count_io), V]),
         "nrx_cfo_estimate": (RC, [P(nrx_cfo_io), V]),
         "nrx_cfo_rotate": (RC, [P(nrx_cfo_io), V]),

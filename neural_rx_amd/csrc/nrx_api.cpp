@@ -786,21 +786,63 @@ static int check_gen_cir(const nrx_gen_desc* d, const nrx_gen_cir* cir) {
   return NRX_OK;
 }
 
-// the generator's workspace: its own, then the x' of a CFO, the pilot table, the replayed H
-static size_t gen_need(const nrx_gen_desc* d, bool cfo_on, const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir) {
+// The OFDM numerology that nrx_ofdm_io and nrx_gen_td share: N a power of two in 64..4096, F <= N, first_bin
+// -1 or 0..N-F, the cyclic prefix of the first T symbols in 0..N; *min_cp (optional): the shortest of them
+static int check_ofdm_numerology(int N, const char* f_name, int F, int first_bin, const int32_t* cp, int T,
+                                 int* min_cp = nullptr) {
+  if (N < 64 || N > 4096 || (N & (N - 1))) return fail(NRX_ERR_SHAPE, "fft_size must be a power of two in 64..4096");
+  if (int rc = check_range(f_name, F, 1, N)) return rc;
+  if (int rc = check_range("first_bin", first_bin, -1, N - F)) return rc;
+  int lo = N;
+  for (int t = 0; t < T; ++t) {
+    if (int rc = check_range("cp_length", cp[t], 0, N)) return rc;
+    lo = cp[t] < lo ? cp[t] : lo;
+  }
+  if (min_cp) *min_cp = lo;
+  return NRX_OK;
+}
+
+// the time-domain transmit stage (nrx_generate_slots_td), after check_gen and check_gen_cfo
+static int check_gen_td(const nrx_gen_desc* d, const nrx_gen_td* td, bool cfo_on) {
+  if (!td) return NRX_OK;
+  if (cfo_on) return fail(NRX_ERR_INVALID_ARG, "a td and a cfo with a non-zero offset: one transmit-side stage per call");
+  if (int rc = check_ofdm_numerology(td->fft_size, "num_subcarriers", d->num_subcarriers, td->first_bin, td->cp_length, kT)) return rc;
+  for (int u = 0; u < d->num_tx; ++u)
+    if (td->delay[u] < 0) return fail(NRX_ERR_INVALID_ARG, "per-port delay must be >= 0");
+  if (int rc = check_range("pa_enable", td->pa_enable, 0, 1, NRX_ERR_INVALID_ARG)) return rc;
+  if (int rc = check_range("h_with_delay", td->h_with_delay, 0, 1, NRX_ERR_INVALID_ARG)) return rc;
+  if (td->pa_enable) {
+    if (!std::isfinite(td->pa_ibo_db)) return fail(NRX_ERR_INVALID_ARG, "pa_ibo_db must be finite");
+    if (int rc = check_pos("pa_smoothness", td->pa_smoothness)) return rc;
+  }
+  if ((uintptr_t)td->x_out & 7) return fail(NRX_ERR_INVALID_ARG, "x_out must be 8-byte aligned");
+  return NRX_OK;
+}
+
+// the generator's workspace: its own, then the x' of a CFO or the x' and samples of a td, the pilot table,
+// the replayed H
+static size_t gen_need(const nrx_gen_desc* d, bool cfo_on, const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir,
+                       const nrx_gen_td* td = nullptr) {
   return gen_workspace_bytes(*d, nullptr, nullptr) + (cfo_on ? cfo_workspace_bytes(*d) : 0) +
-         (dmrs ? dmrs_workspace_bytes(*d) : 0) + (cir ? cir_workspace_bytes(*d) : 0);
+         (td ? td_workspace_bytes(*d, *td) : 0) + (dmrs ? dmrs_workspace_bytes(*d) : 0) +
+         (cir ? cir_workspace_bytes(*d) : 0);
 }
 
 int nrx_gen_workspace_size_cir(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
                                const nrx_gen_cir* cir, size_t* bytes) {
+  return nrx_gen_workspace_size_td(desc, cfo, dmrs, cir, nullptr, bytes);
+}
+
+int nrx_gen_workspace_size_td(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
+                              const nrx_gen_cir* cir, const nrx_gen_td* td, size_t* bytes) {
   if (int rc = check_gen(desc)) return rc;
   GenCfo g{};
   bool on;
   if (int rc = check_gen_cfo(desc, cfo, &g, &on)) return rc;
   if (int rc = check_gen_dmrs(desc, dmrs)) return rc;
   if (int rc = check_gen_cir(desc, cir)) return rc;
-  return store_size(bytes, gen_need(desc, on, dmrs, cir));
+  if (int rc = check_gen_td(desc, td, on)) return rc;
+  return store_size(bytes, gen_need(desc, on, dmrs, cir, td));
 }
 
 // NULL chan: every port has the desc's scalars, no mixing
@@ -820,6 +862,12 @@ static int check_gen_chan(const nrx_gen_desc* desc, const nrx_gen_chan* chan, nr
 int nrx_generate_slots_cir(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
                            const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_out* out, void* workspace,
                            size_t workspace_bytes, void* stream) {
+  return nrx_generate_slots_td(desc, chan, cfo, dmrs, cir, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+int nrx_generate_slots_td(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                          const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
+                          const nrx_gen_out* out, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_gen(desc)) return rc;
   if (cir && chan) return fail(NRX_ERR_INVALID_ARG, "chan must be NULL with a cir: the dataset is the channel");
   nrx_gen_chan c{};
@@ -829,15 +877,58 @@ int nrx_generate_slots_cir(const nrx_gen_desc* desc, const nrx_gen_chan* chan, c
   if (int rc = check_gen_cfo(desc, cfo, &g, &cfo_on)) return rc;
   if (int rc = check_gen_dmrs(desc, dmrs)) return rc;
   if (int rc = check_gen_cir(desc, cir)) return rc;
+  if (int rc = check_gen_td(desc, td, cfo_on)) return rc;
   if (!out || !out->y) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (out->bits)
     if (int rc = check_bits_stride(out->bits_stride, desc->mcs_bits, desc->num_mcs)) return rc;
   if ((out->y_real == nullptr) != (out->y_imag == nullptr))
     return fail(NRX_ERR_INVALID_ARG, "Aerial outputs come in (real, imag) pairs");
   if (int rc = check_aerial_list(out->h_ls_real, out->h_ls_imag, desc->num_subcarriers)) return rc;
-  if (int rc = check_workspace(workspace, workspace_bytes, gen_need(desc, cfo_on, dmrs, cir), 1)) return rc;
-  return launched(launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr, dmrs, cir),
-                  "slot generator launch");
+  if (int rc = check_workspace(workspace, workspace_bytes, gen_need(desc, cfo_on, dmrs, cir, td), 1)) return rc;
+  return launched(
+      launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr, dmrs, cir, td),
+      "slot generator launch");
+}
+
+// nrx_ofdm_modulate / nrx_ofdm_demodulate
+static int check_ofdm(const nrx_ofdm_io* io, bool modulate) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->grid || !io->samples) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (int rc = check_range("precision", io->precision, NRX_OFDM_F32, NRX_OFDM_F64, NRX_ERR_INVALID_ARG)) return rc;
+  if (int rc = check_range("grid_layout", io->grid_layout, NRX_OFDM_GRID_PLANAR, NRX_OFDM_GRID_CGNN,
+                           NRX_ERR_INVALID_ARG))
+    return rc;
+  const uintptr_t real = io->precision == NRX_OFDM_F32 ? 4 : 8;
+  if ((uintptr_t)io->samples & (2 * real - 1))
+    return fail(NRX_ERR_INVALID_ARG, "samples must be aligned to its complex element");
+  if ((uintptr_t)io->grid & ((io->grid_layout == NRX_OFDM_GRID_PLANAR ? 2 * real : real) - 1))
+    return fail(NRX_ERR_INVALID_ARG, "grid must be aligned to its element");
+  if (modulate && io->pa_asat > 0.0)
+    if (int rc = check_pos("pa_smoothness", io->pa_smoothness)) return rc;
+  if (int rc = check_range("batch", io->batch, 1, 65535)) return rc;
+  if (int rc = check_range("num_streams", io->num_streams, 1, 16)) return rc;
+  if (int rc = check_range("num_symbols", io->num_symbols, 1, kT)) return rc;
+  int min_cp = 0;
+  if (int rc = check_ofdm_numerology(io->fft_size, "grid_subcarriers", io->grid_subcarriers, io->first_bin, io->cp_length,
+                                     io->num_symbols, &min_cp))
+    return rc;
+  if (!modulate)
+    if (int rc = check_range("timing_advance", io->timing_advance, 0, min_cp)) return rc;
+  int64_t need = 0;
+  for (int t = 0; t < io->num_symbols; ++t) need += io->cp_length[t] + io->fft_size;
+  if (io->num_samples < need)
+    return fail(NRX_ERR_SHAPE, "num_samples must be >= " + std::to_string(need) + ", the symbols with their prefixes");
+  return NRX_OK;
+}
+
+int nrx_ofdm_modulate(const nrx_ofdm_io* io, void* stream) {
+  if (int rc = check_ofdm(io, true)) return rc;
+  return launched(launch_ofdm(*io, true, (hipStream_t)stream), "ofdm modulator launch");
+}
+
+int nrx_ofdm_demodulate(const nrx_ofdm_io* io, void* stream) {
+  if (int rc = check_ofdm(io, false)) return rc;
+  return launched(launch_ofdm(*io, false, (hipStream_t)stream), "ofdm demodulator launch");
 }
 
 int nrx_generate_taps(const nrx_gen_desc* desc, const nrx_gen_chan* chan, float* a_out, float* tau_out,

@@ -177,9 +177,11 @@ struct GenCfo;
 // behind everything else, and h_hat / the Aerial list come from launch_ls_estimate
 // cir (optional, nrx_generate_slots_cir): the channel is replayed from the caller's impulse responses;
 // H in f64 and its energy sums (cir_workspace_bytes) lie behind the pilot table
+// td (optional, nrx_generate_slots_td; never with a cfo): the time-domain transmit stage; its x' lies where
+// the CFO's would, behind the generator's own workspace, and its sample buffer behind that (td_workspace_bytes)
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
                            hipStream_t st, const GenCfo* cfo = nullptr, const nrx_gen_dmrs* dmrs = nullptr,
-                           const nrx_gen_cir* cir = nullptr);
+                           const nrx_gen_cir* cir = nullptr, const nrx_gen_td* td = nullptr);
 size_t dmrs_workspace_bytes(const nrx_gen_desc& d);
 // nrx_generate_taps: the finished taps and delays of the built-in channel, rounded to f32
 hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, float* a_out, float* tau_out, void* ws,
@@ -210,6 +212,14 @@ hipError_t launch_cfo_apply(const nrx_gen_desc& d, const GenCfo& c, const double
 hipError_t launch_cfo_h_phase(const nrx_gen_desc& d, const GenCfo& c, float* h, hipStream_t st);
 hipError_t launch_cfo_estimate(const nrx_cfo_io& io, hipStream_t st);
 hipError_t launch_cfo_rotate(const nrx_cfo_io& io, hipStream_t st);
+
+// OFDM modulation / demodulation and the generator's time-domain stage (nrx_ofdm.hip); io validated by
+// nrx_ofdm_modulate / nrx_ofdm_demodulate, td by nrx_generate_slots_td.  launch_td_apply: x [B][U][F][14]
+// complex f64 -> x' at the start of ws (td_workspace_bytes), the samples behind it
+hipError_t launch_ofdm(const nrx_ofdm_io& io, bool modulate, hipStream_t st);
+size_t td_workspace_bytes(const nrx_gen_desc& d, const nrx_gen_td& td);
+hipError_t launch_td_apply(const nrx_gen_desc& d, const nrx_gen_td& td, const double* x, void* ws, hipStream_t st);
+hipError_t launch_td_h_phase(const nrx_gen_desc& d, const nrx_gen_td& td, float* h, hipStream_t st);
 
 // LMMSE + max-log baseline detector (nrx_lmmse.hip); io validated by nrx_lmmse_detect
 hipError_t launch_lmmse(const nrx_lmmse_io& io, hipStream_t st);

@@ -615,15 +615,18 @@ hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, floa
 }
 
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
-                           hipStream_t st, const GenCfo* cfo, const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir) {
+                           hipStream_t st, const GenCfo* cfo, const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir,
+                           const nrx_gen_td* td) {
   GenWs w;
   const size_t own = gen_workspace_bytes(d, &w, (char*)ws);
+  // the transmit-side stage's block behind the generator's own: the x' of a CFO, or x' and the samples of a td
+  const size_t tx = cfo ? cfo_workspace_bytes(d) : (td ? td_workspace_bytes(d, *td) : 0);
   const int64_t B = d.batch, U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols, A = d.num_rx_ant;
   auto blocks = [](int64_t n) { return (unsigned)((n + 255) / 256); };
   launch_taps(d, c, w, o, /*taps=*/!cir, st);      // a replayed channel keeps the active ports and the MCS
   GenDmrs dm{};
   if (dmrs) {
-    dm.ptab = reinterpret_cast<float*>((char*)ws + own + (cfo ? cfo_workspace_bytes(d) : 0));
+    dm.ptab = reinterpret_cast<float*>((char*)ws + own + tx);
     dm.pmax = (int)((F + 1) / 2);
     for (int u = 0; u < U; ++u) {
       dm.focc |= (unsigned)dmrs->focc[u] << u;
@@ -645,8 +648,12 @@ hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const n
                                         reinterpret_cast<double*>(wr.x), st))
       return e;
   }
+  if (td) {        // x' = demodulate(impair(modulate(x))), in the same place
+    wr.x = reinterpret_cast<double2*>((char*)ws + own);
+    if (hipError_t e = launch_td_apply(d, *td, reinterpret_cast<const double*>(w.x), wr.x, st)) return e;
+  }
   if (cir) {
-    char* cws = (char*)ws + own + (cfo ? cfo_workspace_bytes(d) : 0) + (dmrs ? dmrs_workspace_bytes(d) : 0);
+    char* cws = (char*)ws + own + tx + (dmrs ? dmrs_workspace_bytes(d) : 0);
     if (hipError_t e = launch_cir_rx(d, *cir, reinterpret_cast<const double*>(wr.x), cws, o.y, o.h, o.y_real,
                                      o.y_imag, st))
       return e;
@@ -656,6 +663,8 @@ hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const n
   }
   if (cfo && cfo->h_with_phase && o.h)
     if (hipError_t e = launch_cfo_h_phase(d, *cfo, o.h, st)) return e;
+  if (td && td->h_with_delay && o.h)
+    if (hipError_t e = launch_td_h_phase(d, *td, o.h, st)) return e;
   if (dmrs) {      // one definition: the receiver-side estimator, on this call's y, pilot table and active mask
     if (!o.h_hat && !o.h_ls_real) return hipGetLastError();
     nrx_ls_io io{};

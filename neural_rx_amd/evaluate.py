@@ -26,6 +26,10 @@ point without errors; ``target_bler`` ends it once the BLER falls below the targ
 perfect-CSI systems and the NMSE see the diagonal of the effective channel; the reference hands its
 perfect-CSI baselines the un-rotated channel, with which they collapse.
 
+``-td_fft_size N`` puts the time-domain transmit stage of ``GenParams.td`` in front of the channel:
+``-timing_offset`` (a late arrival per user) and ``-pa_ibo_db`` (a Rapp power amplifier) act on its samples, and
+the generator runs with ``h_with_delay`` for the same reason.
+
 ``-dmrs_cover`` gives the ``-num_tx_eval`` users orthogonal cover-coded DMRS ports (``ls.DMRSPorts``):
 ``h_hat`` is then the despreading LS estimate and users of one CDM group no longer collide on their
 pilots; ``-dmrs_symbols 2 3 10 11`` supplies the symbol pairs that more than four ports need.
@@ -42,7 +46,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .config import get_config
-from .generator import SCENARIOS, GenParams, SlotGenerator, count_errors, ebno_to_no, rx_correlation, scenario
+from .generator import (SCENARIOS, GenParams, SlotGenerator, TimeDomain, count_errors, ebno_to_no, rx_correlation,
+                        scenario)
 from .baseline import BaselineReceiver
 from .chest import COV_SLOT_OFFSET, EstimatorBaselineReceiver, estimate_covariance
 from .cfo import CFOCompensator
@@ -416,7 +421,22 @@ def main(argv=None):
     ap.add_argument("-dmrs_symbols", type=int, nargs="+", default=None, metavar="T",
                     help="DMRS symbols in place of the config's, ascending, at most 4; the positional encoding, the "
                          "data REs, the pilot overhead of Eb/N0 and the LDPC code size follow")
+    ap.add_argument("-td_fft_size", type=int, default=None, metavar="N",
+                    help="a time-domain transmit stage between the grid and the channel (GenParams.td): OFDM "
+                         "modulation at FFT size N (a power of two, 64..4096, at least the grid), the impairments "
+                         "below on the samples, demodulation; the generator then runs with h_with_delay")
+    ap.add_argument("-td_cp", type=int, default=None, metavar="L", help="cyclic prefix in samples (default 9 N / 128)")
+    ap.add_argument("-pa_ibo_db", type=float, default=None, metavar="X",
+                    help="Rapp power amplifier at this input back-off over the nominal sample power (needs -td_fft_size)")
+    ap.add_argument("-pa_smoothness", type=float, default=2.0, metavar="P", help="the Rapp curve's p")
+    ap.add_argument("-timing_offset", type=int, nargs="+", default=None, metavar="D",
+                    help="samples by which a user's signal arrives late, one value or one per user (needs "
+                         "-td_fft_size); beyond the cyclic prefix it is inter-symbol interference")
     a = ap.parse_args(argv)
+    if a.td_fft_size is None and (a.pa_ibo_db is not None or a.timing_offset is not None or a.td_cp is not None):
+        ap.error("-pa_ibo_db, -timing_offset and -td_cp act on the samples of the time-domain stage: give -td_fft_size")
+    if a.td_fft_size is not None and (a.cfo_hz is not None or a.cfo_ppm is not None):
+        ap.error("-td_fft_size and a CFO are two transmit-side stages: give one")
     if a.cfo_hz is not None and a.cfo_ppm is not None:
         ap.error("-cfo_hz and -cfo_ppm are two ways to say the same thing: give one")
     if (a.channel == "dataset") != (a.cir_file is not None):
@@ -457,6 +477,11 @@ def main(argv=None):
         a.carrier_frequency_hz / 1e6 * a.cfo_ppm if a.cfo_ppm is not None else None
     if cfo_hz is not None:
         params = dataclasses.replace(params, cfo_hz=cfo_hz, cfo_constant=a.cfo_constant, h_with_phase=True)
+    if a.td_fft_size is not None:
+        delay = a.timing_offset if a.timing_offset is not None else [0]
+        params = dataclasses.replace(params, td=TimeDomain(
+            fft_size=a.td_fft_size, cp=a.td_cp, delay=delay[0] if len(delay) == 1 else tuple(delay),
+            pa_ibo_db=a.pa_ibo_db, pa_smoothness=a.pa_smoothness, h_with_delay=True))
     # a correlated channel: the LMMSE estimator takes the spatial covariance unless -chest_2d keeps it out
     # (a replayed dataset counts as one: its antennas are as correlated as its geometry makes them)
     chest3 = (params.rx_corr is not None or params.cir is not None) and not a.chest_2d
@@ -541,6 +566,9 @@ def main(argv=None):
                 # rms of eps_hat - eps (in subcarrier spacings) over this rank's active (slot, user) pairs
                 d["cfo"]["eps_rms_error"] = [cfo_stats.rms(ebno_to_no(float(e), len(params.dmrs_symbols)))
                                              for e in res.ebno_db]
+        if params.td is not None:                  # a run without the stage keeps the keys it always had
+            d["td"] = dict(fft_size=params.td.fft_size, cp=params.td.cp_list(), delay=params.td.delay_per_port(u),
+                           pa_ibo_db=params.td.pa_ibo_db, pa_smoothness=params.td.pa_smoothness, h_with_delay=True)
         if base:
             d["baselines"] = {name: r.as_dict() for name, r in base.items()}
         for name, points in soft.items():

@@ -26,6 +26,11 @@ of ``neural_rx_amd/ls.py`` and ``SlotBatch.pilots`` is the pilot table an extern
 ``GenParams.cir`` (a ``cir.CIRChannel``) replaces the tapped-delay line by a replayed set of channel impulse
 responses, through ``nrx_generate_slots_cir``; ``SlotGenerator.export_taps`` writes the built-in channel in
 that format (``nrx_generate_taps``).
+
+``GenParams.td`` (a ``TimeDomain``) puts a time-domain transmit stage between the transmit grid and the channel,
+``x' = demodulate(impair(modulate(x)))`` through ``nrx_generate_slots_td``: a per-user timing error and a Rapp
+power amplifier, the two transmit-side effects without a closed form on the grid (the construction of the
+reference's utils/impairments.py:67-108; the transforms are those of ``neural_rx_amd/ofdm.py``).
 """
 from __future__ import annotations
 
@@ -39,6 +44,7 @@ from ._call import Workspace, fill_dmrs, fill_grid, fill_mcs, ptr, ref, require,
 from .cir import SELECT, CIRChannel, CIRDataset
 from .config import NRXConfig, dmrs_symbols, get_config, user_cdm_groups
 from .ls import DMRSPorts
+from .ofdm import default_cp
 
 NUM_SYMBOLS = 14
 
@@ -49,6 +55,50 @@ def ebno_to_no(ebno_db: float, num_dmrs_symbols: int = 2, num_symbols: int = NUM
     With two CDM groups without data every RE of a DMRS symbol is a pilot RE."""
     ebno_db = ebno_db - 10.0 * np.log10(1.0 - num_dmrs_symbols / num_symbols)
     return float(10.0 ** (-ebno_db / 10.0))
+
+
+@dataclasses.dataclass
+class TimeDomain:
+    """The time-domain transmit stage (include/nrx.h nrx_gen_td).  ``delay``: samples by which each port's
+    signal arrives late, one value or one per port; ``pa_ibo_db``: the Rapp amplifier's input back-off over the
+    nominal mean sample power F / N, None = a linear amplifier; ``h_with_delay``: ``SlotBatch.h`` carries the
+    delay's frequency ramp, the effective channel a perfect-CSI receiver should be scored against."""
+    fft_size: int
+    cp: Optional[object] = None        # one int or 14; None = ofdm.default_cp(fft_size)
+    delay: object = 0
+    pa_ibo_db: Optional[float] = None
+    pa_smoothness: float = 2.0
+    h_with_delay: bool = False
+    first_bin: int = -1
+
+    def cp_list(self) -> list:
+        cp = default_cp(self.fft_size) if self.cp is None else self.cp
+        v = [int(c) for c in np.atleast_1d(cp)]
+        if len(v) == 1:
+            v = v * NUM_SYMBOLS
+        if len(v) != NUM_SYMBOLS:
+            raise ValueError(f"cp needs one value or one per symbol: {NUM_SYMBOLS}, got {len(v)}")
+        return v
+
+    def delay_per_port(self, num_tx: int) -> list:
+        v = [int(d) for d in np.atleast_1d(self.delay)]
+        if len(v) == 1:
+            v = v * num_tx
+        if len(v) != num_tx:
+            raise ValueError(f"delay needs one value or one per port: {num_tx}, got {len(v)}")
+        return v
+
+    def struct(self, num_tx: int) -> _lib.nrx_gen_td:
+        t = _lib.nrx_gen_td()
+        t.fft_size, t.first_bin = int(self.fft_size), int(self.first_bin)
+        for k, c in enumerate(self.cp_list()):
+            t.cp_length[k] = c
+        for u, d in enumerate(self.delay_per_port(num_tx)[:16]):
+            t.delay[u] = d
+        t.pa_enable, t.h_with_delay = int(self.pa_ibo_db is not None), int(self.h_with_delay)
+        t.pa_ibo_db = 0.0 if self.pa_ibo_db is None else float(self.pa_ibo_db)
+        t.pa_smoothness = float(self.pa_smoothness)
+        return t
 
 
 @dataclasses.dataclass
@@ -84,8 +134,13 @@ class GenParams:
     # a replayed channel-impulse-response dataset (cir.CIRChannel) in place of the tapped-delay line; None =
     # the built-in channel.  Excludes user_profiles / rx_corr: a dataset brings its own structure.
     cir: Optional[CIRChannel] = None
+    # a time-domain transmit stage (TimeDomain): per-user timing error and power amplifier; None = the generator
+    # without it.  Excludes cfo_hz: one transmit-side stage per generator.
+    td: Optional[TimeDomain] = None
 
     def __post_init__(self):
+        if self.td is not None and self.cfo_hz is not None:
+            raise ValueError("td and cfo_hz are two transmit-side stages: a generator takes one of them")
         if self.cir is not None:
             if self.user_profiles is not None or self.rx_corr is not None:
                 raise ValueError("a cir dataset is the channel: user_profiles and rx_corr do not apply to it")
@@ -239,17 +294,20 @@ class SlotBatch:
     h_ls_imag: "object" = None
     cfo_eps: "object" = None   # [B, U] f64: the carrier frequency offset in subcarrier spacings, or None
     pilots: "object" = None    # [2, Pmax, nd, 2] f32: the DMRS base sequence (GenParams.dmrs), or None
+    x_td: "object" = None      # [B, U, F, T] c128: the grid behind the time-domain stage (GenParams.td), or None
 
 
 class SlotGenerator:
     """``gen(batch, no, slot_offset) -> SlotBatch`` on one GPU.  Slot ``slot_offset + b``
     is the same slot whichever call, rank or batch split generates it."""
 
-    def __init__(self, params: GenParams, device: int = 0, want_h: bool = False, aerial: bool = False):
+    def __init__(self, params: GenParams, device: int = 0, want_h: bool = False, aerial: bool = False,
+                 want_x: bool = False):
         self.p = params
         self.device = device
         self.want_h = want_h
         self.aerial = aerial
+        self.want_x = want_x            # SlotBatch.x_td (with GenParams.td)
         self._lib = _lib.load()
         self._ws = Workspace()
         self._bufs = {}
@@ -293,15 +351,16 @@ class SlotGenerator:
             self._cir_tau = self._cir_data.tau.contiguous()
             r.a, r.tau = self._cir_a.data_ptr(), self._cir_tau.data_ptr()
             self._cir = r
+        self._td = params.td.struct(params.num_tx) if params.td is not None else None
 
     def workspace_bytes(self, batch: int) -> int:
-        """what ``nrx_gen_workspace_size_cir`` asks for with whichever blocks this generator has (NULL for
+        """what ``nrx_gen_workspace_size_td`` asks for with whichever blocks this generator has (NULL for
         the absent ones: the older ``nrx_gen_workspace_size*`` are that call with fewer blocks)"""
         if self._cir is not None and self._cir.select == SELECT["index"] and not self._cir.index:
             # the size is no function of the index, which comes with every call: any address passes the check
             self._cir.index = self._cir_tau.data_ptr()
-        return self._ws.size(self._lib.nrx_gen_workspace_size_cir, ref(self.p.desc(batch, 0.0)), ref(self._cfo),
-                             ref(self._dmrs), ref(self._cir))
+        return self._ws.size(self._lib.nrx_gen_workspace_size_td, ref(self.p.desc(batch, 0.0)), ref(self._cfo),
+                             ref(self._dmrs), ref(self._cir), ref(self._td))
 
     def _alloc(self, batch: int) -> SlotBatch:
         torch = _torch()
@@ -329,6 +388,8 @@ class SlotGenerator:
             sb.cfo_eps = torch.zeros((batch, U), dtype=torch.float64, device=dev)
         if self._dmrs is not None:
             sb.pilots = torch.empty((2, (F + 1) // 2, len(p.dmrs_symbols), 2), **f32)
+        if self._td is not None and self.want_x:
+            sb.x_td = torch.empty((batch, U, F, NUM_SYMBOLS), dtype=torch.complex128, device=dev)
         self._bufs = {key: sb}
         return sb
 
@@ -356,11 +417,13 @@ class SlotGenerator:
                 raise ValueError("select='index' needs cir_index")
             require("cir_index", cir_index, (batch, self.p.num_tx), torch.int32, sb.y.device)
             self._cir.index = cir_index.data_ptr()
+        if self._td is not None:
+            self._td.x_out = ptr(sb.x_td)
         # one entry point: the older nrx_generate_slots* are this call with NULL for the blocks they lack.
         # A dataset is the channel, so chan stays NULL with it (GenParams refuses the two together).
-        _lib.check(self._lib.nrx_generate_slots_cir(
-            ref(d), ref(self._chan), ref(self._cfo), ref(self._dmrs), ref(self._cir), ref(o), ws.data_ptr(), ws.numel(),
-            stream_of(sb.y, stream)))
+        _lib.check(self._lib.nrx_generate_slots_td(
+            ref(d), ref(self._chan), ref(self._cfo), ref(self._dmrs), ref(self._cir), ref(self._td), ref(o),
+            ws.data_ptr(), ws.numel(), stream_of(sb.y, stream)))
         return sb
 
     def export_taps(self, batch: int, slot_offset: int = 0, stream=None) -> CIRDataset:
