@@ -620,6 +620,95 @@ int nrx_generate_slots_td(const nrx_gen_desc* desc, const nrx_gen_chan* chan, co
                           const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
                           const nrx_gen_out* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- Time-domain channel
+ * The channel on the samples between OFDM modulation and demodulation: discrete-time taps from the path
+ * delays, applied per sample, with path gains that move inside a symbol -- the counterpart of Sionna's
+ * TimeChannel, and an addition of this project (the reference's OFDMChannel, utils/parameters.py:346-439,
+ * never leaves the frequency domain).  tests/timechan_ref.py states it in numpy.  With fs = sample_rate,
+ * sinc(0) = 1, sinc(v) = sin(pi v) / (pi v) and x read as zero outside [0, num_samples):
+ *
+ *   r[b,a,n] = sum_u sum_l g[b,u,a,l](n) v[b,u,l](n)
+ *   g(n)     = sum_{s < NS} g0[b,u,a,l,s] exp(j 2 pi fd[b,u,a,l,s] (n - n0) / fs)
+ *   v(n)     = sum_{l' = l_min..l_max} sinc(l' - tau[b,u,l] fs) x[b,u,n - l']
+ *
+ * and, with rx_mix = M, r'[a] = sum_a' M[a][a'] r[a'] (a' ascending).  The sinc is plainly truncated to
+ * l_min..l_max: no window and no re-normalisation, so the energy of a path is preserved only approximately
+ * (exactly for a delay of a whole number of samples inside the span; a fractional delay loses the tails beyond
+ * the span, of the order 1 / (pi^2 d) of the path's energy at d samples from the nearest end).
+ *
+ * One launch (csrc/nrx_timechan.hip).  Every element of r is written.  Asynchronous on `stream`; no workspace,
+ * no atomics, no allocation, no host synchronisation; the same bits on every call and for every split of the
+ * batch: a sinusoid's rotation is exact at a fixed sample stride that depends on num_rx_ant alone.
+ *
+ * Checks, all before the first HIP call.  NRX_ERR_INVALID_ARG: a NULL io / tau / g0 / fd / x / r, a g0, x, r or
+ * rx_mix not 16-byte aligned, a tau or fd not 8-byte aligned, a sample_rate that is not finite and > 0.
+ * NRX_ERR_SHAPE: batch outside 1..65535, num_tx or num_rx_ant outside 1..16, num_paths outside 1..8,
+ * num_sinusoids outside 1..16, l_min outside -255..0, l_max outside 0..255, l_max - l_min + 1 > 256,
+ * num_samples outside 1..2^31 - 1, n0 outside -2^31..2^31 - 1. */
+typedef struct nrx_tc_io {
+  int32_t batch, num_tx, num_rx_ant, num_paths, num_sinusoids; /* B, U, A, L, NS */
+  int32_t l_min, l_max;    /* l_min <= 0 <= l_max, l_max - l_min + 1 <= 256 */
+  int32_t pad_;
+  int64_t num_samples;     /* Ls: samples per (b, u) row of x and per (b, a) row of r */
+  int64_t n0;              /* the sample at which every sinusoid has the phase of its g0 */
+  double  sample_rate;     /* fs, Hz */
+  const double* tau;       /* device [B][U][L], seconds */
+  const double* g0;        /* device [B][U][A][L][NS][2] (re, im) */
+  const double* fd;        /* device [B][U][A][L][NS], Hz */
+  const double* x;         /* device [B][U][Ls][2] */
+  const double* rx_mix;    /* optional, device [A][A][2] */
+  double* r;               /* device [B][A][Ls][2] */
+} nrx_tc_io;
+
+int nrx_time_channel(const nrx_tc_io* io, void* stream);
+
+/* The slot generator with the time-domain channel in place of the per-RE product.
+ *   - Samples: the modulated x of every (slot, port) (nrx_ofdm_modulate, f64, PLANAR), fs = fft_size scs.
+ *   - Channel: nrx_time_channel with the built-in channel's own draws: tau, the sinusoid amplitudes g0 with
+ *     sqrt(pdp) folded in, the Doppler frequencies fd, per-port profiles and rx_mix of nrx_gen_chan included.
+ *     n0 = cp_length[0], so the useful part of symbol t starts at about t 1.07 / scs, the instant at which the
+ *     grid channel samples its gains; each path also carries exp(+j 2 pi (first_bin - N/2) scs tau_l), which
+ *     refers the delay ramp to grid subcarrier 0 as on the grid channel.  With zero Doppler the slot is the
+ *     realisation of the plain generator up to the sinc truncation, so curves with and without are paired.
+ *   - Receive side: the A antenna streams are demodulated with timing_advance = ta; the generator's grid
+ *     noise (the same draws) is added after demodulation, where the unitary DFT keeps it white; h_hat and the
+ *     Aerial lists come from y as always; bits, active ports and MCS keep their draws.
+ *   - h is the ISI-free diagonal of the effective channel, what perfect CSI and the NMSE are scored against:
+ *       h[b,u,f,t,a] = sum_l' hbar_t[l'] exp(-j 2 pi k_f l' / N),   k_f = f + first_bin - N/2
+ *       hbar_t[l']   = (1/N) sum_{m < N} h_{u,a}[w_t + m, l'],      w_t = start[t] + cp_length[t] - ta
+ *       h_{u,a}[n,l'] = sum_l g(n) sinc(l' - tau_l fs)
+ *     It is exact when l_max <= cp_length - ta and ta >= -l_min, and the dominant term otherwise: a delay
+ *     beyond the prefix adds inter-symbol, a gain that moves inside the window inter-carrier interference.
+ *   - l_max < 0 stands for ceil(max over ports of max_delay_s fs) + 6; the usual l_min is -6.
+ *   - r_out (optional, device [B][A][Ls] complex f64, Ls = sum_t (cp_length[t] + N)) receives the noise-free
+ *     received samples, x_out (optional, device [B][U][Ls] complex f64) the transmitted ones.
+ * tc == NULL is exactly nrx_generate_slots_td: the same launches, workspace and bits.  Cover-coded DMRS ports
+ * (dmrs) compose: they act on x.  The workspace grows by both sample buffers, the sinusoids and the antenna
+ * grids (nrx_gen_workspace_size_tc): about 750 MB at B = 128, U = 2, A = 4, N = 4096.  Slot slot_offset + b
+ * stays a pure function of the global slot index; no atomics, the same bits on every call.
+ * NRX_ERR_INVALID_ARG: a tc together with a td, a cir or a cfo that has a non-zero offset (one sample-domain
+ * stage per call), an r_out or x_out that is not 16-byte aligned.  NRX_ERR_SHAPE: fft_size, first_bin and
+ * cp_length as for nrx_ofdm_io with F = num_subcarriers, timing_advance outside 0..min cp_length, l_min outside
+ * -255..0, a resolved l_max outside 0..255 or a span l_max - l_min + 1 > 256.  The other checks are those of
+ * nrx_generate_slots_td, all before the first HIP call. */
+typedef struct nrx_gen_tc {
+  int32_t fft_size, first_bin;   /* as nrx_ofdm_io; F <= N */
+  int32_t cp_length[14];
+  int32_t l_min, l_max;          /* taps l_min..l_max; l_max < 0: from the ports' max_delay_s */
+  int32_t timing_advance;        /* 0..min(cp_length) */
+  int32_t pad_;
+  double* r_out;                 /* optional, device [B][A][Ls] complex f64 */
+  double* x_out;                 /* optional, device [B][U][Ls] complex f64 */
+} nrx_gen_tc;
+
+int nrx_gen_workspace_size_tc(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                              const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
+                              const nrx_gen_tc* tc, size_t* bytes);
+int nrx_generate_slots_tc(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                          const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
+                          const nrx_gen_tc* tc, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* Uncoded error counters of one batch (sim_ber's counting, scripts/evaluate.py:193-202,
  * with the active-port masking of E2E_Model._mask_active_dmrs, e2e_model.py:195-209):
  * counts[u][0..3] += (bit errors, bits, block errors, blocks) over the active (slot, user)

@@ -146,6 +146,17 @@ class nrx_gen_td(ctypes.Structure):
                 + _i32("pa_enable", "h_with_delay") + _f64("pa_ibo_db", "pa_smoothness") + _ptr("x_out"))
 
 
+class nrx_tc_io(ctypes.Structure):
+    _fields_ = (_i32("batch", "num_tx", "num_rx_ant", "num_paths", "num_sinusoids", "l_min", "l_max", "pad_")
+                + [("num_samples", ctypes.c_int64), ("n0", ctypes.c_int64)] + _f64("sample_rate")
+                + _ptr("tau", "g0", "fd", "x", "rx_mix", "r"))
+
+
+class nrx_gen_tc(ctypes.Structure):
+    _fields_ = (_i32("fft_size", "first_bin") + [("cp_length", I32 * 14)]
+                + _i32("l_min", "l_max", "timing_advance", "pad_") + _ptr("r_out", "x_out"))
+
+
 class nrx_count_io(ctypes.Structure):
     _fields_ = GRID + _i32("num_heads") + MCS + _ptr("llr", "bits", "mcs", "active", "counts")
 
@@ -211,7 +222,7 @@ def _signatures():
     RC, I, V, Z, PZ = c.c_int, c.c_int32, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)
     desc, gen, chan, cfo, dmrs, cir, out = (P(nrx_desc), P(nrx_gen_desc), P(nrx_gen_chan), P(nrx_gen_cfo),
                                             P(nrx_gen_dmrs), P(nrx_gen_cir), P(nrx_gen_out))
-    td = P(nrx_gen_td)
+    td, tc = P(nrx_gen_td), P(nrx_gen_tc)
     run = [V, Z, V]          # workspace, workspace_bytes, stream
     return {
         "nrx_create": (RC, [desc, P(V), P(c.c_int64), I, I, P(V)]),
@@ -249,6 +260,9 @@ def _signatures():
         "nrx_ofdm_demodulate": (RC, [P(nrx_ofdm_io), V]),
         "nrx_gen_workspace_size_td": (RC, [gen, cfo, dmrs, cir, td, PZ]),
         "nrx_generate_slots_td": (RC, [gen, chan, cfo, dmrs, cir, td, out] + run),
+        "nrx_time_channel": (RC, [P(nrx_tc_io), V]),
+        "nrx_gen_workspace_size_tc": (RC, [gen, chan, cfo, dmrs, cir, td, tc, PZ]),
+        "nrx_generate_slots_tc": (RC, [gen, chan, cfo, dmrs, cir, td, tc, out] + run),
         "nrx_count_errors": (RC, [P(nrx_count_io), V]),
         "nrx_cfo_estimate": (RC, [P(nrx_cfo_io), V]),
         "nrx_cfo_rotate": (RC, [P(nrx_cfo_io), V]),

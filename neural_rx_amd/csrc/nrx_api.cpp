@@ -151,6 +151,14 @@ int check_nonneg(const char* name, double v) {
   return fail(NRX_ERR_INVALID_ARG, std::string(name) + " must be finite and >= 0");
 }
 
+// the taps l_min..l_max of the time-domain channel (nrx_tc_io, nrx_gen_tc)
+int check_tap_span(long l_min, long l_max) {
+  if (int rc = check_range("l_min", l_min, -255, 0)) return rc;
+  if (int rc = check_range("l_max", l_max, 0, 255)) return rc;
+  if (l_max - l_min + 1 > 256) return fail(NRX_ERR_SHAPE, "the tap span l_max - l_min + 1 must be <= 256");
+  return NRX_OK;
+}
+
 int too_small(size_t need) {
   return fail(NRX_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
 }
@@ -819,32 +827,6 @@ static int check_gen_td(const nrx_gen_desc* d, const nrx_gen_td* td, bool cfo_on
   return NRX_OK;
 }
 
-// the generator's workspace: its own, then the x' of a CFO or the x' and samples of a td, the pilot table,
-// the replayed H
-static size_t gen_need(const nrx_gen_desc* d, bool cfo_on, const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir,
-                       const nrx_gen_td* td = nullptr) {
-  return gen_workspace_bytes(*d, nullptr, nullptr) + (cfo_on ? cfo_workspace_bytes(*d) : 0) +
-         (td ? td_workspace_bytes(*d, *td) : 0) + (dmrs ? dmrs_workspace_bytes(*d) : 0) +
-         (cir ? cir_workspace_bytes(*d) : 0);
-}
-
-int nrx_gen_workspace_size_cir(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
-                               const nrx_gen_cir* cir, size_t* bytes) {
-  return nrx_gen_workspace_size_td(desc, cfo, dmrs, cir, nullptr, bytes);
-}
-
-int nrx_gen_workspace_size_td(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
-                              const nrx_gen_cir* cir, const nrx_gen_td* td, size_t* bytes) {
-  if (int rc = check_gen(desc)) return rc;
-  GenCfo g{};
-  bool on;
-  if (int rc = check_gen_cfo(desc, cfo, &g, &on)) return rc;
-  if (int rc = check_gen_dmrs(desc, dmrs)) return rc;
-  if (int rc = check_gen_cir(desc, cir)) return rc;
-  if (int rc = check_gen_td(desc, td, on)) return rc;
-  return store_size(bytes, gen_need(desc, on, dmrs, cir, td));
-}
-
 // NULL chan: every port has the desc's scalars, no mixing
 static int check_gen_chan(const nrx_gen_desc* desc, const nrx_gen_chan* chan, nrx_gen_chan* c) {
   for (int u = 0; u < desc->num_tx; ++u) {
@@ -859,6 +841,68 @@ static int check_gen_chan(const nrx_gen_desc* desc, const nrx_gen_chan* chan, nr
   return NRX_OK;
 }
 
+// the time-domain channel (nrx_generate_slots_tc), after the checks of every other stage; c: the resolved ports
+static int check_gen_tc(const nrx_gen_desc* d, const nrx_gen_chan* c, const nrx_gen_tc* tc, bool cfo_on,
+                        const nrx_gen_cir* cir, const nrx_gen_td* td) {
+  if (!tc) return NRX_OK;
+  if (cfo_on) return fail(NRX_ERR_INVALID_ARG, "a tc and a cfo with a non-zero offset: one sample-domain stage per call");
+  if (td) return fail(NRX_ERR_INVALID_ARG, "a tc and a td: one sample-domain stage per call");
+  if (cir) return fail(NRX_ERR_INVALID_ARG, "a tc and a cir: one sample-domain stage per call");
+  int min_cp = 0;
+  if (int rc = check_ofdm_numerology(tc->fft_size, "num_subcarriers", d->num_subcarriers, tc->first_bin, tc->cp_length, kT, &min_cp)) return rc;
+  if (int rc = check_range("timing_advance", tc->timing_advance, 0, min_cp)) return rc;
+  if (int rc = check_tap_span(tc->l_min, tc_resolve_l_max(*d, *c, *tc))) return rc;
+  if (((uintptr_t)tc->r_out | (uintptr_t)tc->x_out) & 15) return fail(NRX_ERR_INVALID_ARG, "r_out and x_out must be 16-byte aligned");
+  return NRX_OK;
+}
+
+// The generator's stage planner: every descriptor check of a generator call in one order, the resolved ports
+// (*c; chan_known = false for the size calls that take no chan: the desc's scalars) and offset (*g, *cfo_on),
+// and *need, the workspace: the generator's own, then the block of the one sample-domain stage (the x' of a
+// CFO, the x' and samples of a td, the buffers of a tc), the pilot table, the replayed H
+static int plan_gen(const nrx_gen_desc* d, bool chan_known, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                    const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td, const nrx_gen_tc* tc,
+                    nrx_gen_chan* c, GenCfo* g, bool* cfo_on, size_t* need) {
+  if (int rc = check_gen(d)) return rc;
+  if (cir && chan) return fail(NRX_ERR_INVALID_ARG, "chan must be NULL with a cir: the dataset is the channel");
+  if (int rc = check_gen_chan(d, chan_known ? chan : nullptr, c)) return rc;
+  if (int rc = check_gen_cfo(d, cfo, g, cfo_on)) return rc;
+  if (int rc = check_gen_dmrs(d, dmrs)) return rc;
+  if (int rc = check_gen_cir(d, cir)) return rc;
+  if (int rc = check_gen_td(d, td, *cfo_on)) return rc;
+  if (int rc = check_gen_tc(d, c, tc, *cfo_on, cir, td)) return rc;
+  *need = gen_workspace_bytes(*d, nullptr, nullptr) + (*cfo_on ? cfo_workspace_bytes(*d) : 0) +
+          (td ? td_workspace_bytes(*d, *td) : 0) + (tc ? tc_workspace_bytes(*d, *tc) : 0) +
+          (dmrs ? dmrs_workspace_bytes(*d) : 0) + (cir ? cir_workspace_bytes(*d) : 0);
+  return NRX_OK;
+}
+
+int nrx_gen_workspace_size_cir(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
+                               const nrx_gen_cir* cir, size_t* bytes) {
+  return nrx_gen_workspace_size_td(desc, cfo, dmrs, cir, nullptr, bytes);
+}
+
+int nrx_gen_workspace_size_td(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
+                              const nrx_gen_cir* cir, const nrx_gen_td* td, size_t* bytes) {
+  nrx_gen_chan c{};
+  GenCfo g{};
+  bool on;
+  size_t need = 0;
+  if (int rc = plan_gen(desc, false, nullptr, cfo, dmrs, cir, td, nullptr, &c, &g, &on, &need)) return rc;
+  return store_size(bytes, need);
+}
+
+int nrx_gen_workspace_size_tc(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                              const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
+                              const nrx_gen_tc* tc, size_t* bytes) {
+  nrx_gen_chan c{};
+  GenCfo g{};
+  bool on;
+  size_t need = 0;
+  if (int rc = plan_gen(desc, true, chan, cfo, dmrs, cir, td, tc, &c, &g, &on, &need)) return rc;
+  return store_size(bytes, need);
+}
+
 int nrx_generate_slots_cir(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
                            const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_out* out, void* workspace,
                            size_t workspace_bytes, void* stream) {
@@ -868,26 +912,51 @@ int nrx_generate_slots_cir(const nrx_gen_desc* desc, const nrx_gen_chan* chan, c
 int nrx_generate_slots_td(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
                           const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
                           const nrx_gen_out* out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_gen(desc)) return rc;
-  if (cir && chan) return fail(NRX_ERR_INVALID_ARG, "chan must be NULL with a cir: the dataset is the channel");
+  return nrx_generate_slots_tc(desc, chan, cfo, dmrs, cir, td, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+int nrx_generate_slots_tc(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                          const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
+                          const nrx_gen_tc* tc, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
+                          void* stream) {
   nrx_gen_chan c{};
-  if (int rc = check_gen_chan(desc, chan, &c)) return rc;
   GenCfo g{};
   bool cfo_on;
-  if (int rc = check_gen_cfo(desc, cfo, &g, &cfo_on)) return rc;
-  if (int rc = check_gen_dmrs(desc, dmrs)) return rc;
-  if (int rc = check_gen_cir(desc, cir)) return rc;
-  if (int rc = check_gen_td(desc, td, cfo_on)) return rc;
+  size_t need = 0;
+  if (int rc = plan_gen(desc, true, chan, cfo, dmrs, cir, td, tc, &c, &g, &cfo_on, &need)) return rc;
   if (!out || !out->y) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (out->bits)
     if (int rc = check_bits_stride(out->bits_stride, desc->mcs_bits, desc->num_mcs)) return rc;
   if ((out->y_real == nullptr) != (out->y_imag == nullptr))
     return fail(NRX_ERR_INVALID_ARG, "Aerial outputs come in (real, imag) pairs");
   if (int rc = check_aerial_list(out->h_ls_real, out->h_ls_imag, desc->num_subcarriers)) return rc;
-  if (int rc = check_workspace(workspace, workspace_bytes, gen_need(desc, cfo_on, dmrs, cir, td), 1)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, need, 1)) return rc;
   return launched(
-      launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr, dmrs, cir, td),
+      launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr, dmrs, cir, td, tc),
       "slot generator launch");
+}
+
+// nrx_time_channel
+static int check_tc(const nrx_tc_io* io) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->tau || !io->g0 || !io->fd || !io->x || !io->r) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (((uintptr_t)io->g0 | (uintptr_t)io->x | (uintptr_t)io->r | (uintptr_t)io->rx_mix) & 15)
+    return fail(NRX_ERR_INVALID_ARG, "g0, x, r and rx_mix must be 16-byte aligned");
+  if (((uintptr_t)io->tau | (uintptr_t)io->fd) & 7) return fail(NRX_ERR_INVALID_ARG, "tau and fd must be 8-byte aligned");
+  if (int rc = check_pos("sample_rate", io->sample_rate)) return rc;
+  if (int rc = check_range("batch", io->batch, 1, 65535)) return rc;
+  if (int rc = check_range("num_tx", io->num_tx, 1, kMaxUsers)) return rc;
+  if (int rc = check_range("num_rx_ant", io->num_rx_ant, 1, 16)) return rc;
+  if (int rc = check_range("num_paths", io->num_paths, 1, 8)) return rc;
+  if (int rc = check_range("num_sinusoids", io->num_sinusoids, 1, 16)) return rc;
+  if (int rc = check_tap_span(io->l_min, io->l_max)) return rc;
+  if (int rc = check_range("num_samples", io->num_samples, 1, 2147483647L)) return rc;
+  return check_range("n0", io->n0, -2147483647L - 1, 2147483647L);
+}
+
+int nrx_time_channel(const nrx_tc_io* io, void* stream) {
+  if (int rc = check_tc(io)) return rc;
+  return launched(launch_time_channel(*io, (hipStream_t)stream), "time channel launch");
 }
 
 // nrx_ofdm_modulate / nrx_ofdm_demodulate

@@ -179,9 +179,12 @@ struct GenCfo;
 // H in f64 and its energy sums (cir_workspace_bytes) lie behind the pilot table
 // td (optional, nrx_generate_slots_td; never with a cfo): the time-domain transmit stage; its x' lies where
 // the CFO's would, behind the generator's own workspace, and its sample buffer behind that (td_workspace_bytes)
+// tc (optional, nrx_generate_slots_tc; never with a cfo, a cir or a td): the time-domain channel takes the place
+// of k_gen_rx; its block (tc_workspace_bytes) lies where the other stages' would
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
                            hipStream_t st, const GenCfo* cfo = nullptr, const nrx_gen_dmrs* dmrs = nullptr,
-                           const nrx_gen_cir* cir = nullptr, const nrx_gen_td* td = nullptr);
+                           const nrx_gen_cir* cir = nullptr, const nrx_gen_td* td = nullptr,
+                           const nrx_gen_tc* tc = nullptr);
 size_t dmrs_workspace_bytes(const nrx_gen_desc& d);
 // nrx_generate_taps: the finished taps and delays of the built-in channel, rounded to f32
 hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, float* a_out, float* tau_out, void* ws,
@@ -220,6 +223,20 @@ hipError_t launch_ofdm(const nrx_ofdm_io& io, bool modulate, hipStream_t st);
 size_t td_workspace_bytes(const nrx_gen_desc& d, const nrx_gen_td& td);
 hipError_t launch_td_apply(const nrx_gen_desc& d, const nrx_gen_td& td, const double* x, void* ws, hipStream_t st);
 hipError_t launch_td_h_phase(const nrx_gen_desc& d, const nrx_gen_td& td, float* h, hipStream_t st);
+
+// The time-domain channel and the generator's receive path through it (nrx_timechan.hip); io validated by
+// nrx_time_channel, tc by nrx_generate_slots_tc.  tc_resolve_l_max: l_max, or for l_max < 0 the ceiling of the
+// longest port delay in samples + 6.  launch_tc_taps: the sinusoid draws into ws (tc_workspace_bytes) and the
+// window means of the taps into gt [B][U][A][L][14] (the generator's tap layout, so its antenna mixing applies);
+// launch_tc_rx: modulate(x) -> channel -> demodulate -> y (+ the grid noise), h from the mean taps, r_out / x_out
+hipError_t launch_time_channel(const nrx_tc_io& io, hipStream_t st);
+int tc_resolve_l_max(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_tc& tc);
+size_t tc_workspace_bytes(const nrx_gen_desc& d, const nrx_gen_tc& tc);
+hipError_t launch_tc_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_tc& tc, const double* tau,
+                          const double* spdp, double* gt, void* ws, hipStream_t st);
+hipError_t launch_tc_rx(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_tc& tc, const double* x,
+                        const double* tau, const double* gt, void* ws, float* y, float* h, float* y_re, float* y_im,
+                        hipStream_t st);
 
 // LMMSE + max-log baseline detector (nrx_lmmse.hip); io validated by nrx_lmmse_detect
 hipError_t launch_lmmse(const nrx_lmmse_io& io, hipStream_t st);

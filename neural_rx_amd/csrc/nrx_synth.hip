@@ -15,7 +15,8 @@
 //   k_gen_tx       per (slot, user, RE): Philox bits, Gray QAM / DMRS QPSK x sqrt(2), x *= active
 //   k_gen_rx       per (slot, subcarrier): the user/tap phasors of that subcarrier in LDS,
 //                  then y[a][t] = sum_u H_u x_u + AWGN (and the true channel, optional); with a replayed
-//                  channel (nrx_generate_slots_cir) the kernels of nrx_cir.hip take its place and k_gen_taps's
+//                  channel (nrx_generate_slots_cir) the kernels of nrx_cir.hip take its place and k_gen_taps's,
+//                  with the time-domain channel (nrx_generate_slots_tc) those of nrx_timechan.hip
 //   k_export_taps  per tap / delay: the finished taps and delays rounded to f32 (nrx_generate_taps)
 //   k_gen_ls       per (slot, user, RE, antenna): LS at the nearest own pilot (closed form
 //                  of the Manhattan argmin), and the Aerial pilot list (optional)
@@ -616,14 +617,25 @@ hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, floa
 
 hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
                            hipStream_t st, const GenCfo* cfo, const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir,
-                           const nrx_gen_td* td) {
+                           const nrx_gen_td* td, const nrx_gen_tc* tc) {
   GenWs w;
   const size_t own = gen_workspace_bytes(d, &w, (char*)ws);
-  // the transmit-side stage's block behind the generator's own: the x' of a CFO, or x' and the samples of a td
-  const size_t tx = cfo ? cfo_workspace_bytes(d) : (td ? td_workspace_bytes(d, *td) : 0);
+  // the sample-domain stage's block behind the generator's own: the x' of a CFO, x' and the samples of a td,
+  // or the samples, sinusoids and antenna grids of a tc
+  const size_t tx = cfo ? cfo_workspace_bytes(d)
+                        : (td ? td_workspace_bytes(d, *td) : (tc ? tc_workspace_bytes(d, *tc) : 0));
   const int64_t B = d.batch, U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols, A = d.num_rx_ant;
   auto blocks = [](int64_t n) { return (unsigned)((n + 255) / 256); };
-  launch_taps(d, c, w, o, /*taps=*/!cir, st);      // a replayed channel keeps the active ports and the MCS
+  // a replayed channel keeps the active ports and the MCS; so does the time-domain channel, whose taps are the
+  // window means of the per-sample gains, mixed over the antennas like the grid channel's
+  launch_taps(d, c, w, o, /*taps=*/!cir && !tc, st);
+  if (tc) {
+    if (hipError_t e = launch_tc_taps(d, c, *tc, w.tau, w.spdp, reinterpret_cast<double*>(w.gt), (char*)ws + own, st))
+      return e;
+    if (c.rx_mix)
+      k_gen_mix<<<(unsigned)((B * U * d.num_taps * kT + 255) / 256), 256, 0, st>>>(
+          w, c.rx_mix, (int)A, (int)(d.num_taps * kT), B * U * d.num_taps * kT);
+  }
   GenDmrs dm{};
   if (dmrs) {
     dm.ptab = reinterpret_cast<float*>((char*)ws + own + tx);
@@ -652,7 +664,12 @@ hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const n
     wr.x = reinterpret_cast<double2*>((char*)ws + own);
     if (hipError_t e = launch_td_apply(d, *td, reinterpret_cast<const double*>(w.x), wr.x, st)) return e;
   }
-  if (cir) {
+  if (tc) {
+    if (hipError_t e = launch_tc_rx(d, c, *tc, reinterpret_cast<const double*>(w.x), w.tau,
+                                    reinterpret_cast<const double*>(w.gt), (char*)ws + own, o.y, o.h, o.y_real,
+                                    o.y_imag, st))
+      return e;
+  } else if (cir) {
     char* cws = (char*)ws + own + tx + (dmrs ? dmrs_workspace_bytes(d) : 0);
     if (hipError_t e = launch_cir_rx(d, *cir, reinterpret_cast<const double*>(wr.x), cws, o.y, o.h, o.y_real,
                                      o.y_imag, st))

@@ -30,6 +30,12 @@ perfect-CSI baselines the un-rotated channel, with which they collapse.
 ``-timing_offset`` (a late arrival per user) and ``-pa_ibo_db`` (a Rapp power amplifier) act on its samples, and
 the generator runs with ``h_with_delay`` for the same reason.
 
+``-tc_fft_size N`` replaces the per-RE channel product by the time-domain channel of ``GenParams.tc``: OFDM
+modulation, per-sample Doppler and sinc delay taps (``-tc_l_min``, ``-tc_l_max``) on the samples, demodulation
+with ``-tc_timing_advance``.  ``-max_doppler_hz`` and ``-max_delay_s`` set the spreads of the built-in channel
+(inside a symbol a high Doppler is inter-carrier, a delay beyond ``-tc_cp`` inter-symbol interference); the
+perfect-CSI systems and the NMSE see the ISI-free diagonal of the effective channel.
+
 ``-dmrs_cover`` gives the ``-num_tx_eval`` users orthogonal cover-coded DMRS ports (``ls.DMRSPorts``):
 ``h_hat`` is then the despreading LS estimate and users of one CDM group no longer collide on their
 pilots; ``-dmrs_symbols 2 3 10 11`` supplies the symbol pairs that more than four ports need.
@@ -46,8 +52,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .config import get_config
-from .generator import (SCENARIOS, GenParams, SlotGenerator, TimeDomain, count_errors, ebno_to_no, rx_correlation,
-                        scenario)
+from .generator import (SCENARIOS, GenParams, SlotGenerator, TimeChannelParams, TimeDomain, count_errors, ebno_to_no,
+                        rx_correlation, scenario)
 from .baseline import BaselineReceiver
 from .chest import COV_SLOT_OFFSET, EstimatorBaselineReceiver, estimate_covariance
 from .cfo import CFOCompensator
@@ -432,7 +438,28 @@ def main(argv=None):
     ap.add_argument("-timing_offset", type=int, nargs="+", default=None, metavar="D",
                     help="samples by which a user's signal arrives late, one value or one per user (needs "
                          "-td_fft_size); beyond the cyclic prefix it is inter-symbol interference")
+    ap.add_argument("-tc_fft_size", type=int, default=None, metavar="N",
+                    help="the time-domain channel in place of the per-RE product (GenParams.tc): OFDM modulation at "
+                         "FFT size N (a power of two, 64..4096, at least the grid), per-sample Doppler and sinc "
+                         "delay taps on the samples, demodulation; h is the ISI-free diagonal of the effective channel")
+    ap.add_argument("-tc_cp", type=int, default=None, metavar="L", help="cyclic prefix in samples (default 9 N / 128)")
+    ap.add_argument("-tc_l_min", type=int, default=-6, metavar="L", help="first tap of the truncated sinc, <= 0")
+    ap.add_argument("-tc_l_max", type=int, default=None, metavar="L",
+                    help="last tap (default: the longest delay in samples, rounded up, + 6)")
+    ap.add_argument("-tc_timing_advance", type=int, default=0, metavar="D",
+                    help="the receive windows start D samples early, 0..cyclic prefix")
+    ap.add_argument("-max_doppler_hz", type=float, default=None, metavar="HZ",
+                    help="maximum Doppler shift of the built-in channel (GenParams.max_doppler_hz; -channel iid)")
+    ap.add_argument("-max_delay_s", type=float, default=None, metavar="S",
+                    help="maximum path delay of the built-in channel (GenParams.max_delay_s; -channel iid)")
     a = ap.parse_args(argv)
+    if a.tc_fft_size is None and (a.tc_cp is not None or a.tc_l_max is not None or a.tc_timing_advance or a.tc_l_min != -6):
+        ap.error("-tc_cp, -tc_l_min, -tc_l_max and -tc_timing_advance belong to the time-domain channel: give -tc_fft_size")
+    if a.tc_fft_size is not None and (a.td_fft_size is not None or a.cfo_hz is not None or a.cfo_ppm is not None
+                                      or a.channel == "dataset"):
+        ap.error("-tc_fft_size with -td_fft_size, a CFO or -channel dataset: a run takes one sample-domain stage")
+    if a.channel != "iid" and (a.max_doppler_hz is not None or a.max_delay_s is not None):
+        ap.error("-max_doppler_hz and -max_delay_s set the spreads of -channel iid; the other channels bring their own")
     if a.td_fft_size is None and (a.pa_ibo_db is not None or a.timing_offset is not None or a.td_cp is not None):
         ap.error("-pa_ibo_db, -timing_offset and -td_cp act on the samples of the time-domain stage: give -td_fft_size")
     if a.td_fft_size is not None and (a.cfo_hz is not None or a.cfo_ppm is not None):
@@ -464,6 +491,10 @@ def main(argv=None):
     if a.dmrs_cover:
         params = dataclasses.replace(params, dmrs=DMRSPorts.for_config(cfg, u))
     params.num_active = a.num_tx_eval or u
+    if a.max_doppler_hz is not None:
+        params = dataclasses.replace(params, max_doppler_hz=a.max_doppler_hz)
+    if a.max_delay_s is not None:
+        params = dataclasses.replace(params, max_delay_s=a.max_delay_s)
     if a.channel == "dataset":
         from .cir import CIRChannel, CIRDataset
         params = dataclasses.replace(params, cir=CIRChannel(
@@ -482,6 +513,10 @@ def main(argv=None):
         params = dataclasses.replace(params, td=TimeDomain(
             fft_size=a.td_fft_size, cp=a.td_cp, delay=delay[0] if len(delay) == 1 else tuple(delay),
             pa_ibo_db=a.pa_ibo_db, pa_smoothness=a.pa_smoothness, h_with_delay=True))
+    if a.tc_fft_size is not None:
+        params = dataclasses.replace(params, tc=TimeChannelParams(
+            fft_size=a.tc_fft_size, cp=a.tc_cp, l_min=a.tc_l_min, l_max=a.tc_l_max,
+            timing_advance=a.tc_timing_advance))
     # a correlated channel: the LMMSE estimator takes the spatial covariance unless -chest_2d keeps it out
     # (a replayed dataset counts as one: its antennas are as correlated as its geometry makes them)
     chest3 = (params.rx_corr is not None or params.cir is not None) and not a.chest_2d
@@ -569,6 +604,10 @@ def main(argv=None):
         if params.td is not None:                  # a run without the stage keeps the keys it always had
             d["td"] = dict(fft_size=params.td.fft_size, cp=params.td.cp_list(), delay=params.td.delay_per_port(u),
                            pa_ibo_db=params.td.pa_ibo_db, pa_smoothness=params.td.pa_smoothness, h_with_delay=True)
+        if params.tc is not None:
+            d["tc"] = dict(fft_size=params.tc.fft_size, cp=params.tc.cp_list(), l_min=params.tc.l_min,
+                           l_max=params.tc.l_max, timing_advance=params.tc.timing_advance,
+                           max_doppler_hz=params.max_doppler_hz, max_delay_s=params.max_delay_s)
         if base:
             d["baselines"] = {name: r.as_dict() for name, r in base.items()}
         for name, points in soft.items():

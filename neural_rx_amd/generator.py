@@ -31,6 +31,12 @@ that format (``nrx_generate_taps``).
 ``x' = demodulate(impair(modulate(x)))`` through ``nrx_generate_slots_td``: a per-user timing error and a Rapp
 power amplifier, the two transmit-side effects without a closed form on the grid (the construction of the
 reference's utils/impairments.py:67-108; the transforms are those of ``neural_rx_amd/ofdm.py``).
+
+``GenParams.tc`` (a ``TimeChannelParams``) replaces the per-RE channel product by the time-domain channel of
+``neural_rx_amd/timechannel.py`` between modulation and demodulation, through ``nrx_generate_slots_tc``: path
+gains that move inside a symbol (inter-carrier interference) and delay taps that may exceed the cyclic prefix
+(inter-symbol interference), with the built-in channel's own draws, so a run with zero Doppler is the plain
+generator's realisation up to the truncation of the sinc taps.
 """
 from __future__ import annotations
 
@@ -102,6 +108,36 @@ class TimeDomain:
 
 
 @dataclasses.dataclass
+class TimeChannelParams:
+    """The time-domain channel of the generator (include/nrx.h nrx_gen_tc).  Taps ``l_min..l_max`` of the plainly
+    truncated sinc (``l_max = None``: the longest port delay in samples, rounded up, + 6); ``timing_advance``:
+    the receive windows start this many samples early (0..min cp).  ``SlotBatch.h`` is then the ISI-free
+    diagonal of the effective channel: exact when ``l_max <= cp - timing_advance`` and ``timing_advance >=
+    -l_min``, the dominant term otherwise."""
+    fft_size: int
+    cp: Optional[object] = None        # one int or 14; None = ofdm.default_cp(fft_size)
+    l_min: int = -6
+    l_max: Optional[int] = None
+    timing_advance: int = 0
+    first_bin: int = -1
+
+    def cp_list(self) -> list:
+        return TimeDomain.cp_list(self)
+
+    def num_samples(self) -> int:
+        return sum(c + int(self.fft_size) for c in self.cp_list())
+
+    def struct(self) -> _lib.nrx_gen_tc:
+        t = _lib.nrx_gen_tc()
+        t.fft_size, t.first_bin = int(self.fft_size), int(self.first_bin)
+        for k, c in enumerate(self.cp_list()):
+            t.cp_length[k] = c
+        t.l_min, t.l_max = int(self.l_min), -1 if self.l_max is None else int(self.l_max)
+        t.timing_advance = int(self.timing_advance)
+        return t
+
+
+@dataclasses.dataclass
 class GenParams:
     """Everything that defines a batch of generated slots (besides ``no``/offset)."""
     num_tx: int
@@ -137,8 +173,14 @@ class GenParams:
     # a time-domain transmit stage (TimeDomain): per-user timing error and power amplifier; None = the generator
     # without it.  Excludes cfo_hz: one transmit-side stage per generator.
     td: Optional[TimeDomain] = None
+    # the time-domain channel (TimeChannelParams) in place of the per-RE product; None = the grid channel.
+    # Excludes td, cir and cfo_hz: one sample-domain stage per generator.  dmrs composes: it acts on x.
+    tc: Optional[TimeChannelParams] = None
 
     def __post_init__(self):
+        if self.tc is not None and (self.td is not None or self.cir is not None or self.cfo_hz is not None):
+            raise ValueError("tc with td, cir or cfo_hz: a generator takes one sample-domain stage "
+                             "(as it takes one transmit-side stage)")
         if self.td is not None and self.cfo_hz is not None:
             raise ValueError("td and cfo_hz are two transmit-side stages: a generator takes one of them")
         if self.cir is not None:
@@ -295,6 +337,7 @@ class SlotBatch:
     cfo_eps: "object" = None   # [B, U] f64: the carrier frequency offset in subcarrier spacings, or None
     pilots: "object" = None    # [2, Pmax, nd, 2] f32: the DMRS base sequence (GenParams.dmrs), or None
     x_td: "object" = None      # [B, U, F, T] c128: the grid behind the time-domain stage (GenParams.td), or None
+    r_tc: "object" = None      # [B, A, Ls] c128: the noise-free received samples (GenParams.tc), or None
 
 
 class SlotGenerator:
@@ -302,12 +345,13 @@ class SlotGenerator:
     is the same slot whichever call, rank or batch split generates it."""
 
     def __init__(self, params: GenParams, device: int = 0, want_h: bool = False, aerial: bool = False,
-                 want_x: bool = False):
+                 want_x: bool = False, want_r: bool = False):
         self.p = params
         self.device = device
         self.want_h = want_h
         self.aerial = aerial
         self.want_x = want_x            # SlotBatch.x_td (with GenParams.td)
+        self.want_r = want_r            # SlotBatch.r_tc (with GenParams.tc)
         self._lib = _lib.load()
         self._ws = Workspace()
         self._bufs = {}
@@ -352,15 +396,16 @@ class SlotGenerator:
             r.a, r.tau = self._cir_a.data_ptr(), self._cir_tau.data_ptr()
             self._cir = r
         self._td = params.td.struct(params.num_tx) if params.td is not None else None
+        self._tc = params.tc.struct() if params.tc is not None else None
 
     def workspace_bytes(self, batch: int) -> int:
-        """what ``nrx_gen_workspace_size_td`` asks for with whichever blocks this generator has (NULL for
+        """what ``nrx_gen_workspace_size_tc`` asks for with whichever blocks this generator has (NULL for
         the absent ones: the older ``nrx_gen_workspace_size*`` are that call with fewer blocks)"""
         if self._cir is not None and self._cir.select == SELECT["index"] and not self._cir.index:
             # the size is no function of the index, which comes with every call: any address passes the check
             self._cir.index = self._cir_tau.data_ptr()
-        return self._ws.size(self._lib.nrx_gen_workspace_size_td, ref(self.p.desc(batch, 0.0)), ref(self._cfo),
-                             ref(self._dmrs), ref(self._cir), ref(self._td))
+        return self._ws.size(self._lib.nrx_gen_workspace_size_tc, ref(self.p.desc(batch, 0.0)), ref(self._chan),
+                             ref(self._cfo), ref(self._dmrs), ref(self._cir), ref(self._td), ref(self._tc))
 
     def _alloc(self, batch: int) -> SlotBatch:
         torch = _torch()
@@ -390,6 +435,8 @@ class SlotGenerator:
             sb.pilots = torch.empty((2, (F + 1) // 2, len(p.dmrs_symbols), 2), **f32)
         if self._td is not None and self.want_x:
             sb.x_td = torch.empty((batch, U, F, NUM_SYMBOLS), dtype=torch.complex128, device=dev)
+        if self._tc is not None and self.want_r:
+            sb.r_tc = torch.empty((batch, A, p.tc.num_samples()), dtype=torch.complex128, device=dev)
         self._bufs = {key: sb}
         return sb
 
@@ -419,11 +466,13 @@ class SlotGenerator:
             self._cir.index = cir_index.data_ptr()
         if self._td is not None:
             self._td.x_out = ptr(sb.x_td)
+        if self._tc is not None:
+            self._tc.r_out = ptr(sb.r_tc)
         # one entry point: the older nrx_generate_slots* are this call with NULL for the blocks they lack.
         # A dataset is the channel, so chan stays NULL with it (GenParams refuses the two together).
-        _lib.check(self._lib.nrx_generate_slots_td(
-            ref(d), ref(self._chan), ref(self._cfo), ref(self._dmrs), ref(self._cir), ref(self._td), ref(o),
-            ws.data_ptr(), ws.numel(), stream_of(sb.y, stream)))
+        _lib.check(self._lib.nrx_generate_slots_tc(
+            ref(d), ref(self._chan), ref(self._cfo), ref(self._dmrs), ref(self._cir), ref(self._td), ref(self._tc),
+            ref(o), ws.data_ptr(), ws.numel(), stream_of(sb.y, stream)))
         return sb
 
     def export_taps(self, batch: int, slot_offset: int = 0, stream=None) -> CIRDataset:
