@@ -1206,6 +1206,76 @@ typedef struct nrx_ldpc_count_io {
 
 int nrx_ldpc_count(const nrx_ldpc_count_io* io, void* stream);
 
+/* ---------------------------------------------------------------- training: loss, gradient, Adam
+ * nrx_train_grad runs the CGNN of `desc` forward in f32 on the weights it is given, evaluates
+ *   loss_data  = sum_r sum_m [ sum active[b,u] mcs_mask[b,u,m] l(z, bit) ] / (B U F (14 - n_dmrs) bits_m)
+ *                l(z, bit) = max(z, 0) - bit z + log1p(exp(-|z|)) over the data symbols (those outside
+ *                dmrs_symbol_mask) and the bits k < bits_m; LLR > 0 means bit 1, as in nrx_count_errors
+ *   loss_chest = sum_r mean over [B,U,F,T,2A] of active[b,u] (h_ref - h)^2   (h_ref as the readout gives it and h
+ *                as the generator gives it: the convention of nrx_chest_nmse, no rescaling by the slot norm)
+ * over the readouts r (multiloss = 0: after iteration num_it; 1: after every iteration 1..num_it) and writes the
+ * gradient of loss_data + w_chest loss_chest with respect to every weight.  With var_mcs_masking the one head is
+ * sliced to bits_m for each m.  The per-slot input normalisation depends on no weight and has no backward.
+ *
+ * weights / grad: one flat f32 buffer each, the arrays of nrx_weight_layout(desc) concatenated in that order.
+ * grad is overwritten; the arrays of iterations beyond num_it come back exactly zero.  loss = {loss_data,
+ * loss_chest} (loss_chest = 0 when h is NULL).  llr / h_ref (optional): the last readout, in nrx_io's layouts.
+ * All sums across workgroups are slab sums in a fixed order: the outputs are bit-reproducible from call to call.
+ * Stateless, nothing allocated, no host synchronisation, everything on the caller's stream.
+ *
+ * Workspace: f32 activations kept position-major [P][C], P = B U F 14 positions (see csrc/nrx_train.hip for
+ * the list); nrx_train_workspace_size gives the bytes.
+ *
+ * A NULL desc / io / y / pe / active / bits / weights / grad / loss / workspace / bytes, a NULL h_hat with
+ * desc.use_h_hat, a NULL h with w_chest > 0, a float pointer that is not 4-byte aligned, a loss that is not
+ * 8-byte aligned, a workspace that is not 256-byte aligned, num_it outside 1..desc.num_it, multiloss outside
+ * 0/1, a dmrs_symbol_mask that is no mask of the 14 symbols or holds all of them, or a w_chest that is negative
+ * or not finite is NRX_ERR_INVALID_ARG; T != 14, B / U / F outside nrx_forward's ranges, more than 2^24
+ * positions or bits_stride < max(bits) is NRX_ERR_SHAPE; a topology nrx_create refuses is
+ * NRX_ERR_UNSUPPORTED; a workspace smaller than nrx_train_workspace_size is NRX_ERR_WORKSPACE. */
+typedef struct nrx_train_io {
+  nrx_shape shape;
+  int32_t num_it;              /* iterations to run, 1..desc.num_it */
+  int32_t dmrs_symbol_mask;    /* bit t set: symbol t carries DMRS and no loss */
+  int32_t multiloss;           /* 0: read out after the last iteration; 1: after every iteration */
+  int32_t bits_stride;         /* bit axis of `bits`, >= max(desc.bits) */
+  double w_chest;              /* weight of loss_chest in the gradient; 0 switches it off */
+  const float* y;              /* as nrx_io */
+  const float* pe;
+  const float* h_hat;          /* may be NULL only if desc.use_h_hat == 0 */
+  const float* active;
+  const float* mcs_mask;       /* may be NULL: one-hot on MCS 0 */
+  const uint8_t* bits;         /* [B][U][F][T][bits_stride], nrx_gen_out.bits */
+  const float* h;              /* [B][U][F][T][2A] true channel, nrx_gen_out.h; may be NULL only if w_chest == 0 */
+  const float* weights;        /* flat, Keras get_weights() order */
+  float* grad;                 /* flat, like weights; overwritten */
+  double* loss;                /* [2]: loss_data, loss_chest */
+  float* llr;                  /* [H][B][U][F][T][bits_max] of the last readout, or NULL */
+  float* h_ref;                /* [B][U][F][T][2A] of the last readout, or NULL */
+} nrx_train_io;
+
+int nrx_train_workspace_size(const nrx_desc* desc, const nrx_train_io* io, size_t* bytes);
+int nrx_train_grad(const nrx_desc* desc, const nrx_train_io* io, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* One Adam step (Keras: tf.keras.optimizers.Adam, defaults 1e-3 / 0.9 / 0.999 / 1e-7) on n f32 elements, with
+ * t = step:   m = b1 m + (1 - b1) g;   v = b2 v + (1 - b2) g^2;
+ *             w -= lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps)
+ * The bias corrections are formed on the host in double; the update is one elementwise launch that works in
+ * double on the stored (f32) m and v.  A NULL io / w / g / m / v or a pointer that is not 4-byte aligned, n < 0,
+ * step < 1, lr / eps negative or not finite, or beta1 / beta2 outside [0, 1) is NRX_ERR_INVALID_ARG. */
+typedef struct nrx_adam_io {
+  int64_t n;
+  float* w;
+  const float* g;
+  float* m;
+  float* v;
+  double lr, beta1, beta2, eps;
+  int64_t step;                /* t >= 1 */
+} nrx_adam_io;
+
+int nrx_adam_step(const nrx_adam_io* io, void* stream);
+
 /* Host helper: nearest-pilot positional encoding pe[U][F][T][2] for DMRS
  * configuration type 1 (restates onnx_utils.py:172-260 for the product path).
  * dmrs_symbols: the DMRS OFDM symbol indices; cdm_group[u] in {0,1}. */

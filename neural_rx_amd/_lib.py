@@ -216,6 +216,16 @@ class nrx_ldpc_count_io(ctypes.Structure):
                 + _ptr("hard", "skip", "iters", "counts", "iter_counts"))
 
 
+class nrx_train_io(ctypes.Structure):
+    _fields_ = ([("shape", nrx_shape)] + _i32("num_it", "dmrs_symbol_mask", "multiloss", "bits_stride") + _f64("w_chest")
+                + _ptr("y", "pe", "h_hat", "active", "mcs_mask", "bits", "h", "weights", "grad", "loss", "llr", "h_ref"))
+
+
+class nrx_adam_io(ctypes.Structure):
+    _fields_ = ([("n", ctypes.c_int64)] + _ptr("w", "g", "m", "v") + _f64("lr", "beta1", "beta2", "eps")
+                + [("step", ctypes.c_int64)])
+
+
 def _signatures():
     c = ctypes
     P = c.POINTER
@@ -288,6 +298,9 @@ def _signatures():
         "nrx_ldpc_decode": (RC, [V, P(nrx_ldpc_io)] + run),
         "nrx_ldpc_gather": (RC, [P(nrx_ldpc_gather_io), V]),
         "nrx_ldpc_count": (RC, [P(nrx_ldpc_count_io), V]),
+        "nrx_train_workspace_size": (RC, [desc, P(nrx_train_io), PZ]),
+        "nrx_train_grad": (RC, [desc, P(nrx_train_io)] + run),
+        "nrx_adam_step": (RC, [P(nrx_adam_io), V]),
     }
 
 

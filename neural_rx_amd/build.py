@@ -24,7 +24,7 @@ SOURCES = [os.path.join(CSRC, f) for f in KERNEL_TUS] + [
     os.path.join(CSRC, "nrx_kbest.hip"), os.path.join(CSRC, "nrx_chest.hip"),
     os.path.join(CSRC, "nrx_softmetrics.hip"), os.path.join(CSRC, "nrx_ldpc.hip"),
     os.path.join(CSRC, "nrx_cfo.hip"), os.path.join(CSRC, "nrx_ls.hip"), os.path.join(CSRC, "nrx_cir.hip"),
-    os.path.join(CSRC, "nrx_ofdm.hip"), os.path.join(CSRC, "nrx_timechan.hip"),
+    os.path.join(CSRC, "nrx_ofdm.hip"), os.path.join(CSRC, "nrx_timechan.hip"), os.path.join(CSRC, "nrx_train.hip"),
     os.path.join(CSRC, "nrx_model.cpp"), os.path.join(CSRC, "nrx_api.cpp")]
 HEADERS = [os.path.join(CSRC, "nrx_internal.h"), os.path.join(CSRC, "nrx_model.h"), os.path.join(CSRC, "nrx_rng.h"),
            os.path.join(HERE, "..", "include", "nrx.h")]

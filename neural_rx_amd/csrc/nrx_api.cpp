@@ -1355,6 +1355,64 @@ int nrx_ldpc_count(const nrx_ldpc_count_io* io, void* stream) {
   return launched(launch_ldpc_count(*io, (hipStream_t)stream), "ldpc count launch");
 }
 
+// ---- training: the topology check is nrx_create's, the grid check nrx_forward's
+static int check_aligned(const char* name, const void* p, size_t align) {
+  if (!((uintptr_t)p & (align - 1))) return NRX_OK;
+  return fail(NRX_ERR_INVALID_ARG, std::string(name) + " must be " + std::to_string(align) + "-byte aligned");
+}
+
+static int check_train(const nrx_desc* d, const nrx_train_io* io) {
+  if (int rc = check_desc(d)) return rc;
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (int rc = check_shape(&io->shape)) return rc;
+  if ((int64_t)io->shape.batch * io->shape.num_tx * io->shape.num_subcarriers * kT > (1 << 24))
+    return fail(NRX_ERR_SHAPE, "training takes at most 2^24 positions (batch x num_tx x num_subcarriers x 14)");
+  if (io->num_it < 1 || io->num_it > d->num_it) return fail(NRX_ERR_INVALID_ARG, "Invalid number of iterations");
+  if (int rc = check_symbol_mask("dmrs_symbol_mask", io->dmrs_symbol_mask)) return rc;
+  if (io->dmrs_symbol_mask == (1 << kT) - 1)
+    return fail(NRX_ERR_INVALID_ARG, "dmrs_symbol_mask must leave a data symbol");
+  if (int rc = check_range("multiloss", io->multiloss, 0, 1, NRX_ERR_INVALID_ARG)) return rc;
+  if (int rc = check_nonneg("w_chest", io->w_chest)) return rc;
+  if (int rc = check_bits_stride(io->bits_stride, d->bits, d->num_mcs)) return rc;
+  if (!io->y || !io->pe || !io->active || !io->bits || !io->weights || !io->grad || !io->loss)
+    return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  if (d->use_h_hat && !io->h_hat) return fail(NRX_ERR_INVALID_ARG, "h_hat is required by this model");
+  if (io->w_chest > 0.0 && !io->h) return fail(NRX_ERR_INVALID_ARG, "h is required when w_chest > 0");
+  const void* f32s[] = {io->y, io->pe, io->h_hat, io->active, io->mcs_mask, io->h, io->weights, io->grad, io->llr,
+                        io->h_ref};
+  for (const void* p : f32s)
+    if (int rc = check_aligned("float tensors", p, 4)) return rc;
+  return check_aligned("loss", io->loss, 8);
+}
+
+int nrx_train_workspace_size(const nrx_desc* desc, const nrx_train_io* io, size_t* bytes) {
+  if (int rc = check_train(desc, io)) return rc;
+  return store_size(bytes, train_workspace_bytes(*desc, *io));
+}
+
+int nrx_train_grad(const nrx_desc* desc, const nrx_train_io* io, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+  if (int rc = check_train(desc, io)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, train_workspace_bytes(*desc, *io), 256)) return rc;
+  return launched(launch_train_grad(*desc, *io, workspace, (hipStream_t)stream), "training launch");
+}
+
+int nrx_adam_step(const nrx_adam_io* io, void* stream) {
+  if (!io) return fail(NRX_ERR_INVALID_ARG, "io is NULL");
+  if (!io->w || !io->g || !io->m || !io->v) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
+  const void* f32s[] = {io->w, io->g, io->m, io->v};
+  for (const void* p : f32s)
+    if (int rc = check_aligned("float tensors", p, 4)) return rc;
+  if (io->n < 0) return fail(NRX_ERR_INVALID_ARG, "n must be >= 0");
+  if (io->step < 1) return fail(NRX_ERR_INVALID_ARG, "step must be >= 1");
+  if (int rc = check_nonneg("lr", io->lr)) return rc;
+  if (int rc = check_nonneg("eps", io->eps)) return rc;
+  if (!(io->beta1 >= 0.0 && io->beta1 < 1.0) || !(io->beta2 >= 0.0 && io->beta2 < 1.0))
+    return fail(NRX_ERR_INVALID_ARG, "beta1 and beta2 must be in [0, 1)");
+  const double c1 = 1.0 - std::pow(io->beta1, (double)io->step), c2 = 1.0 - std::pow(io->beta2, (double)io->step);
+  return launched(launch_adam(*io, c1, c2, (hipStream_t)stream), "adam launch");
+}
+
 int nrx_profile_enable(nrx_handle* h, int32_t enable) {
   if (!h) return fail(NRX_ERR_INVALID_ARG, "null handle");
   if (enable) {

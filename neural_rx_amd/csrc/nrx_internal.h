@@ -281,6 +281,12 @@ hipError_t launch_ldpc_decode(const LdpcDev& d, const nrx_ldpc_io& io, void* ws,
 hipError_t launch_ldpc_gather(const nrx_ldpc_gather_io& io, hipStream_t st);
 hipError_t launch_ldpc_count(const nrx_ldpc_count_io& io, hipStream_t st);
 
+// Training (nrx_train.hip); desc and io validated by the nrx_train_* / nrx_adam_step entry points.  c1, c2: the
+// bias corrections 1 - beta^step
+size_t train_workspace_bytes(const nrx_desc& d, const nrx_train_io& io);
+hipError_t launch_train_grad(const nrx_desc& d, const nrx_train_io& io, void* ws, hipStream_t st);
+hipError_t launch_adam(const nrx_adam_io& io, double c1, double c2, hipStream_t st);
+
 hipError_t launch_llr_demap(const float* llr, int B, int U, int F, int T, int bits_stride, int bits,
                             const int32_t* data_re, int n_data, float* out, hipStream_t st);
 

@@ -351,46 +351,49 @@ def baseline_note(name: str, receiver) -> Optional[str]:
             "so h_hat is pilot-contaminated and this curve is not a meaningful baseline")
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+def add_arguments(ap, generator_only=False):
+    """The options of the command line.  ``generator_only``: just those that choose the configuration and the
+    generated slots -- what ``train.py`` shares with the evaluation (``generator_params`` reads them)."""
+    ev = (lambda *args, **kw: None) if generator_only else ap.add_argument   # the evaluation's own options
     ap.add_argument("-config_name", default="nrx_rt")
     ap.add_argument("-num_tx_eval", type=int, default=None, help="active DMRS ports per slot")
     ap.add_argument("-num_prbs", type=int, default=None)
-    ap.add_argument("-ebno_db", type=float, nargs="+", default=None)
+    ev("-ebno_db", type=float, nargs="+", default=None)
     ap.add_argument("-batch_size", type=int, default=128)
-    ap.add_argument("-max_mc_iter", type=int, default=100)
-    ap.add_argument("-num_target_block_errors", type=int, default=500)
-    ap.add_argument("-target_bler", type=float, default=None)
+    ev("-max_mc_iter", type=int, default=100)
+    ev("-num_target_block_errors", type=int, default=500)
+    ev("-target_bler", type=float, default=None)
     ap.add_argument("-var_mcs", action="store_true", help="draw the MCS of every (slot, user)")
-    ap.add_argument("-precision", default="f16")
+    ev("-precision", default="f16")
     ap.add_argument("-seed", type=int, default=1234)
-    ap.add_argument("-sync_every", type=int, default=8, help="MC batches per counter all-reduce")
+    ev("-sync_every", type=int, default=8, help="MC batches per counter all-reduce")
     ap.add_argument("-gpu", type=int, default=None)
-    ap.add_argument("-out", default=None, help="write the result JSON here")
-    ap.add_argument("-baselines", nargs="*", default=[],
-                    choices=["lsnn_lmmse", "lslin_lmmse", "lmmse_lmmse", "perf_csi_lmmse", "lmmse_kbest",
-                             "perf_csi_kbest"],
-                    help="classical baselines run on the same slots (baseline.BaselineReceiver, "
-                         "chest.EstimatorBaselineReceiver, kbest.KBestBaselineReceiver); the JSON gains "
-                         "\"baselines\": {name: result}")
-    ap.add_argument("-kbest_k", type=int, default=64, help="survivors per level of the K-best baselines (1..64)")
-    ap.add_argument("-num_cov_slots", type=int, default=2048,
-                    help="slots the covariance of lmmse_lmmse / lmmse_kbest is estimated from (drawn at slot offset 2^40, "
-                         "disjoint from every Monte-Carlo slot)")
-    ap.add_argument("-soft_metrics", action="store_true",
-                    help="also accumulate the soft-output metrics (softmetrics.py): BMI / GMI of every system's "
-                         "LLRs and the NMSE of its channel estimate; the JSON gains \"soft\" (per point) next to "
-                         "every result")
-    ap.add_argument("-llr_scales", type=float, nargs="+", default=None,
-                    help="LLR scale factors the GMI is searched over (1..16 positive numbers)")
-    ap.add_argument("-code_rate", type=float, default=None,
-                    help="with -soft_metrics: report the Eb/N0 at which BMI and GMI reach this rate")
-    ap.add_argument("-ldpc", default=None, choices=["r13", "r12", "r23", "r34"],
-                    help="also decode every batch with the GPU QC-LDPC decoder (ldpc.py; the project's own regular "
-                         "code of that rate, sized to the slot) and report coded BER / BLER for every system; the "
-                         "JSON gains \"coded\" next to every result")
-    ap.add_argument("-ldpc_iter", type=int, default=20, help="decoder iterations (1..100), with early stop")
-    ap.add_argument("-ldpc_cn", default="boxplus", choices=["boxplus", "minsum"], help="check-node update")
+    ev("-out", default=None, help="write the result JSON here")
+    ev("-weights", default=None, metavar="FILE.npz",
+       help="score this weight file (weights.save, train.py -out) in place of the config's shipped weights")
+    ev("-baselines", nargs="*", default=[],
+       choices=["lsnn_lmmse", "lslin_lmmse", "lmmse_lmmse", "perf_csi_lmmse", "lmmse_kbest", "perf_csi_kbest"],
+       help="classical baselines run on the same slots (baseline.BaselineReceiver, "
+            "chest.EstimatorBaselineReceiver, kbest.KBestBaselineReceiver); the JSON gains "
+            "\"baselines\": {name: result}")
+    ev("-kbest_k", type=int, default=64, help="survivors per level of the K-best baselines (1..64)")
+    ev("-num_cov_slots", type=int, default=2048,
+       help="slots the covariance of lmmse_lmmse / lmmse_kbest is estimated from (drawn at slot offset 2^40, "
+            "disjoint from every Monte-Carlo slot)")
+    ev("-soft_metrics", action="store_true",
+       help="also accumulate the soft-output metrics (softmetrics.py): BMI / GMI of every system's "
+            "LLRs and the NMSE of its channel estimate; the JSON gains \"soft\" (per point) next to "
+            "every result")
+    ev("-llr_scales", type=float, nargs="+", default=None,
+       help="LLR scale factors the GMI is searched over (1..16 positive numbers)")
+    ev("-code_rate", type=float, default=None,
+       help="with -soft_metrics: report the Eb/N0 at which BMI and GMI reach this rate")
+    ev("-ldpc", default=None, choices=["r13", "r12", "r23", "r34"],
+       help="also decode every batch with the GPU QC-LDPC decoder (ldpc.py; the project's own regular "
+            "code of that rate, sized to the slot) and report coded BER / BLER for every system; the "
+            "JSON gains \"coded\" next to every result")
+    ev("-ldpc_iter", type=int, default=20, help="decoder iterations (1..100), with early stop")
+    ev("-ldpc_cn", default="boxplus", choices=["boxplus", "minsum"], help="check-node update")
     ap.add_argument("-cir_file", default=None, metavar="PATH",
                     help="-channel dataset: the .npz of channel impulse responses to replay (cir.CIRDataset: 'a' "
                          "complex64 [E, A, L, 1 | 14], 'tau' float32 [E, L] in seconds)")
@@ -406,9 +409,9 @@ def main(argv=None):
                          "two-port config)")
     ap.add_argument("-rx_corr", type=float, default=None, metavar="ALPHA",
                     help="receive-antenna correlation rx_correlation(A, ALPHA), replacing the channel's own")
-    ap.add_argument("-chest_2d", action="store_true",
-                    help="on a correlated channel lmmse_lmmse uses the spatial covariance (nrx_chest_lmmse3); this "
-                         "keeps the 2-D filter that ignores it, so that both can be tabulated")
+    ev("-chest_2d", action="store_true",
+       help="on a correlated channel lmmse_lmmse uses the spatial covariance (nrx_chest_lmmse3); this "
+            "keeps the 2-D filter that ignores it, so that both can be tabulated")
     ap.add_argument("-cfo_hz", type=float, default=None, metavar="HZ",
                     help="per-user carrier frequency offset at the transmitter, drawn uniformly in +-HZ per "
                          "(slot, user) (GenParams.cfo_hz); the generator then runs with h_with_phase")
@@ -416,10 +419,10 @@ def main(argv=None):
                     help="the same as a fraction of the carrier: HZ = carrier_frequency_hz / 1e6 * PPM")
     ap.add_argument("-carrier_frequency_hz", type=float, default=2.14e9)
     ap.add_argument("-cfo_constant", action="store_true", help="every user has exactly the offset, not a draw")
-    ap.add_argument("-cfo_comp", action="store_true",
-                    help="DMRS-based CFO estimation and compensation (cfo.py) in front of every system: the NRX and "
-                         "lsnn_lmmse read the compensated h_hat, the estimators run between a de-rotation and a "
-                         "re-rotation")
+    ev("-cfo_comp", action="store_true",
+       help="DMRS-based CFO estimation and compensation (cfo.py) in front of every system: the NRX and "
+            "lsnn_lmmse read the compensated h_hat, the estimators run between a de-rotation and a "
+            "re-rotation")
     ap.add_argument("-dmrs_cover", action="store_true",
                     help="cover-coded DMRS ports (ls.DMRSPorts.for_config) for -num_tx_eval users, all active: CDM "
                          "group x frequency cover x time cover, despread by the LS estimator (nrx_ls_estimate); more "
@@ -452,7 +455,10 @@ def main(argv=None):
                     help="maximum Doppler shift of the built-in channel (GenParams.max_doppler_hz; -channel iid)")
     ap.add_argument("-max_delay_s", type=float, default=None, metavar="S",
                     help="maximum path delay of the built-in channel (GenParams.max_delay_s; -channel iid)")
-    a = ap.parse_args(argv)
+
+
+def check_arguments(ap, a):
+    """the refusals among the generator's options, which come before the first import of torch"""
     if a.tc_fft_size is None and (a.tc_cp is not None or a.tc_l_max is not None or a.tc_timing_advance or a.tc_l_min != -6):
         ap.error("-tc_cp, -tc_l_min, -tc_l_max and -tc_timing_advance belong to the time-domain channel: give -tc_fft_size")
     if a.tc_fft_size is not None and (a.td_fft_size is not None or a.cfo_hz is not None or a.cfo_ppm is not None
@@ -471,19 +477,9 @@ def main(argv=None):
     if a.channel == "dataset" and a.rx_corr is not None:
         ap.error("-rx_corr does not apply to -channel dataset: the dataset brings its own antenna structure")
 
-    import torch
-    import torch.distributed as dist
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    device = a.gpu if a.gpu is not None else local
-    torch.cuda.set_device(device)
-    if world > 1:
-        dist.init_process_group("nccl", device_id=torch.device(f"cuda:{device}"))
-    cfg = get_config(a.config_name)
-    spec = spec_for(cfg)
-    from . import weights as W
-    engine = CGNNEngine(spec, W.load(cfg.label), device=device)
+
+def generator_params(a, cfg):
+    """``(GenParams, ports, cfo_hz)`` of the parsed options ``a`` (``add_arguments``) for config ``cfg``"""
     u = (a.num_tx_eval or cfg.max_num_tx) if a.dmrs_cover else cfg.max_num_tx
     params = GenParams.from_config(cfg, num_tx=u, num_prbs=a.num_prbs, var_mcs=a.var_mcs, seed=a.seed)
     if a.dmrs_symbols is not None:
@@ -517,6 +513,29 @@ def main(argv=None):
         params = dataclasses.replace(params, tc=TimeChannelParams(
             fft_size=a.tc_fft_size, cp=a.tc_cp, l_min=a.tc_l_min, l_max=a.tc_l_max,
             timing_advance=a.tc_timing_advance))
+    return params, u, cfo_hz
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    add_arguments(ap)
+    a = ap.parse_args(argv)
+    check_arguments(ap, a)
+
+    import torch
+    import torch.distributed as dist
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    device = a.gpu if a.gpu is not None else local
+    torch.cuda.set_device(device)
+    if world > 1:
+        dist.init_process_group("nccl", device_id=torch.device(f"cuda:{device}"))
+    cfg = get_config(a.config_name)
+    spec = spec_for(cfg)
+    from . import weights as W
+    engine = CGNNEngine(spec, W.load_file(a.weights) if a.weights else W.load(cfg.label), device=device)
+    params, u, cfo_hz = generator_params(a, cfg)
     # a correlated channel: the LMMSE estimator takes the spatial covariance unless -chest_2d keeps it out
     # (a replayed dataset counts as one: its antennas are as correlated as its geometry makes them)
     chest3 = (params.rx_corr is not None or params.cir is not None) and not a.chest_2d

@@ -28,6 +28,19 @@ def load(label: str) -> List[np.ndarray]:
                 for i in range(int(d["count"]))]
 
 
+def load_file(path: str) -> List[np.ndarray]:
+    """A weight list from any ``.npz`` of the shipped format (``save`` writes it)."""
+    with np.load(path, allow_pickle=False) as d:
+        return [np.ascontiguousarray(d[f"w{i:03d}"], dtype=np.float32) for i in range(int(d["count"]))]
+
+
+def save(path: str, weight_list) -> None:
+    """The inverse of ``load``: the arrays as ``w000``, ``w001``, ... and their ``count``."""
+    arrays = {f"w{i:03d}": np.ascontiguousarray(w, dtype=np.float32) for i, w in enumerate(weight_list)}
+    with open(path, "wb") as f:     # a file object: numpy appends no ".npz" to the name
+        np.savez(f, count=np.int64(len(weight_list)), **arrays)
+
+
 def seeded(spec, seed: int = 0) -> List[np.ndarray]:
     """Random Keras-ordered weights of a topology (Glorot uniform kernels).  Used
     for BASELINE config 3 (16 rx antennas), for which no trained weights exist."""

@@ -1,0 +1,87 @@
+"""Time of one nrx_train_grad call (forward, loss and backward) and of one nrx_adam_step.
+
+    python tools/bench_train.py [--config nrx_rt] [--prbs 4] [--batch 128] [--users 2] [--runs 20] [--multiloss]
+
+The bench configuration (nrx_rt, 4 PRB, B = 128, U = 2) on generated slots.  Every call is timed on its own with a
+pair of HIP events after a warm-up; the JSON line gives the median, the extremes and the spread over ``--runs``
+calls, the workspace, and the arithmetic: multiply-adds x 2 of the forward, of the backward-data products (every
+layer but the first of each StateInit stack, whose input needs no gradient) and of the backward-weight products,
+depthwise taps included, biases and elementwise work not -- and the rate that count gives at the median time.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def flops_per_position(spec, num_it, multiloss):
+    """(forward, backward) multiply-adds x 2 per position"""
+    sep = lambda ci, co: 9 * ci + ci * co            # noqa: E731
+    stack = lambda ci: [sep(ci, 128), sep(128, 128), sep(128, spec.d_s)]        # noqa: E731
+    init = stack(spec.init_in_ch)
+    it = [spec.d_s * 64, 64 * spec.d_s] + stack(spec.update_in_ch)
+    ro = sum(spec.d_s * 128 + 128 * b for b in spec.head_bits) + spec.d_s * 128 + 128 * 2 * spec.num_rx_ant
+    nro = num_it if multiloss else 1
+    fwd = spec.num_init * sum(init) + num_it * sum(it) + nro * ro
+    bwd = 2 * fwd - spec.num_init * init[0]          # weight + data products, minus StateInit conv1's data product
+    return 2.0 * fwd, 2.0 * bwd
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="nrx_rt")
+    ap.add_argument("--prbs", type=int, default=4)
+    ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--users", type=int, default=2)
+    ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--multiloss", action="store_true")
+    ap.add_argument("--w_chest", type=float, default=0.02)
+    a = ap.parse_args(argv)
+    import torch
+    from neural_rx_amd import weights as W
+    from neural_rx_amd.config import get_config
+    from neural_rx_amd.generator import GenParams, SlotGenerator, ebno_to_no
+    from neural_rx_amd.receiver import compute_pe, spec_for
+    from neural_rx_amd.train import Trainer
+    cfg = get_config(a.config)
+    spec = spec_for(cfg)
+    p = GenParams.from_config(cfg, num_tx=a.users, num_prbs=a.prbs)
+    sb = SlotGenerator(p, want_h=True)(a.batch, ebno_to_no(6.0, len(p.dmrs_symbols)))
+    pe = torch.from_numpy(compute_pe(p.num_tx, p.num_subcarriers, p.dmrs_symbols, p.cdm_group)).cuda()
+    tr = Trainer(spec, W.load(cfg.label))
+    kw = dict(multiloss=a.multiloss, w_chest=a.w_chest, dmrs_symbols=p.dmrs_symbols)
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        ms = []
+        for _ in range(a.runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return np.array(ms)
+
+    g_ms = timed(lambda: tr.grad_async(sb, pe, **kw))
+    a_ms = timed(tr.step)
+    P = a.batch * a.users * p.num_subcarriers * 14
+    fwd, bwd = flops_per_position(spec, spec.num_it, a.multiloss)
+    med = float(np.median(g_ms))
+    stat = lambda x: dict(median=round(float(np.median(x)), 4), min=round(float(x.min()), 4),     # noqa: E731
+                          max=round(float(x.max()), 4), std=round(float(x.std()), 4))
+    print(json.dumps(dict(config=cfg.label, batch=a.batch, users=a.users, prbs=a.prbs, positions=P, runs=a.runs,
+                          multiloss=a.multiloss, w_chest=a.w_chest, grad_ms=stat(g_ms), adam_ms=stat(a_ms),
+                          num_weights=tr.w.numel(), workspace_bytes=int(tr._ws.buf.numel()),
+                          gflop_forward=round(fwd * P * 1e-9, 2), gflop_backward=round(bwd * P * 1e-9, 2),
+                          tflops=round((fwd + bwd) * P / med * 1e-9, 2), loss=tr.loss.tolist())))
+
+
+if __name__ == "__main__":
+    main()
