@@ -261,14 +261,29 @@ struct nrx_handle {
   FusedCtl fused_ctl() const { return FusedCtl{fused_sync, fused_enabled, spin_limit, dbg_err, update_rr}; }
 };
 
-static size_t state_bytes(const nrx_shape* s, int precision) {
-  const size_t es = precision == NRX_PREC_F16 ? 2 : 4;
-  return align256((size_t)s->batch * s->num_tx * s->num_subcarriers * kT * kDS * es);
+// The forward workspace: the slot norms, four state / aggregate planes [B][U][F][14][56] of the storage type
+// (_Float16 or float) and, in f16 workspaces only, the pe16 plane [U][F][14][56] of the one-launch forward.
+// ws == nullptr: the size query.
+struct FwdWs {
+  double* norm;
+  void *s_out, *s_in, *a_out, *a, *pe16;
+  size_t total;
+};
+static FwdWs fwd_layout(const nrx_shape* s, int precision, void* ws) {
+  const bool f16 = precision == NRX_PREC_F16;
+  const size_t plane = (size_t)s->num_tx * s->num_subcarriers * kT * kDS * (f16 ? 2 : 4);
+  Carver c(ws);
+  FwdWs w{};
+  w.norm = c.take<double>(s->batch);
+  w.s_out = c.take<char>(s->batch * plane);
+  w.s_in = c.take<char>(s->batch * plane);
+  w.a_out = c.take<char>(s->batch * plane);
+  w.a = c.take<char>(s->batch * plane);
+  if (f16) w.pe16 = c.take<char>(plane);
+  w.total = c.bytes();
+  return w;
 }
-// pe16 plane [U][F][14][56] f16 of the one-launch forward (f16 workspaces only)
-static size_t pe16_bytes(const nrx_shape* s, int precision) {
-  return precision == NRX_PREC_F16 ? align256((size_t)s->num_tx * s->num_subcarriers * kT * kDS * 2) : 0;
-}
+static size_t ws_bytes_of(const nrx_shape* s, int precision) { return fwd_layout(s, precision, nullptr).total; }
 
 static int check_shape(const nrx_shape* s) {
   if (!s) return fail(NRX_ERR_INVALID_ARG, "shape is NULL");
@@ -300,19 +315,15 @@ static void fill_args(FwdArgs<WT, BT, S>& a, const nrx_handle* h, const nrx_io* 
   a.mcs_mask = io->mcs_mask;
   a.llr = io->llr;
   a.h_ref = io->h_ref;
-  char* p = (char*)ws;
-  a.norm = (double*)p;
-  p += align256((size_t)s->batch * sizeof(double));
-  const size_t sb = state_bytes(s, io->precision);
-  a.s_in = (S*)(p + sb);
-  a.s_out = (S*)p;
-  a.a = (S*)(p + 3 * sb);
-  a.a_out = (S*)(p + 2 * sb);
+  const FwdWs w = fwd_layout(s, io->precision, ws);
+  a.norm = w.norm;
+  a.s_in = (S*)w.s_in;
+  a.s_out = (S*)w.s_out;
+  a.a = (S*)w.a;
+  a.a_out = (S*)w.a_out;
+  a.pe16 = (S*)w.pe16;
   a.ws_base = (const char*)ws;
-  const size_t pb = pe16_bytes(s, io->precision);
-  a.pe16 = pb ? (S*)(p + 4 * sb) : nullptr;
-  const size_t total = (size_t)(p + 4 * sb + pb - (char*)ws);
-  a.ws_bytes = total < 0xFFFFFFFFull ? (unsigned)total : 0xFFFFFFFFu;
+  a.ws_bytes = w.total < 0xFFFFFFFFull ? (unsigned)w.total : 0xFFFFFFFFu;
 }
 
 static int forward_slots(nrx_handle* h, const nrx_io* io, int llr_B, void* workspace, hipStream_t st);
@@ -329,7 +340,7 @@ static int busy(const nrx_handle* h, hipStream_t st) {
 
 // busy() for the whole of a forward entry point, called before ANY of its launches, so a refused
 // call has launched nothing (the y-layout / Aerial preprocessing used to run first).
-static int fused_busy(nrx_handle* h, const nrx_io* io, hipStream_t st) {
+static int fused_busy(nrx_handle* h, const nrx_io* io, void* ws, hipStream_t st) {
   if (io->precision != NRX_PREC_F16) return NRX_OK;
   bool takes = false;
   // decided on the shapes the forward will run: a forward above the 1 GB workspace runs as slot
@@ -341,7 +352,8 @@ static int fused_busy(nrx_handle* h, const nrx_io* io, hipStream_t st) {
     nrx_io c = *io;
     c.shape.batch = n;
     FwdArgs<_Float16, float, _Float16> a{};
-    fill_args(a, h, &c, nullptr, h->m16.init_cinp);   // pointers unused: the decision needs sizes only
+    // ws: the workspace the forward will run in, never null (the size query leaves pe16 null, which gates the path)
+    fill_args(a, h, &c, ws, h->m16.init_cinp);
     takes = takes || fused_would_run(a, io->num_it, h->fused_ctl());
   }
   return takes ? busy(h, st) : NRX_OK;
@@ -437,10 +449,6 @@ void nrx_destroy(nrx_handle* h) {
   delete h;
 }
 
-static size_t ws_bytes_of(const nrx_shape* s, int precision) {
-  return align256((size_t)s->batch * sizeof(double)) + 4 * state_bytes(s, precision) + pe16_bytes(s, precision);
-}
-
 // Slots per sub-forward.  An f16 forward whose workspace would reach kGzRange runs as
 // consecutive forwards of at most this many slots on the caller's stream (slots are independent,
 // neural_rx.py:544-595 has no cross-slot term), each in the same workspace: conv1's z-row loader
@@ -531,15 +539,18 @@ static int forward_slots(nrx_handle* h, const nrx_io* io, int llr_B, void* works
   return launched(e, "kernel launch");
 }
 
-static size_t y_cgnn_bytes(const nrx_handle* h, const nrx_shape* s) {
-  return align256((size_t)s->batch * s->num_subcarriers * s->num_symbols * 2 * h->desc.num_rx_ant * sizeof(float));
+// y in the CGNN layout [B][F][T][2A], the block of a forward_ex workspace in front of the forward's own
+static float* take_y_cgnn(Carver& c, const nrx_handle* h, const nrx_shape* s) {
+  return c.take<float>((size_t)s->batch * s->num_subcarriers * s->num_symbols * 2 * h->desc.num_rx_ant);
 }
 
 int nrx_workspace_size_ex(const nrx_handle* h, const nrx_shape* shape, int32_t precision, int32_t y_layout,
                           size_t* bytes) {
   if (int rc = nrx_workspace_size(h, shape, precision, bytes)) return rc;
   if (y_layout < NRX_Y_CGNN || y_layout > NRX_Y_SPLIT) return fail(NRX_ERR_INVALID_ARG, "unknown y layout");
-  if (y_layout != NRX_Y_CGNN) *bytes += y_cgnn_bytes(h, shape);
+  Carver c(nullptr);
+  if (y_layout != NRX_Y_CGNN) take_y_cgnn(c, h, shape);
+  *bytes += c.bytes();
   return NRX_OK;
 }
 
@@ -555,15 +566,17 @@ int nrx_forward_ex(nrx_handle* h, const nrx_io* io, int32_t y_layout, const floa
   if (!workspace || workspace_bytes < need) return too_small(need);
   if (!io->y || ((y_layout == NRX_Y_SPLIT) != (y_imag != nullptr)))
     return fail(NRX_ERR_INVALID_ARG, "y / y_imag do not match the y layout");
-  if (int rc = fused_busy(h, io, (hipStream_t)stream)) return rc;
-  const size_t yb = y_cgnn_bytes(h, &io->shape);
-  float* ycg = (float*)workspace;
+  Carver c(workspace);
+  float* ycg = take_y_cgnn(c, h, &io->shape);
+  const size_t fwd_bytes = workspace_bytes - c.bytes();   // the rest is the forward's
+  void* fwd_ws = c.take<char>(fwd_bytes);
+  if (int rc = fused_busy(h, io, fwd_ws, (hipStream_t)stream)) return rc;
   hipError_t e = launch_y_layout(io->y, y_imag, y_layout, io->shape.batch, io->shape.num_subcarriers,
                                  io->shape.num_symbols, h->desc.num_rx_ant, ycg, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "y layout launch");
   nrx_io cio = *io;
   cio.y = ycg;
-  return nrx_forward(h, &cio, (char*)workspace + yb, workspace_bytes - yb, stream);
+  return nrx_forward(h, &cio, fwd_ws, fwd_bytes, stream);
 }
 
 // ---------------------------------------------------------------- Aerial contract
@@ -584,20 +597,15 @@ AerialWs aerial_layout(const nrx_handle* h, const nrx_aerial_io* io, void* base,
   const size_t A2 = 2 * (size_t)h->desc.num_rx_ant;
   const size_t re = (size_t)s.num_subcarriers * s.num_symbols;
   AerialWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += align256(bytes);
-    return (char*)base + o;
-  };
-  w.y = (float*)take((size_t)s.batch * re * A2 * 4);
-  w.h = (float*)take((size_t)s.batch * s.num_tx * re * A2 * 4);
-  w.pe = (float*)take((size_t)s.num_tx * re * 2 * 4);
-  w.nn = (int32_t*)take((size_t)s.num_tx * s.num_symbols * 12 * 4);
-  w.llr = (float*)take((size_t)num_heads(&h->desc) * s.batch * s.num_tx * re * bits_max(&h->desc) * 4);
-  w.cgnn = take(cgnn_bytes);
+  Carver c(base);
+  w.y = c.take<float>((size_t)s.batch * re * A2);
+  w.h = c.take<float>((size_t)s.batch * s.num_tx * re * A2);
+  w.pe = c.take<float>((size_t)s.num_tx * re * 2);
+  w.nn = c.take<int32_t>((size_t)s.num_tx * s.num_symbols * 12);
+  w.llr = c.take<float>((size_t)num_heads(&h->desc) * s.batch * s.num_tx * re * bits_max(&h->desc));
+  w.cgnn = c.take<char>(cgnn_bytes);
   w.cgnn_bytes = cgnn_bytes;
-  w.total = off;
+  w.total = c.bytes();
   return w;
 }
 
@@ -668,7 +676,7 @@ int nrx_forward_aerial(nrx_handle* h, const nrx_aerial_io* io, void* workspace, 
   cio.active = io->dmrs_port_mask;
   cio.llr = w.llr;
   cio.h_ref = io->h_hat;
-  if (int rc = fused_busy(h, &cio, st)) return rc;
+  if (int rc = fused_busy(h, &cio, w.cgnn, st)) return rc;
   hipError_t e = aerial_prepare(h, io, w.y, w.h, w.pe, w.nn, st);
   if (e != hipSuccess) return hip_fail(e, "aerial preprocessing launch");
   if (int rc = nrx_forward(h, &cio, w.cgnn, w.cgnn_bytes, stream)) return rc;
@@ -711,8 +719,7 @@ static int check_gen(const nrx_gen_desc* d) {
 }
 
 int nrx_gen_workspace_size(const nrx_gen_desc* desc, size_t* bytes) {
-  if (int rc = check_gen(desc)) return rc;
-  return store_size(bytes, gen_workspace_bytes(*desc, nullptr, nullptr));
+  return nrx_gen_workspace_size_cfo(desc, nullptr, bytes);
 }
 
 int nrx_generate_slots(const nrx_gen_desc* desc, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
@@ -743,11 +750,7 @@ static int check_gen_cfo(const nrx_gen_desc* d, const nrx_gen_cfo* cfo, GenCfo* 
 }
 
 int nrx_gen_workspace_size_cfo(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, size_t* bytes) {
-  if (int rc = check_gen(desc)) return rc;
-  GenCfo g{};
-  bool on;
-  if (int rc = check_gen_cfo(desc, cfo, &g, &on)) return rc;
-  return store_size(bytes, gen_workspace_bytes(*desc, nullptr, nullptr) + (on ? cfo_workspace_bytes(*desc) : 0));
+  return nrx_gen_workspace_size_dmrs(desc, cfo, nullptr, bytes);
 }
 
 int nrx_generate_slots_ex(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_out* out, void* workspace,
@@ -857,23 +860,21 @@ static int check_gen_tc(const nrx_gen_desc* d, const nrx_gen_chan* c, const nrx_
 }
 
 // The generator's stage planner: every descriptor check of a generator call in one order, the resolved ports
-// (*c; chan_known = false for the size calls that take no chan: the desc's scalars) and offset (*g, *cfo_on),
-// and *need, the workspace: the generator's own, then the block of the one sample-domain stage (the x' of a
-// CFO, the x' and samples of a td, the buffers of a tc), the pilot table, the replayed H
-static int plan_gen(const nrx_gen_desc* d, bool chan_known, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
-                    const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td, const nrx_gen_tc* tc,
-                    nrx_gen_chan* c, GenCfo* g, bool* cfo_on, size_t* need) {
+// (p->c; a NULL chan, as in the size calls that take none: the desc's scalars) and offset (p->cfo, p->cfo_on),
+// the stages and the workspace blocks (gen_layout)
+static int plan_gen(const nrx_gen_desc* d, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
+                    const nrx_gen_cir* cir, const nrx_gen_td* td, const nrx_gen_tc* tc, GenPlan* p) {
   if (int rc = check_gen(d)) return rc;
   if (cir && chan) return fail(NRX_ERR_INVALID_ARG, "chan must be NULL with a cir: the dataset is the channel");
-  if (int rc = check_gen_chan(d, chan_known ? chan : nullptr, c)) return rc;
-  if (int rc = check_gen_cfo(d, cfo, g, cfo_on)) return rc;
+  if (int rc = check_gen_chan(d, chan, &p->c)) return rc;
+  if (int rc = check_gen_cfo(d, cfo, &p->cfo, &p->cfo_on)) return rc;
   if (int rc = check_gen_dmrs(d, dmrs)) return rc;
   if (int rc = check_gen_cir(d, cir)) return rc;
-  if (int rc = check_gen_td(d, td, *cfo_on)) return rc;
-  if (int rc = check_gen_tc(d, c, tc, *cfo_on, cir, td)) return rc;
-  *need = gen_workspace_bytes(*d, nullptr, nullptr) + (*cfo_on ? cfo_workspace_bytes(*d) : 0) +
-          (td ? td_workspace_bytes(*d, *td) : 0) + (tc ? tc_workspace_bytes(*d, *tc) : 0) +
-          (dmrs ? dmrs_workspace_bytes(*d) : 0) + (cir ? cir_workspace_bytes(*d) : 0);
+  if (int rc = check_gen_td(d, td, p->cfo_on)) return rc;
+  if (int rc = check_gen_tc(d, &p->c, tc, p->cfo_on, cir, td)) return rc;
+  p->d = *d;
+  p->dmrs = dmrs, p->cir = cir, p->td = td, p->tc = tc;
+  gen_layout(*p);
   return NRX_OK;
 }
 
@@ -884,23 +885,15 @@ int nrx_gen_workspace_size_cir(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo,
 
 int nrx_gen_workspace_size_td(const nrx_gen_desc* desc, const nrx_gen_cfo* cfo, const nrx_gen_dmrs* dmrs,
                               const nrx_gen_cir* cir, const nrx_gen_td* td, size_t* bytes) {
-  nrx_gen_chan c{};
-  GenCfo g{};
-  bool on;
-  size_t need = 0;
-  if (int rc = plan_gen(desc, false, nullptr, cfo, dmrs, cir, td, nullptr, &c, &g, &on, &need)) return rc;
-  return store_size(bytes, need);
+  return nrx_gen_workspace_size_tc(desc, nullptr, cfo, dmrs, cir, td, nullptr, bytes);
 }
 
 int nrx_gen_workspace_size_tc(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
                               const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
                               const nrx_gen_tc* tc, size_t* bytes) {
-  nrx_gen_chan c{};
-  GenCfo g{};
-  bool on;
-  size_t need = 0;
-  if (int rc = plan_gen(desc, true, chan, cfo, dmrs, cir, td, tc, &c, &g, &on, &need)) return rc;
-  return store_size(bytes, need);
+  GenPlan p{};
+  if (int rc = plan_gen(desc, chan, cfo, dmrs, cir, td, tc, &p)) return rc;
+  return store_size(bytes, p.total);
 }
 
 int nrx_generate_slots_cir(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
@@ -919,21 +912,16 @@ int nrx_generate_slots_tc(const nrx_gen_desc* desc, const nrx_gen_chan* chan, co
                           const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
                           const nrx_gen_tc* tc, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
                           void* stream) {
-  nrx_gen_chan c{};
-  GenCfo g{};
-  bool cfo_on;
-  size_t need = 0;
-  if (int rc = plan_gen(desc, true, chan, cfo, dmrs, cir, td, tc, &c, &g, &cfo_on, &need)) return rc;
+  GenPlan p{};
+  if (int rc = plan_gen(desc, chan, cfo, dmrs, cir, td, tc, &p)) return rc;
   if (!out || !out->y) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (out->bits)
     if (int rc = check_bits_stride(out->bits_stride, desc->mcs_bits, desc->num_mcs)) return rc;
   if ((out->y_real == nullptr) != (out->y_imag == nullptr))
     return fail(NRX_ERR_INVALID_ARG, "Aerial outputs come in (real, imag) pairs");
   if (int rc = check_aerial_list(out->h_ls_real, out->h_ls_imag, desc->num_subcarriers)) return rc;
-  if (int rc = check_workspace(workspace, workspace_bytes, need, 1)) return rc;
-  return launched(
-      launch_generate(*desc, c, *out, workspace, (hipStream_t)stream, cfo_on ? &g : nullptr, dmrs, cir, td, tc),
-      "slot generator launch");
+  if (int rc = check_workspace(workspace, workspace_bytes, p.total, 1)) return rc;
+  return launched(launch_generate(p, *out, workspace, (hipStream_t)stream), "slot generator launch");
 }
 
 // nrx_time_channel
@@ -983,8 +971,7 @@ static int check_ofdm(const nrx_ofdm_io* io, bool modulate) {
     return rc;
   if (!modulate)
     if (int rc = check_range("timing_advance", io->timing_advance, 0, min_cp)) return rc;
-  int64_t need = 0;
-  for (int t = 0; t < io->num_symbols; ++t) need += io->cp_length[t] + io->fft_size;
+  const int64_t need = slot_samples(io->cp_length, io->fft_size, io->num_symbols);
   if (io->num_samples < need)
     return fail(NRX_ERR_SHAPE, "num_samples must be >= " + std::to_string(need) + ", the symbols with their prefixes");
   return NRX_OK;

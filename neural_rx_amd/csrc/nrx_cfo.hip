@@ -267,10 +267,7 @@ unsigned phase_chunks(int64_t F, int64_t A) { return (unsigned)((F * kT * A + kP
 
 }  // namespace
 
-size_t cfo_workspace_bytes(const nrx_gen_desc& d) {
-  const size_t n = (size_t)d.batch * d.num_tx * d.num_subcarriers * kT * 2 * sizeof(double);
-  return (n + 255) / 256 * 256;
-}
+size_t cfo_workspace_bytes(const nrx_gen_desc& d) { return align256(gen_grid_elems(d) * sizeof(double2)); }
 
 hipError_t launch_cfo_apply(const nrx_gen_desc& d, const GenCfo& c, const double* x, const float* active, double* xp,
                             hipStream_t st) {

@@ -47,22 +47,15 @@ __host__ __device__ inline int cir_f_tiles(int F) { return (F + kCirTM - 1) / kC
 // one step start 128 bytes apart modulo the 256 bytes of the LDS banks
 __host__ __device__ inline int cir_g_stride(int ncol) { return ncol % 32 == 16 ? ncol : ncol + 16; }
 
-size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
-size_t cir_ws(const nrx_gen_desc& d, CirWs* w, char* base) {
+size_t cir_ws(const nrx_gen_desc& d, CirWs* w, void* base) {
   const size_t BU = (size_t)d.batch * d.num_tx, F = d.num_subcarriers, A = d.num_rx_ant;
-  size_t o = 0;
-  auto take = [&](size_t n) {
-    char* p = base ? base + o : nullptr;
-    o += al(n);
-    return p;
-  };
+  Carver c(base);
   CirWs v;
-  v.H = (double2*)take(BU * F * kT * A * sizeof(double2));
-  v.part = (double*)take(BU * cir_f_tiles((int)F) * cir_col_groups((int)A) * sizeof(double));
-  v.scale = (double*)take(BU * sizeof(double));
+  v.H = c.take<double2>(BU * F * kT * A);
+  v.part = c.take<double>(BU * cir_f_tiles((int)F) * cir_col_groups((int)A));
+  v.scale = c.take<double>(BU);
   if (w) *w = v;
-  return o;
+  return c.bytes();
 }
 
 // the example of (slot b, user u), or -1: a zero channel
@@ -274,7 +267,7 @@ size_t cir_workspace_bytes(const nrx_gen_desc& d) { return cir_ws(d, nullptr, nu
 hipError_t launch_cir_rx(const nrx_gen_desc& d, const nrx_gen_cir& c, const double* x, void* ws, float* y, float* h,
                          float* y_re, float* y_im, hipStream_t st) {
   CirWs w;
-  cir_ws(d, &w, (char*)ws);
+  cir_ws(d, &w, ws);
   const int F = d.num_subcarriers, A = d.num_rx_ant;
   const int64_t BU = (int64_t)d.batch * d.num_tx;
   const int nft = cir_f_tiles(F), ncg = cir_col_groups(A);

@@ -10,6 +10,7 @@
 //   dense:          wT [COUTP][CINP], bias [COUTP]
 //   WT = _Float16 / double, BT = float / double.  Zero padding everywhere.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/nrx.h"
@@ -40,6 +41,24 @@ constexpr unsigned kGzRange = 0x40000000u;
 // StateInit pads each antenna block of its input z = [y | h | pe] to A2P channels; the weight packer
 // (nrx_model.cpp) and the launchers (nrx_launch.inc) pick the kernels' A2P with this one rule
 constexpr int init_a2p(int num_rx_ant) { return 2 * num_rx_ant <= 8 ? 8 : (2 * num_rx_ant <= 16 ? 16 : 32); }
+
+// ---- workspaces (host).  Every block of a workspace starts on a 256-byte boundary of it.
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+// The carver lays a workspace out: take() hands out the next block.  A null base is the size query: every
+// block is null and bytes() the workspace size, so the size a caller is told and the pointers the kernels get
+// come from one walk.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* ws) : base((char*)ws) {}
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += align256(count * sizeof(T));
+    return p;
+  }
+  size_t bytes() const { return off; }
+};
 
 // ---- LDS images of the f16 weights (kernels: SepStage / DenseStage).  A W^T [COUTP][CINP] image is a stack
 // of 16-row tiles addressed like an activation image: element (co, chunk q of 8 inputs) at
@@ -167,24 +186,38 @@ hipError_t launch_aerial_llr(const float* llr, int B, int U, int F, int T, int b
                              hipStream_t st);
 
 // Slot generator + error counters (nrx_synth.hip); struct types from include/nrx.h.
-// gen_workspace_bytes(d, nullptr, nullptr) = workspace size.
+// elements of one [B][U][F][14] grid: x and the x' of the stages, complex f64
+inline size_t gen_grid_elems(const nrx_gen_desc& d) {
+  return (size_t)d.batch * d.num_tx * d.num_subcarriers * kT;
+}
+// the resolved carrier frequency offset of a generator call (nrx_cfo.hip)
+struct GenCfo {
+  double eps_max[16];                // cfo_hz[u] / subcarrier_spacing
+  int constant;
+  int fft_size;                      // N, resolved (never 0)
+  int h_with_phase;
+  double* eps_out;
+};
+// One generator call: what the checks of nrx_api.cpp (plan_gen) resolved, the optional stages (null: absent)
+// and the blocks of its workspace.  gen_layout (nrx_synth.hip) alone knows their order.
+struct GenPlan {
+  nrx_gen_desc d;
+  nrx_gen_chan c;                    // the resolved ports
+  GenCfo cfo;
+  bool cfo_on;                       // a port has a non-zero offset
+  const nrx_gen_dmrs* dmrs;
+  const nrx_gen_cir* cir;
+  const nrx_gen_td* td;
+  const nrx_gen_tc* tc;
+  // byte offsets: behind the generator's own block at 0 the block of the one sample-domain stage (the x' of a
+  // cfo, the x' and samples of a td, the buffers of a tc), the pilot table and the replayed channel
+  size_t stage, pilots, cir_ws, total;
+};
+void gen_layout(GenPlan& p);
+hipError_t launch_generate(const GenPlan& p, const nrx_gen_out& o, void* ws, hipStream_t st);
+// the generator's own block: gen_workspace_bytes(d, nullptr, nullptr) = its size
 struct GenWs;
-size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base);
-// cfo (optional, nrx_generate_slots_cfo with a non-zero offset): the workspace holds the x' buffer
-// (cfo_workspace_bytes) behind the generator's own
-struct GenCfo;
-// dmrs (optional, nrx_generate_slots_dmrs): cover-coded ports; the pilot table (dmrs_workspace_bytes) lies
-// behind everything else, and h_hat / the Aerial list come from launch_ls_estimate
-// cir (optional, nrx_generate_slots_cir): the channel is replayed from the caller's impulse responses;
-// H in f64 and its energy sums (cir_workspace_bytes) lie behind the pilot table
-// td (optional, nrx_generate_slots_td; never with a cfo): the time-domain transmit stage; its x' lies where
-// the CFO's would, behind the generator's own workspace, and its sample buffer behind that (td_workspace_bytes)
-// tc (optional, nrx_generate_slots_tc; never with a cfo, a cir or a td): the time-domain channel takes the place
-// of k_gen_rx; its block (tc_workspace_bytes) lies where the other stages' would
-hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
-                           hipStream_t st, const GenCfo* cfo = nullptr, const nrx_gen_dmrs* dmrs = nullptr,
-                           const nrx_gen_cir* cir = nullptr, const nrx_gen_td* td = nullptr,
-                           const nrx_gen_tc* tc = nullptr);
+size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, void* base);
 size_t dmrs_workspace_bytes(const nrx_gen_desc& d);
 // nrx_generate_taps: the finished taps and delays of the built-in channel, rounded to f32
 hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, float* a_out, float* tau_out, void* ws,
@@ -202,13 +235,6 @@ hipError_t launch_count_errors(const nrx_count_io& c, hipStream_t st);
 
 // Carrier frequency offset (nrx_cfo.hip); validated by nrx_generate_slots_cfo / nrx_cfo_estimate /
 // nrx_cfo_rotate.  x, xp: [B][U][F][14] complex f64 (re, im)
-struct GenCfo {
-  double eps_max[16];                // cfo_hz[u] / subcarrier_spacing
-  int constant;
-  int fft_size;                      // N, resolved (never 0)
-  int h_with_phase;
-  double* eps_out;
-};
 size_t cfo_workspace_bytes(const nrx_gen_desc& d);
 hipError_t launch_cfo_apply(const nrx_gen_desc& d, const GenCfo& c, const double* x, const float* active, double* xp,
                             hipStream_t st);
@@ -220,6 +246,25 @@ hipError_t launch_cfo_rotate(const nrx_cfo_io& io, hipStream_t st);
 // nrx_ofdm_modulate / nrx_ofdm_demodulate, td by nrx_generate_slots_td.  launch_td_apply: x [B][U][F][14]
 // complex f64 -> x' at the start of ws (td_workspace_bytes), the samples behind it
 hipError_t launch_ofdm(const nrx_ofdm_io& io, bool modulate, hipStream_t st);
+// samples of one row: the symbols with their prefixes
+inline int64_t slot_samples(const int32_t* cp_length, int fft_size, int num_symbols) {
+  int64_t n = 0;
+  for (int t = 0; t < num_symbols; ++t) n += cp_length[t] + fft_size;
+  return n;
+}
+// the f64 planar nrx_ofdm_io of a generator stage s (nrx_gen_td, nrx_gen_tc) over `streams` rows per slot;
+// the caller adds what only its stage has (amplifier, offsets, timing advance)
+template <class Stage>
+nrx_ofdm_io stage_ofdm(const nrx_gen_desc& d, const Stage& s, int streams, void* grid, void* samples) {
+  nrx_ofdm_io io{};
+  io.batch = d.batch, io.num_streams = streams, io.grid_subcarriers = d.num_subcarriers, io.num_symbols = kT;
+  io.fft_size = s.fft_size, io.first_bin = s.first_bin;
+  for (int t = 0; t < kT; ++t) io.cp_length[t] = s.cp_length[t];
+  io.precision = NRX_OFDM_F64, io.grid_layout = NRX_OFDM_GRID_PLANAR;
+  io.num_samples = slot_samples(s.cp_length, s.fft_size, kT);
+  io.grid = grid, io.samples = samples;
+  return io;
+}
 size_t td_workspace_bytes(const nrx_gen_desc& d, const nrx_gen_td& td);
 hipError_t launch_td_apply(const nrx_gen_desc& d, const nrx_gen_td& td, const double* x, void* ws, hipStream_t st);
 hipError_t launch_td_h_phase(const nrx_gen_desc& d, const nrx_gen_td& td, float* h, hipStream_t st);

@@ -15,8 +15,6 @@ namespace nrx {
 int fail(int code, const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
 
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
 // Topology checks: the kernels are specialised for the in-scope configs.
 int check_desc(const nrx_desc* d);
 

@@ -302,42 +302,36 @@ hipError_t launch_ofdm(const nrx_ofdm_io& io, bool modulate, hipStream_t st) {
 
 // ---- the generator's time-domain stage: x' = demodulate(impair(modulate(x))) per (slot, port), f64
 
-static int64_t td_row_samples(const nrx_gen_td& td) {
-  int64_t L = 0;
-  for (int t = 0; t < kT; ++t) L += td.cp_length[t] + td.fft_size;
-  return L;
+struct TdWs {
+  double2* xp;        // [B][U][F][14]
+  double2* samples;   // [B][U][Ls]
+};
+
+static size_t td_layout(const nrx_gen_desc& d, const nrx_gen_td& td, TdWs* w, void* base) {
+  Carver c(base);
+  TdWs v;
+  v.xp = c.take<double2>(gen_grid_elems(d));
+  v.samples = c.take<double2>((size_t)d.batch * d.num_tx * (size_t)slot_samples(td.cp_length, td.fft_size, kT));
+  if (w) *w = v;
+  return c.bytes();
 }
 
-static size_t td_xp_bytes(const nrx_gen_desc& d) {
-  const size_t n = (size_t)d.batch * d.num_tx * d.num_subcarriers * kT * 2 * sizeof(double);
-  return (n + 255) / 256 * 256;
-}
-
-size_t td_workspace_bytes(const nrx_gen_desc& d, const nrx_gen_td& td) {
-  const size_t n = (size_t)d.batch * d.num_tx * (size_t)td_row_samples(td) * 2 * sizeof(double);
-  return td_xp_bytes(d) + (n + 255) / 256 * 256;
-}
+size_t td_workspace_bytes(const nrx_gen_desc& d, const nrx_gen_td& td) { return td_layout(d, td, nullptr, nullptr); }
 
 hipError_t launch_td_apply(const nrx_gen_desc& d, const nrx_gen_td& td, const double* x, void* ws, hipStream_t st) {
-  nrx_ofdm_io io{};
-  io.batch = d.batch, io.num_streams = d.num_tx, io.grid_subcarriers = d.num_subcarriers, io.num_symbols = kT;
-  io.fft_size = td.fft_size, io.first_bin = td.first_bin;
-  for (int t = 0; t < kT; ++t) io.cp_length[t] = td.cp_length[t];
-  io.precision = NRX_OFDM_F64, io.grid_layout = NRX_OFDM_GRID_PLANAR;
-  io.num_samples = td_row_samples(td);
+  TdWs w;
+  td_layout(d, td, &w, ws);
+  nrx_ofdm_io io = stage_ofdm(d, td, d.num_tx, const_cast<double*>(x), w.samples);
   if (td.pa_enable) {
     io.pa_asat = sqrt((double)d.num_subcarriers / td.fft_size) * pow(10.0, td.pa_ibo_db / 20.0);
     io.pa_smoothness = td.pa_smoothness;
   }
-  io.grid = const_cast<double*>(x);
-  io.samples = (char*)ws + td_xp_bytes(d);
   if (hipError_t e = launch_ofdm(io, /*modulate=*/true, st)) return e;
   for (int u = 0; u < d.num_tx; ++u) io.offset[u] = -td.delay[u];
-  io.grid = ws;
+  io.grid = w.xp;
   if (hipError_t e = launch_ofdm(io, /*modulate=*/false, st)) return e;
   if (td.x_out)
-    return hipMemcpyAsync(td.x_out, ws, (size_t)d.batch * d.num_tx * d.num_subcarriers * kT * 2 * sizeof(double),
-                          hipMemcpyDeviceToDevice, st);
+    return hipMemcpyAsync(td.x_out, w.xp, gen_grid_elems(d) * sizeof(double2), hipMemcpyDeviceToDevice, st);
   return hipSuccess;
 }
 

@@ -552,32 +552,42 @@ __global__ __launch_bounds__(NRX_CNT_T) void k_count_errors_re(nrx_count_io c, i
   }
 }
 
-size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
 }  // namespace
 
-size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, char* base) {
-  const size_t B = d.batch, U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols, A = d.num_rx_ant,
-               L = d.num_taps;
-  size_t o = 0;
-  auto take = [&](size_t n) {
-    char* p = base ? base + o : nullptr;
-    o += al(n);
-    return p;
-  };
+size_t gen_workspace_bytes(const nrx_gen_desc& d, GenWs* w, void* base) {
+  const size_t BU = (size_t)d.batch * d.num_tx, A = d.num_rx_ant, L = d.num_taps;
+  Carver c(base);
   GenWs v;
-  v.x = (double2*)take(B * U * F * T * sizeof(double2));
-  v.gt = (double2*)take(B * U * A * L * T * sizeof(double2));
-  v.tau = (double*)take(B * U * L * sizeof(double));
-  v.spdp = (double*)take(B * U * L * sizeof(double));
-  v.mcs = (uint8_t*)take(B * U);
-  v.active = (float*)take(B * U * sizeof(float));
+  v.x = c.take<double2>(gen_grid_elems(d));
+  v.gt = c.take<double2>(BU * A * L * kT);
+  v.tau = c.take<double>(BU * L);
+  v.spdp = c.take<double>(BU * L);
+  v.mcs = c.take<uint8_t>(BU);
+  v.active = c.take<float>(BU);
   if (w) *w = v;
-  return o;
+  return c.bytes();
 }
 
+// the pilot table [2][pmax][nd][2] f32 of k_gen_pilots
 size_t dmrs_workspace_bytes(const nrx_gen_desc& d) {
-  return al((size_t)2 * ((d.num_subcarriers + 1) / 2) * d.num_dmrs_symbols * 2 * sizeof(float));
+  return align256((size_t)2 * ((d.num_subcarriers + 1) / 2) * d.num_dmrs_symbols * 2 * sizeof(float));
+}
+
+// The block order of the generator workspace, the one place that knows it: the generator's own block, the block
+// of the one sample-domain stage (plan_gen admits one of cfo, td and tc), the pilot table, the replayed channel.
+void gen_layout(GenPlan& p) {
+  p.stage = gen_workspace_bytes(p.d, nullptr, nullptr);
+  p.pilots = p.stage + (p.cfo_on ? cfo_workspace_bytes(p.d) : 0) + (p.td ? td_workspace_bytes(p.d, *p.td) : 0) +
+             (p.tc ? tc_workspace_bytes(p.d, *p.tc) : 0);
+  p.cir_ws = p.pilots + (p.dmrs ? dmrs_workspace_bytes(p.d) : 0);
+  p.total = p.cir_ws + (p.cir ? cir_workspace_bytes(p.d) : 0);
+}
+
+// receive-antenna mixing of the finished taps in w.gt
+static void launch_mix(const nrx_gen_desc& d, const nrx_gen_chan& c, const GenWs& w, hipStream_t st) {
+  const int64_t n = (int64_t)d.batch * d.num_tx * d.num_taps * kT;
+  if (c.rx_mix)
+    k_gen_mix<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(w, c.rx_mix, d.num_rx_ant, d.num_taps * kT, n);
 }
 
 // the taps of the built-in channel into w.gt / w.tau (and active / mcs, which k_gen_params draws with them)
@@ -587,9 +597,7 @@ static void launch_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, const GenW
   k_gen_params<<<(unsigned)B, 64, 0, st>>>(d, c, w, o.active, o.mcs_mask, o.mcs);
   if (!taps) return;
   k_gen_taps<<<(unsigned)((B * U * A * L + kTapGroups - 1) / kTapGroups), kTapGroups * kT, 0, st>>>(d, c, w);
-  if (c.rx_mix)
-    k_gen_mix<<<(unsigned)((B * U * L * kT + 255) / 256), 256, 0, st>>>(w, c.rx_mix, (int)A, (int)(L * kT),
-                                                                        B * U * L * kT);
+  launch_mix(d, c, w, st);
 }
 
 // one thread per complex tap (a_out has the layout of w.gt) and per delay
@@ -607,7 +615,7 @@ __global__ __launch_bounds__(256) void k_export_taps(GenWs w, int64_t ntap, int6
 hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, float* a_out, float* tau_out, void* ws,
                               hipStream_t st) {
   GenWs w;
-  gen_workspace_bytes(d, &w, (char*)ws);
+  gen_workspace_bytes(d, &w, ws);
   const nrx_gen_out none{};
   launch_taps(d, c, w, none, true, st);
   const int64_t ntau = (int64_t)d.batch * d.num_tx * d.num_taps, ntap = ntau * d.num_rx_ant * kT;
@@ -615,64 +623,57 @@ hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, floa
   return hipGetLastError();
 }
 
-hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_out& o, void* ws,
-                           hipStream_t st, const GenCfo* cfo, const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir,
-                           const nrx_gen_td* td, const nrx_gen_tc* tc) {
+hipError_t launch_generate(const GenPlan& p, const nrx_gen_out& o, void* ws, hipStream_t st) {
+  const nrx_gen_desc& d = p.d;
+  const nrx_gen_chan& c = p.c;
+  const GenCfo* cfo = p.cfo_on ? &p.cfo : nullptr;
+  char* const stage = (char*)ws + p.stage;   // of whichever sample-domain stage the call has
   GenWs w;
-  const size_t own = gen_workspace_bytes(d, &w, (char*)ws);
-  // the sample-domain stage's block behind the generator's own: the x' of a CFO, x' and the samples of a td,
-  // or the samples, sinusoids and antenna grids of a tc
-  const size_t tx = cfo ? cfo_workspace_bytes(d)
-                        : (td ? td_workspace_bytes(d, *td) : (tc ? tc_workspace_bytes(d, *tc) : 0));
+  gen_workspace_bytes(d, &w, ws);
   const int64_t B = d.batch, U = d.num_tx, F = d.num_subcarriers, T = d.num_symbols, A = d.num_rx_ant;
   auto blocks = [](int64_t n) { return (unsigned)((n + 255) / 256); };
   // a replayed channel keeps the active ports and the MCS; so does the time-domain channel, whose taps are the
   // window means of the per-sample gains, mixed over the antennas like the grid channel's
-  launch_taps(d, c, w, o, /*taps=*/!cir && !tc, st);
-  if (tc) {
-    if (hipError_t e = launch_tc_taps(d, c, *tc, w.tau, w.spdp, reinterpret_cast<double*>(w.gt), (char*)ws + own, st))
-      return e;
-    if (c.rx_mix)
-      k_gen_mix<<<(unsigned)((B * U * d.num_taps * kT + 255) / 256), 256, 0, st>>>(
-          w, c.rx_mix, (int)A, (int)(d.num_taps * kT), B * U * d.num_taps * kT);
+  launch_taps(d, c, w, o, /*taps=*/!p.cir && !p.tc, st);
+  if (p.tc) {
+    if (hipError_t e = launch_tc_taps(d, c, *p.tc, w.tau, w.spdp, reinterpret_cast<double*>(w.gt), stage, st)) return e;
+    launch_mix(d, c, w, st);
   }
   GenDmrs dm{};
-  if (dmrs) {
-    dm.ptab = reinterpret_cast<float*>((char*)ws + own + tx);
+  if (p.dmrs) {
+    dm.ptab = reinterpret_cast<float*>((char*)ws + p.pilots);
     dm.pmax = (int)((F + 1) / 2);
     for (int u = 0; u < U; ++u) {
-      dm.focc |= (unsigned)dmrs->focc[u] << u;
-      dm.tocc |= (unsigned)dmrs->tocc[u] << u;
+      dm.focc |= (unsigned)p.dmrs->focc[u] << u;
+      dm.tocc |= (unsigned)p.dmrs->tocc[u] << u;
     }
     k_gen_pilots<<<blocks(2 * dm.pmax * d.num_dmrs_symbols), 256, 0, st>>>(d, dm.pmax, const_cast<float*>(dm.ptab),
-                                                                          dmrs->pilots_out);
+                                                                          p.dmrs->pilots_out);
   }
   k_gen_tx<<<blocks(B * U * F * T), 256, 0, st>>>(d, w, o.bits, o.bits_stride, dm);
   const int at = (int)(A * T);
   int FB = 256 / at;
   if (FB > 4) FB = 4;
-  // with a carrier frequency offset the channel acts on x' = (CFO) x, which lies behind the
-  // generator's own workspace; the clean x stays for the LS division by the known pilots
+  // with a carrier frequency offset the channel acts on x' = (CFO) x, which starts the stage block;
+  // the clean x stays for the LS division by the known pilots
   GenWs wr = w;
   if (cfo) {
-    wr.x = reinterpret_cast<double2*>((char*)ws + own);
+    wr.x = reinterpret_cast<double2*>(stage);
     if (hipError_t e = launch_cfo_apply(d, *cfo, reinterpret_cast<const double*>(w.x), w.active,
                                         reinterpret_cast<double*>(wr.x), st))
       return e;
   }
-  if (td) {        // x' = demodulate(impair(modulate(x))), in the same place
-    wr.x = reinterpret_cast<double2*>((char*)ws + own);
-    if (hipError_t e = launch_td_apply(d, *td, reinterpret_cast<const double*>(w.x), wr.x, st)) return e;
+  if (p.td) {        // x' = demodulate(impair(modulate(x))), in the same place
+    wr.x = reinterpret_cast<double2*>(stage);
+    if (hipError_t e = launch_td_apply(d, *p.td, reinterpret_cast<const double*>(w.x), stage, st)) return e;
   }
-  if (tc) {
-    if (hipError_t e = launch_tc_rx(d, c, *tc, reinterpret_cast<const double*>(w.x), w.tau,
-                                    reinterpret_cast<const double*>(w.gt), (char*)ws + own, o.y, o.h, o.y_real,
-                                    o.y_imag, st))
+  if (p.tc) {
+    if (hipError_t e = launch_tc_rx(d, c, *p.tc, reinterpret_cast<const double*>(w.x), w.tau,
+                                    reinterpret_cast<const double*>(w.gt), stage, o.y, o.h, o.y_real, o.y_imag, st))
       return e;
-  } else if (cir) {
-    char* cws = (char*)ws + own + tx + (dmrs ? dmrs_workspace_bytes(d) : 0);
-    if (hipError_t e = launch_cir_rx(d, *cir, reinterpret_cast<const double*>(wr.x), cws, o.y, o.h, o.y_real,
-                                     o.y_imag, st))
+  } else if (p.cir) {
+    if (hipError_t e = launch_cir_rx(d, *p.cir, reinterpret_cast<const double*>(wr.x), (char*)ws + p.cir_ws, o.y, o.h,
+                                     o.y_real, o.y_imag, st))
       return e;
   } else {
     k_gen_rx<<<dim3((unsigned)((F + FB - 1) / FB), (unsigned)B), FB * at, 0, st>>>(d, wr, FB, o.y, o.h, o.y_real,
@@ -680,17 +681,17 @@ hipError_t launch_generate(const nrx_gen_desc& d, const nrx_gen_chan& c, const n
   }
   if (cfo && cfo->h_with_phase && o.h)
     if (hipError_t e = launch_cfo_h_phase(d, *cfo, o.h, st)) return e;
-  if (td && td->h_with_delay && o.h)
-    if (hipError_t e = launch_td_h_phase(d, *td, o.h, st)) return e;
-  if (dmrs) {      // one definition: the receiver-side estimator, on this call's y, pilot table and active mask
+  if (p.td && p.td->h_with_delay && o.h)
+    if (hipError_t e = launch_td_h_phase(d, *p.td, o.h, st)) return e;
+  if (p.dmrs) {      // one definition: the receiver-side estimator, on this call's y, pilot table and active mask
     if (!o.h_hat && !o.h_ls_real) return hipGetLastError();
     nrx_ls_io io{};
     io.batch = d.batch, io.num_tx = d.num_tx, io.num_subcarriers = d.num_subcarriers, io.num_symbols = d.num_symbols;
     io.num_rx_ant = d.num_rx_ant, io.num_dmrs_symbols = d.num_dmrs_symbols;
     for (int k = 0; k < d.num_dmrs_symbols; ++k) io.dmrs_symbols[k] = d.dmrs_symbols[k];
     for (int u = 0; u < U; ++u)
-      io.cdm_group[u] = d.cdm_group[u], io.focc[u] = dmrs->focc[u], io.tocc[u] = dmrs->tocc[u];
-    io.despread_f = dmrs->despread_f, io.despread_t = dmrs->despread_t;
+      io.cdm_group[u] = d.cdm_group[u], io.focc[u] = p.dmrs->focc[u], io.tocc[u] = p.dmrs->tocc[u];
+    io.despread_f = p.dmrs->despread_f, io.despread_t = p.dmrs->despread_t;
     io.y = o.y, io.pilots = dm.ptab, io.active = w.active;
     io.h_hat = o.h_hat, io.h_ls_real = o.h_ls_real, io.h_ls_imag = o.h_ls_imag;
     return launch_ls_estimate(io, st);

@@ -326,8 +326,6 @@ __global__ __launch_bounds__(256) void k_tc_y(nrx_gen_desc d, const double2* __r
   }
 }
 
-size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
 struct TcWs {
   double2* xs;           // [B][U][Ls]  the transmitted samples
   double2* r;            // [B][A][Ls]  the noise-free received samples
@@ -336,29 +334,19 @@ struct TcWs {
   double2* yg;           // [B][A][F][14]  the demodulated antenna grids
 };
 
-int64_t tc_row_samples(const nrx_gen_tc& tc) {
-  int64_t n = 0;
-  for (int t = 0; t < kT; ++t) n += tc.cp_length[t] + tc.fft_size;
-  return n;
-}
-
-size_t tc_layout(const nrx_gen_desc& d, const nrx_gen_tc& tc, TcWs* w, char* base) {
-  const size_t B = d.batch, U = d.num_tx, A = d.num_rx_ant, F = d.num_subcarriers, Ls = (size_t)tc_row_samples(tc);
+size_t tc_layout(const nrx_gen_desc& d, const nrx_gen_tc& tc, TcWs* w, void* base) {
+  const size_t B = d.batch, U = d.num_tx, A = d.num_rx_ant, F = d.num_subcarriers;
+  const size_t Ls = (size_t)slot_samples(tc.cp_length, tc.fft_size, kT);
   const size_t nsin = B * U * A * d.num_taps * d.num_sinusoids;
-  size_t o = 0;
-  auto take = [&](size_t n) {
-    char* p = base ? base + o : nullptr;
-    o += al(n);
-    return p;
-  };
+  Carver c(base);
   TcWs v;
-  v.xs = (double2*)take(B * U * Ls * sizeof(double2));
-  v.r = (double2*)take(B * A * Ls * sizeof(double2));
-  v.g0 = (double2*)take(nsin * sizeof(double2));
-  v.fd = (double*)take(nsin * sizeof(double));
-  v.yg = (double2*)take(B * A * F * kT * sizeof(double2));
+  v.xs = c.take<double2>(B * U * Ls);
+  v.r = c.take<double2>(B * A * Ls);
+  v.g0 = c.take<double2>(nsin);
+  v.fd = c.take<double>(nsin);
+  v.yg = c.take<double2>(B * A * F * kT);
   if (w) *w = v;
-  return o;
+  return c.bytes();
 }
 
 TcGen tc_gen(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_tc& tc) {
@@ -374,18 +362,6 @@ TcGen tc_gen(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_tc& tc)
   }
   g.Ls = at, g.n0 = tc.cp_length[0];
   return g;
-}
-
-nrx_ofdm_io tc_ofdm(const nrx_gen_desc& d, const nrx_gen_tc& tc, int streams, void* grid, void* samples) {
-  nrx_ofdm_io io{};
-  io.batch = d.batch, io.num_streams = streams, io.grid_subcarriers = d.num_subcarriers, io.num_symbols = kT;
-  io.fft_size = tc.fft_size, io.first_bin = tc.first_bin;
-  for (int t = 0; t < kT; ++t) io.cp_length[t] = tc.cp_length[t];
-  io.precision = NRX_OFDM_F64, io.grid_layout = NRX_OFDM_GRID_PLANAR;
-  io.timing_advance = tc.timing_advance;
-  io.num_samples = tc_row_samples(tc);
-  io.grid = grid, io.samples = samples;
-  return io;
 }
 
 }  // namespace
@@ -413,7 +389,7 @@ size_t tc_workspace_bytes(const nrx_gen_desc& d, const nrx_gen_tc& tc) { return 
 hipError_t launch_tc_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_tc& tc, const double* tau,
                           const double* spdp, double* gt, void* ws, hipStream_t st) {
   TcWs w;
-  tc_layout(d, tc, &w, (char*)ws);
+  tc_layout(d, tc, &w, ws);
   const TcGen g = tc_gen(d, c, tc);
   const int64_t ngrp = (int64_t)d.batch * d.num_tx * d.num_rx_ant * d.num_taps, nsin = ngrp * d.num_sinusoids;
   k_tc_draws<<<(unsigned)((nsin + 255) / 256), 256, 0, st>>>(d, c, g, tau, spdp, w.g0, w.fd);
@@ -426,17 +402,19 @@ hipError_t launch_tc_rx(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_
                         const double* tau, const double* gt, void* ws, float* y, float* h, float* y_re, float* y_im,
                         hipStream_t st) {
   TcWs w;
-  tc_layout(d, tc, &w, (char*)ws);
+  tc_layout(d, tc, &w, ws);
   const TcGen g = tc_gen(d, c, tc);
   const int64_t B = d.batch, U = d.num_tx, A = d.num_rx_ant, F = d.num_subcarriers;
-  if (hipError_t e = launch_ofdm(tc_ofdm(d, tc, (int)U, const_cast<double*>(x), w.xs), /*modulate=*/true, st)) return e;
+  if (hipError_t e = launch_ofdm(stage_ofdm(d, tc, (int)U, const_cast<double*>(x), w.xs), /*modulate=*/true, st)) return e;
   TcArgs p{};
   p.B = (int)B, p.U = (int)U, p.A = (int)A, p.L = d.num_taps, p.NS = d.num_sinusoids;
   p.l_min = g.l_min, p.l_max = g.l_max, p.Ls = g.Ls, p.n0 = g.n0, p.fs = g.fs;
   p.tau = tau, p.g0 = w.g0, p.fd = w.fd, p.x = w.xs, p.r = w.r;
   p.mix = c.rx_mix;
   if (hipError_t e = launch_tc_args(p, st)) return e;
-  if (hipError_t e = launch_ofdm(tc_ofdm(d, tc, (int)A, w.yg, w.r), /*modulate=*/false, st)) return e;
+  nrx_ofdm_io demod = stage_ofdm(d, tc, (int)A, w.yg, w.r);
+  demod.timing_advance = tc.timing_advance;
+  if (hipError_t e = launch_ofdm(demod, /*modulate=*/false, st)) return e;
   k_tc_y<<<(unsigned)((B * F * kT * A + 255) / 256), 256, 0, st>>>(d, w.yg, y, y_re, y_im);
   if (h) {
     const int at = (int)(A * kT);

@@ -435,7 +435,7 @@ struct Plan {
   size_t bytes;
 };
 
-void make_plan(const nrx_desc& d, const nrx_train_io& io, char* base, Plan* pl) {
+void make_plan(const nrx_desc& d, const nrx_train_io& io, void* base, Plan* pl) {
   Plan& p = *pl;
   p.B = io.shape.batch, p.U = io.shape.num_tx, p.F = io.shape.num_subcarriers, p.FT = p.F * kT;
   p.A2 = 2 * d.num_rx_ant, p.P = p.B * p.U * p.FT, p.H = num_heads(&d), p.M = d.num_mcs;
@@ -472,17 +472,12 @@ void make_plan(const nrx_desc& d, const nrx_train_io& io, char* base, Plan* pl) 
   den(p.chest[1], kHID, p.A2);
   p.num_weights = o;
   // workspace
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = base ? base + off : nullptr;     // the size query has no base
-    off += align256(bytes);
-    return q;
-  };
-  auto act = [&](int c) { return (float*)take((size_t)p.P * c * sizeof(float)); };
+  Carver ws(base);
+  auto act = [&](int c) { return ws.take<float>((size_t)p.P * c); };
   auto sep_acts = [&](SepActs& a, int cin) {
     a.D1 = act(cin), a.X2 = act(kHID), a.D2 = act(kHID), a.X3 = act(kHID), a.D3 = act(kHID);
   };
-  p.ns = (float*)take(p.B * sizeof(float));
+  p.ns = ws.take<float>(p.B);
   p.z0 = act(p.C0);
   for (int m = 0; m < p.H; ++m) sep_acts(p.ainit[m], p.C0);
   for (int i = 0; i <= p.I; ++i) p.state[i] = act(kDS);
@@ -495,10 +490,10 @@ void make_plan(const nrx_desc& d, const nrx_train_io& io, char* base, Plan* pl) 
     p.ro[r].chid = act(kHID), p.ro[r].href = act(p.A2), p.ro[r].dh = act(p.A2);
   }
   p.GA = act(kHID), p.GB = act(kHID), p.G56 = act(kDS), p.out56 = act(kDS), p.G64 = act(kAGG), p.dS = act(kDS);
-  p.slab = (float*)take((size_t)p.S * (kHID + 1) * kHID * sizeof(float));
-  p.part_d = (double*)take((size_t)p.R * p.H * kLossBlocks * sizeof(double));
-  p.part_c = (double*)take((size_t)p.R * kLossBlocks * sizeof(double));
-  p.bytes = off;
+  p.slab = ws.take<float>((size_t)p.S * (kHID + 1) * kHID);
+  p.part_d = ws.take<double>((size_t)p.R * p.H * kLossBlocks);
+  p.part_c = ws.take<double>((size_t)p.R * kLossBlocks);
+  p.bytes = ws.bytes();
 }
 
 // ---------------------------------------------------------------- launch helpers
@@ -610,7 +605,7 @@ size_t train_workspace_bytes(const nrx_desc& d, const nrx_train_io& io) {
 
 hipError_t launch_train_grad(const nrx_desc& d, const nrx_train_io& io, void* ws, hipStream_t st) {
   Plan p;
-  make_plan(d, io, (char*)ws, &p);
+  make_plan(d, io, ws, &p);
   Run run{p, io, st};
   const int P = p.P;
   run.err = hipMemsetAsync(io.grad, 0, p.num_weights * sizeof(float), st);
