@@ -29,7 +29,7 @@ SOURCES = [os.path.join(CSRC, f) for f in KERNEL_TUS] + [
 HEADERS = [os.path.join(CSRC, "nrx_internal.h"), os.path.join(CSRC, "nrx_model.h"), os.path.join(CSRC, "nrx_rng.h"),
            os.path.join(HERE, "..", "include", "nrx.h")]
 KERNEL_INCS = [os.path.join(CSRC, "nrx_device.inc"), os.path.join(CSRC, "nrx_launch.inc"),
-               os.path.join(CSRC, "nrx_rr.inc"), os.path.join(CSRC, "nrx_col.inc")]
+               os.path.join(CSRC, "nrx_rr.inc"), os.path.join(CSRC, "nrx_col.inc"), os.path.join(CSRC, "nrx_geom.h")]
 # build.py itself: a change of the id rule (source_hash) relinks with a new nrx_build_id
 DEPS = SOURCES + HEADERS + KERNEL_INCS + [os.path.abspath(__file__)]
 ARCH = os.environ.get("NRX_OFFLOAD_ARCH", "gfx950")

@@ -21,13 +21,12 @@
 
 namespace nrx {
 hipError_t launch_forward_f16(const FwdArgs<_Float16, float, _Float16>& args, const ModelW<_Float16, float>& W,
-                              int num_it, hipStream_t st, Prof* prof, const FusedCtl& fc);
-bool fused_would_run(const FwdArgs<_Float16, float, _Float16>& args, int num_it, const FusedCtl& fc);
+                              const FwdPlan& pl, const FusedCtl& fc, hipStream_t st, Prof* prof);
+void device_counts(int* cus, int* xccs);
 size_t fused_sync_bytes();
 hipError_t fused_sync_status(void* sync, int* st, bool reset, hipEvent_t last);
-hipError_t launch_forward_f64(const FwdArgs<double, double, float>& args,
-                              const ModelW<double, double>& W, int num_it, hipStream_t st,
-                              Prof* prof);
+hipError_t run_tier_p64(const FwdArgs<double, double, float>& args, const ModelW<double, double>& W,
+                        const FwdPlan& pl, hipStream_t st, Prof* prof);
 hipError_t setup_kernels();
 int strip_width(int precision);
 
@@ -258,7 +257,8 @@ struct nrx_handle {
   hipEvent_t last_ev = nullptr;
   hipStream_t last_stream = nullptr;
   bool have_last = false;
-  FusedCtl fused_ctl() const { return FusedCtl{fused_sync, fused_enabled, spin_limit, dbg_err, update_rr}; }
+  FusedCtl fused_ctl() const { return FusedCtl{fused_sync, spin_limit, dbg_err}; }
+  Sched sched() const { return Sched{update_rr, fused_enabled}; }
 };
 
 // The forward workspace: the slot norms, four state / aggregate planes [B][U][F][14][56] of the storage type
@@ -291,8 +291,7 @@ static int check_shape(const nrx_shape* s) {
 }
 
 template <class WT, class BT, class S>
-static void fill_args(FwdArgs<WT, BT, S>& a, const nrx_handle* h, const nrx_io* io, void* ws, int init_cinp) {
-  const nrx_desc* d = &h->desc;
+static void fill_args(FwdArgs<WT, BT, S>& a, const nrx_desc* d, const nrx_io* io, void* ws, int init_cinp) {
   const nrx_shape* s = &io->shape;
   a.B = s->batch;
   a.llr_B = s->batch;
@@ -329,6 +328,24 @@ static void fill_args(FwdArgs<WT, BT, S>& a, const nrx_handle* h, const nrx_io* 
 static int forward_slots(nrx_handle* h, const nrx_io* io, int llr_B, void* workspace, hipStream_t st);
 static int chunk_slots(const nrx_shape* s, int precision);
 
+// The slot chunks [b0, b0 + n) a forward of s->batch slots runs as (chunk_slots): f(b0, n) each, until one fails.
+template <class F>
+static int each_chunk(const nrx_shape* s, int precision, F f) {
+  const int B = s->batch, bc = chunk_slots(s, precision);
+  for (int b0 = 0; b0 < B; b0 += bc)
+    if (int rc = f(b0, b0 + bc < B ? bc : B - b0)) return rc;
+  return NRX_OK;
+}
+
+// The plan of an f16 forward over n slots of io's shape in workspace ws (never null: pe16 gates the GZ paths); fills a.
+static FwdPlan plan_f16(FwdArgs<_Float16, float, _Float16>& a, const nrx_desc* d, const nrx_io* io, int n, void* ws,
+                        int init_cinp, const Sched& sc, int cus, int xccs) {
+  nrx_io c = *io;
+  c.shape.batch = n;
+  fill_args(a, d, &c, ws, init_cinp);
+  return plan_forward(a, io->num_it, sc, cus, xccs);
+}
+
 // The one-stream rule: NRX_ERR_BUSY when a forward that takes the one-launch path arrives on a stream
 // other than the previous one-launch forward's while that forward has not finished (the counters are
 // per handle).
@@ -340,22 +357,20 @@ static int busy(const nrx_handle* h, hipStream_t st) {
 
 // busy() for the whole of a forward entry point, called before ANY of its launches, so a refused
 // call has launched nothing (the y-layout / Aerial preprocessing used to run first).
+// Decided on the shapes the forward will run: each slot chunk may take the one-launch path although the
+// whole batch would not; one plan per distinct chunk size.
 static int fused_busy(nrx_handle* h, const nrx_io* io, void* ws, hipStream_t st) {
   if (io->precision != NRX_PREC_F16) return NRX_OK;
+  int cus, xccs, seen = 0;
+  device_counts(&cus, &xccs);
   bool takes = false;
-  // decided on the shapes the forward will run: a forward above the 1 GB workspace runs as slot
-  // chunks (nrx_forward), full ones of chunk_slots slots and a remainder, and each chunk may take
-  // the one-launch path although the whole batch would not
-  const int B = io->shape.batch, bc = chunk_slots(&io->shape, io->precision);
-  for (const int n : {bc < B ? bc : B, bc < B && B % bc ? B % bc : 0}) {
-    if (n <= 0) continue;
-    nrx_io c = *io;
-    c.shape.batch = n;
+  (void)each_chunk(&io->shape, io->precision, [&](int, int n) {
     FwdArgs<_Float16, float, _Float16> a{};
-    // ws: the workspace the forward will run in, never null (the size query leaves pe16 null, which gates the path)
-    fill_args(a, h, &c, ws, h->m16.init_cinp);
-    takes = takes || fused_would_run(a, io->num_it, h->fused_ctl());
-  }
+    takes = takes ||
+            (n != seen && plan_f16(a, &h->desc, io, n, ws, h->m16.init_cinp, h->sched(), cus, xccs).one_launch());
+    seen = n;
+    return 0;
+  });
   return takes ? busy(h, st) : NRX_OK;
 }
 
@@ -488,41 +503,36 @@ int nrx_forward(nrx_handle* h, const nrx_io* io, void* workspace, size_t workspa
   if (int rc = nrx_workspace_size(h, &io->shape, io->precision, &need)) return rc;
   if (!workspace || workspace_bytes < need) return too_small(need);
   hipStream_t st = (hipStream_t)stream;
-  const int bc = chunk_slots(&io->shape, io->precision);
-  if (bc < io->shape.batch) {
-    // slot chunks (chunk_slots): the same forward on [b0, b0 + n) with offset tensors; the LLR
-    // tensor keeps its head stride (llr_B)
-    const int B = io->shape.batch, U = io->shape.num_tx, F = io->shape.num_subcarriers, A2 = 2 * d->num_rx_ant;
-    const size_t re = (size_t)F * kT;
-    for (int b0 = 0; b0 < B; b0 += bc) {
-      nrx_io c = *io;
-      c.shape.batch = b0 + bc < B ? bc : B - b0;
-      c.y = io->y + (size_t)b0 * re * A2;
-      c.h_hat = io->h_hat ? io->h_hat + (size_t)b0 * U * re * A2 : nullptr;
-      c.active = io->active + (size_t)b0 * U;
-      c.mcs_mask = io->mcs_mask ? io->mcs_mask + (size_t)b0 * U * d->num_mcs : nullptr;
-      c.h_ref = io->h_ref ? io->h_ref + (size_t)b0 * U * re * A2 : nullptr;
-      c.llr = io->llr + (size_t)b0 * U * re * bits_max(d);
-      if (int rc = forward_slots(h, &c, B, workspace, st)) return rc;
-    }
-    return NRX_OK;
-  }
-  return forward_slots(h, io, io->shape.batch, workspace, st);
+  // slot chunks (chunk_slots): the same forward on [b0, b0 + n) with offset tensors; the LLR tensor keeps its
+  // head stride (llr_B)
+  const int U = io->shape.num_tx, A2 = 2 * d->num_rx_ant;
+  const size_t re = (size_t)io->shape.num_subcarriers * kT;
+  return each_chunk(&io->shape, io->precision, [&](int b0, int n) {
+    nrx_io c = *io;
+    c.shape.batch = n;
+    c.y = io->y + (size_t)b0 * re * A2;
+    c.h_hat = io->h_hat ? io->h_hat + (size_t)b0 * U * re * A2 : nullptr;
+    c.active = io->active + (size_t)b0 * U;
+    c.mcs_mask = io->mcs_mask ? io->mcs_mask + (size_t)b0 * U * d->num_mcs : nullptr;
+    c.h_ref = io->h_ref ? io->h_ref + (size_t)b0 * U * re * A2 : nullptr;
+    c.llr = io->llr + (size_t)b0 * U * re * bits_max(d);
+    return forward_slots(h, &c, io->shape.batch, workspace, st);
+  });
 }
 
-// One forward over io->shape.batch slots of an LLR tensor of llr_B slots (its head stride).
+// One forward over io->shape.batch slots of an LLR tensor of llr_B slots (its head stride), by one plan.
 static int forward_slots(nrx_handle* h, const nrx_io* io, int llr_B, void* workspace, hipStream_t st) {
   hipError_t e;
   if (io->precision == NRX_PREC_F16) {
+    int cus, xccs;
+    device_counts(&cus, &xccs);
     FwdArgs<_Float16, float, _Float16> a{};
-    fill_args(a, h, io, workspace, h->m16.init_cinp);
+    const FwdPlan pl = plan_f16(a, &h->desc, io, io->shape.batch, workspace, h->m16.init_cinp, h->sched(), cus, xccs);
     a.llr_B = llr_B;
-    const FusedCtl fc = h->fused_ctl();
-    const bool takes = fused_would_run(a, io->num_it, fc);
-    if (takes)
+    if (pl.one_launch())
       if (int rc = busy(h, st)) return rc;
-    e = launch_forward_f16(a, h->m16.W, io->num_it, st, h->prof, fc);
-    if (e == hipSuccess && takes) {
+    e = launch_forward_f16(a, h->m16.W, pl, h->fused_ctl(), st, h->prof);
+    if (e == hipSuccess && pl.one_launch()) {
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
       if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
         e = hipEventRecord(h->last_ev, st);
@@ -532,9 +542,9 @@ static int forward_slots(nrx_handle* h, const nrx_io* io, int llr_B, void* works
     }
   } else {
     FwdArgs<double, double, float> a{};
-    fill_args(a, h, io, workspace, h->m64.init_cinp);
+    fill_args(a, &h->desc, io, workspace, h->m64.init_cinp);
     a.llr_B = llr_B;
-    e = launch_forward_f64(a, h->m64.W, io->num_it, st, h->prof);
+    e = run_tier_p64(a, h->m64.W, plan_forward(a, io->num_it), st, h->prof);
   }
   return launched(e, "kernel launch");
 }
@@ -1442,6 +1452,50 @@ int nrx_update_schedule(nrx_handle* h, int32_t update_rr) {
   if (update_rr > kSchedMax) return fail(NRX_ERR_INVALID_ARG, "update_rr is a stage mask 0..127");
   if (update_rr >= 0) h->update_rr = update_rr;
   return NRX_OK;
+}
+
+// The launch plan of a forward, without a handle (tests only, like nrx_probe_buffer_oob: not in include/nrx.h): the
+// checks, the chunking and the plan_forward of nrx_forward, at cus / xccs (cus == 0: the current device's; else no
+// HIP call).  Into out[cap], 16 int32 per chunk (b0, n, -1, FwdPlan's 11 fields up to nq, one_launch, combine launches)
+// and per stage s (b0, n, s, StagePlan's 11 fields, 0, 0).  Returns the int32 count of the whole plan or an error code.
+int nrx_debug_forward_plan(const nrx_desc* desc, const nrx_shape* shape, int32_t precision, int32_t num_it,
+                           int32_t sched_mask, int32_t fused_mode, int32_t cus, int32_t xccs, int32_t* out,
+                           int32_t cap) {
+  if (int rc = check_desc(desc)) return rc;
+  if (int rc = check_shape(shape)) return rc;
+  if (precision != NRX_PREC_F16 && precision != NRX_PREC_F32X) return fail(NRX_ERR_INVALID_ARG, "unknown precision");
+  if (num_it < 1 || num_it > desc->num_it) return fail(NRX_ERR_INVALID_ARG, "Invalid number of iterations");
+  if (sched_mask < 0 || sched_mask > kSchedMax || fused_mode < 0 || fused_mode > 2 || cus < 0 || (!out && cap > 0))
+    return fail(NRX_ERR_INVALID_ARG, "bad schedule, device counts or output");
+  if (cus == 0) device_counts(&cus, &xccs);
+  const nrx_io io{*shape, num_it, precision};
+  void* ws = reinterpret_cast<void*>(uintptr_t(256));   // a dummy base: pe16 non-null, nothing is dereferenced
+  int n_out = 0;
+  auto put = [&](int b0, int n, int s, const void* plan, int x, int y) {
+    int rec[16] = {b0, n, s};
+    memcpy(rec + 3, plan, 11 * sizeof(int));   // the leading int fields of a FwdPlan / all of a StagePlan
+    rec[14] = x, rec[15] = y;
+    for (int k = 0; k < 16; ++k, ++n_out)
+      if (n_out < cap) out[n_out] = rec[k];
+  };
+  static_assert(offsetof(FwdPlan, st) == 11 * sizeof(int) && sizeof(StagePlan) == 11 * sizeof(int), "record layout");
+  (void)each_chunk(shape, precision, [&](int b0, int n) {
+    FwdPlan pl;
+    if (precision == NRX_PREC_F16) {
+      FwdArgs<_Float16, float, _Float16> a{};
+      pl = plan_f16(a, desc, &io, n, ws, init_padded_cin(desc, 32), Sched{sched_mask, fused_mode}, cus, xccs);
+    } else {
+      FwdArgs<double, double, float> a{};
+      nrx_io c = io;
+      c.shape.batch = n;
+      fill_args(a, desc, &c, ws, init_padded_cin(desc, 16));
+      pl = plan_forward(a, num_it);
+    }
+    put(b0, n, -1, &pl, pl.one_launch(), pl.combine_launches());
+    for (int s = 0; s < pl.num_init + pl.num_it; ++s) put(b0, n, s, &pl.st[s], 0, 0);
+    return 0;
+  });
+  return n_out;
 }
 
 int nrx_profile_read(nrx_handle* h, int32_t kernel, int64_t* launches, double* total_ms) {

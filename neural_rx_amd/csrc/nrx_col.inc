@@ -33,14 +33,7 @@
 #ifndef NRX_COL_PR3
 #define NRX_COL_PR3 2
 #endif
-constexpr int kColRO = 6;                  // own rows per wave
-constexpr int kColPos = 8 * kColRO;        // positions per item
-constexpr int kColFO = kColPos - 4;        // outputs per strip of a grid wider than kColPos
-constexpr int kColRed = kRrLds;            // 8 doubles: slot_norm's wave partials
-constexpr int kColLds = kColRed + 64;
-static_assert(kColLds <= 160 * 1024, "column LDS plan exceeds the CU's LDS");
-
-__host__ __device__ constexpr int col_strips(int F) { return F <= kColPos ? 1 : (F + kColFO - 1) / kColFO; }
+// (the item geometry kColRO .. kColLds and col_strips: nrx_geom.h)
 // subcarrier of position 0, and the positions whose conv3 outputs are valid (one strip: every
 // position, the grid edges are the SAME padding; several strips: a 2-row halo each side)
 __device__ __forceinline__ int col_fstart(int strip, int strips) { return strips == 1 ? 0 : strip * kColFO - 2; }
@@ -642,7 +635,6 @@ __global__ __launch_bounds__(512) void k_init_col_multi(BlockParams<P16> prm, in
 // the three launches: two launch gaps and two kernel prologues (kernel-argument loads) per
 // forward.  Every item stages its stage's weights (the bench shape gives each workgroup one item
 // per stage), so it is taken for shapes with at most one item per CU and stage.
-constexpr int kColMaxStages = 1 + kMaxIt;
 struct ColFwdParams {
   BlockParams<P16> st[kColMaxStages];   // 0: StateInit, 1 .. nst - 1: the updates (the last: readouts)
   FusedSync* sync;

@@ -41,6 +41,7 @@
 #include <utility>
 
 #include "nrx_internal.h"
+#include "nrx_geom.h"
 
 #ifndef NRX_ABLATE
 #define NRX_ABLATE 0   // diagnostic builds only: 1 skip conv math, 2 skip z loads, 4 skip weight
@@ -317,7 +318,6 @@ __device__ __forceinline__ void lds_store(char* base, int off, typename P::Real 
 // 16-byte chunk q = 4 kc + g in grid row 0 (kGzOob for zero chunks: pad symbols, q = 15, the
 // missing other user of U = 1), and a grid row adds f * kGzRow as the wave-uniform soffset
 // (kGzOob for rows outside the grid).  Out-of-range buffer loads return zeros.
-constexpr unsigned kGzOob = kGzRange;              // > any workspace this path is taken for
 constexpr unsigned kGzRow = kT * kDS * 2;          // bytes per grid row of a state plane
 struct GZ {
   __amdgpu_buffer_rsrc_t rsrc;
@@ -336,30 +336,9 @@ struct GZ {
 };
 
 // ------------------------------------------------ depthwise 3x3 + pointwise on MFMA
-// Strip image in LDS: slot (one subcarrier row) x 16 symbols x up to 128 channels, with a
-// fixed slot pitch so that every layer of a block can run in place in one buffer.
-template <class P>
-constexpr int slot_pitch() { return kTP * kHID * (int)sizeof(typename P::S); }
 template <class P, int NQ>
 __device__ __forceinline__ int xoff(int slot, int t, int q) {
   return slot * slot_pitch<P>() + (t * NQ + (q ^ swz<NQ>(t))) * 16;
-}
-
-// Per-layer weight image in LDS (P16): layout constants kWPw .. kHW2 in nrx_internal.h
-// (shared with the host, which packs the same images for the LDS-DMA of nrx_rr.inc).
-// The paired readout tail gives WB the rest of the 160 KB LDS (P16: 160 KB - 30 x 4 KB) and
-// stages the heads there, so that the strip image X is free for the next item's z DMA
-// during the readout epilogue.  W1^T images in full; W2^T images truncated to their real
-// rows (bits, 2A): the lanes of the padding rows read whatever follows, which only reaches
-// output channels that are never stored.  One LLR head only.
-constexpr int kWAlloc = 160 * 1024 - 30 * kTP * kHID * 2;
-static_assert(kWBytes <= kWAlloc, "layer weight image exceeds the LDS left by the strip image");
-// The truncated W2^T images put the LLR rows [0, bits_max) in the b2 slot of 16 outputs and
-// the ChEst rows [0, 2A) in a CHP-row slot: bits_max <= 16 and 2A <= CHP <= 32 are
-// required besides the byte budget (the padding rows the lanes read beyond the real ones
-// only reach output channels that are never stored; ADVICE r02).
-__host__ __device__ constexpr bool heads_fit_wb(int bits_max, int chp, int a2 = 0) {
-  return bits_max <= 16 && a2 <= chp && chp <= 32 && kHW2 + 256 * (bits_max + chp) <= kWAlloc;
 }
 
 template <class P, int CINP, int COUTP>
@@ -872,10 +851,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 //
 // State / aggregate buffers are compact: [B][U][F][14][56] (no padding in HBM).
 
-// TAIL_READOUT_WB: readout tail with the heads staged into WB, two items per workgroup
-enum Tail { TAIL_NONE = -1, TAIL_AGG = 0, TAIL_READOUT = 1, TAIL_READOUT_WB = 2 };
-constexpr bool readout_tail(int t) { return t == TAIL_READOUT || t == TAIL_READOUT_WB; }
-
+// (the tails, enum Tail: nrx_geom.h)
 template <class P>
 struct BlockParams {
   FwdArgs<typename P::WT, typename P::BT, typename P::S> a;
@@ -893,12 +869,6 @@ struct BlockParams {
   int gz;                                                // k_update: conv1 reads its z rows from memory
 };
 
-template <class P>
-constexpr int strip_slots() { return P::FO + 2 * kHalo; }
-template <class P>
-constexpr int strip_lds_bytes(bool heads_wb = false) {
-  return strip_slots<P>() * slot_pitch<P>() + (P::WLDS ? (heads_wb ? kWAlloc : kWBytes) : 0);
-}
 static_assert(strip_lds_bytes<P16>(true) == 160 * 1024, "P16 strip image + WB = LDS");
 static_assert(P16::FO <= 8 * P16::R && P16M::FO <= 8 * P16M::R && P16S::FO <= 8 * P16S::R,
               "the conv3 of a strip must run in one round");
@@ -1030,8 +1000,7 @@ __device__ __forceinline__ void dense_rows(const CFrag<P, NT> (&in)[NR], const W
   }
 }
 
-// Readout weight images staged into the (then free) strip buffer X (P16).
-constexpr int kHeadSlot = 24 * 1024;   // W1^T 16 KB | W2^T <= 8 KB ... per head, 256-aligned
+// Readout weight images staged into the (then free) strip buffer X (P16): kHeadSlot per head.
 __device__ __forceinline__ int head_w1(int h) { return h * (kHeadSlot + 1024); }
 __device__ __forceinline__ int head_w2(int h) { return head_w1(h) + 16 * 1024; }
 __device__ __forceinline__ int head_b1(int h) { return head_w1(h) + kHeadSlot; }
@@ -1706,9 +1675,6 @@ static __global__ __launch_bounds__(1024) void k_norm(const float* __restrict__ 
 #ifndef NRX_INIT_ORDER
 #define NRX_INIT_ORDER 1
 #endif
-
-// slot grids above this many float4s get the separate k_norm pass (nrx_rt: 1 344)
-constexpr int kNormFusedMaxQ = 8192;
 
 template <class P, int A2P, int CHP, int TAILM>
 __device__ __forceinline__ void init_user(const BlockParams<P>& prm, char* smem, int b, int u,
@@ -2443,22 +2409,6 @@ struct FusedSync {
   int pad[4];
   // int done[kFusedMaxStages][B] follows
 };
-constexpr int kFusedMaxStages = 12;  // StateInit (x M for Var-IO) + the updates (8 for nrx_large);
-                                     // FusedParams ~7.5 KB of kernel arguments (16 KB measured to
-                                     // pass, tools/ubench/kernarg.hip)
-// dynamic LDS of k_forward: the paired-readout layout minus room for the static __shared__
-// words (the slot-norm reduction of StateInit, the queue words); the readout heads must fit
-constexpr int kFusedLds = 160 * 1024 - 256;
-// dynamic LDS of k_forward per strip tier: the 24-row tier's paired-readout layout fills the
-// LDS, so it gives up 256 bytes of WB; the small-grid tiers (8 / 16-row strips) fit whole
-template <class P>
-constexpr int fused_lds() {
-  return strip_lds_bytes<P>(true) > kFusedLds ? kFusedLds : strip_lds_bytes<P>(true);
-}
-constexpr int kFusedMaxB = 65536;
-// logical stages: the StateInit stages, then per iteration (U > kInlineUsers) a combine stage
-// and the update stage; one dependency counter row each
-constexpr int kFusedMaxLS = 20;
 constexpr size_t kFusedSyncBytes = sizeof(FusedSync) + (size_t)kFusedMaxLS * kFusedMaxB * sizeof(int);
 
 template <class P>
@@ -2510,7 +2460,6 @@ __device__ __forceinline__ void fused_wait(const int* cnt, int need, FusedSync* 
 // order, then (sum - sp_u) * p), so the outputs equal the three-launch forward's.  Its rows
 // are its own strip's (no halo); the next update stage waits for all strips of the slot.  It
 // runs no conv2, so the next item's dependency poll is done at its end.
-constexpr int kFusedMaxUsers = 8;
 template <class P>
 __device__ __forceinline__ void combine_item(const BlockParams<P>& prm, int b, int strip, FusedNext<P>* fn) {
   using S = typename P::S;

@@ -139,15 +139,16 @@ struct FwdArgs {
 };
 
 // The one-launch forward's control block (nrx_api.cpp fills it from the handle): the
-// work-queue / counter buffer, whether the path may run (NRX_FUSED, read once at nrx_create),
-// the dependency-wait bound and debug error bits (nrx_debug_fused).
+// work-queue / counter buffer, the dependency-wait bound and debug error bits (nrx_debug_fused).
 struct FusedCtl {
   void* sync;
-  int enabled;   // 0 off, 1 where measured faster (the bench-type schedule), 2 every applicable shape
   int spin_limit;
   int dbg_err;
-  int update_rr;   // three-launch f16 forward: stage mask (nrx_update_schedule: 1 / 2 RR aggregation / readout,
-                   // 4 / 8 column aggregation / readout, 16 column StateInit)
+};
+// What the handle lets the planner choose from (plan_forward)
+struct Sched {
+  int mask;    // stage mask of the f16 forward (nrx_update_schedule; NRX_UPDATE_RR at nrx_create), bits below
+  int fused;   // one-launch forwards (nrx_fused_config; NRX_FUSED): 0 off, 1 where measured faster, 2 where applicable
 };
 // schedule-mask bits of the three-launch f16 forward (nrx_update_schedule)
 constexpr int kSchedRrAgg = 1, kSchedRrRo = 2, kSchedColAgg = 4, kSchedColRo = 8, kSchedColInit = 16;
@@ -173,6 +174,35 @@ struct Prof {
   virtual void end(int kid, void* stream) = 0;
   virtual ~Prof() {}
 };
+
+// ---- the launch plan of one forward: which kernel runs each stage, on what grid.  plan_forward
+// (nrx_dispatch.hip) alone decides it; the launchers (nrx_launch.inc, nrx_k_rr.hip, nrx_k_col.hip) execute it.
+enum FwdPath { PATH_P16S, PATH_P16M, PATH_P16, PATH_FWD_COL, PATH_KFWD0, PATH_KFWD1, PATH_KFWD2, PATH_P64 };
+enum StageKind { STAGE_STRIP, STAGE_RR, STAGE_COL };
+struct StagePlan {       // stage s: StateInit m = s < num_init, else update i = s - num_init
+  int kind;              // StageKind: the launcher
+  int kid;               // KernelId the profiler charges the stage to
+  int tail;              // the kernel variant's Tail ...
+  int chp;               // ... its A2P (StateInit: 8 / 16 / 32) or CHP (update: 16 / 32) ...
+  int one;               // ... the one-item column kernel (items <= grid), else the looping one
+  int pair;              // ... strip update: two items per workgroup
+  int items, strips;     // work items of the stage = B * U * strips
+  int grid, lds;         // workgroups and dynamic LDS bytes of its launch (one-launch paths: FwdPlan's)
+  int order_rev;         // BlockParams::order_rev: alternates with the launches
+};
+struct FwdPlan {
+  int path;              // FwdPath
+  int num_init, num_it;
+  // launch-wide: the k_norm pre-pass runs; conv1 of the updates reads z from memory (GZ); the updates form the
+  // leave-one-out combine themselves (U <= kInlineUsers), else k_combine launches / stages run
+  int norm_pre, gz, inline_combine;
+  int grid, lds, a2p, heads_x, nq;   // the one launch of k_fwd_col / k_forward (a2p: StateInit's; nq: queues)
+  StagePlan st[kMaxInit + kMaxIt];
+  bool one_launch() const { return path >= PATH_FWD_COL && path <= PATH_KFWD2; }
+  bool combine_launches() const { return !inline_combine && !one_launch(); }
+};
+FwdPlan plan_forward(const FwdArgs<_Float16, float, _Float16>& a, int num_it, const Sched& sc, int cus, int xccs);
+FwdPlan plan_forward(const FwdArgs<double, double, float>& a, int num_it);
 
 // Aerial front/back-end (nrx_aerial.hip)
 hipError_t launch_aerial_tables(const int32_t* ofdm_pos, const int32_t* sc_pos, int U, int nsym, int npil, int T,

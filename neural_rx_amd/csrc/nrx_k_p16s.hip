@@ -5,9 +5,8 @@
 
 namespace nrx {
 
-hipError_t run_tier_p16s(const FwdArgs<_Float16, float, _Float16>& a, const ModelW<_Float16, float>& W, int num_it,
-                       hipStream_t st, Prof* prof) {
-  return Launch<P16S>::run(a, W, num_it, st, prof);
+hipError_t run_tier_p16s(const Args16& a, const Model16& W, const FwdPlan& pl, hipStream_t st, Prof* prof) {
+  return Launch<P16S>::run(a, W, pl, st, prof);
 }
 
 hipError_t setup_tier_p16s() { return Launch<P16S>::setup(); }

@@ -5,9 +5,9 @@
 
 namespace nrx {
 
-hipError_t run_tier_p64(const FwdArgs<double, double, float>& a, const ModelW<double, double>& W, int num_it,
+hipError_t run_tier_p64(const FwdArgs<double, double, float>& a, const ModelW<double, double>& W, const FwdPlan& pl,
                         hipStream_t st, Prof* prof) {
-  return Launch<P64>::run(a, W, num_it, st, prof);
+  return Launch<P64>::run(a, W, pl, st, prof);
 }
 
 hipError_t setup_tier_p64() { return Launch<P64>::setup(); }

@@ -1,6 +1,6 @@
 // nrx_k_rr.hip -- the register-resident UpdateState launch (k_update_rr, nrx_rr.inc), one code
 // object of its own; called by the f16 24-row tier's launch loop (Launch<P16>::run) for the
-// update stages it applies to.
+// update stages the plan gives it (plan_forward).
 #include "nrx_device.inc"
 #include "nrx_launch.inc"
 
@@ -8,22 +8,8 @@ namespace nrx {
 
 #include "nrx_rr.inc"
 
-bool update_rr_applicable(const FwdArgs<_Float16, float, _Float16>& a, bool gz, bool inline_combine, bool last) {
-  // conv1 reads [a | s | pe] from memory: a = the other user's act*sp plane (U = 2, inline
-  // combine), none (U = 1) or the a_u plane the combine pass wrote (U > 2); see gz_make
-  (void)inline_combine;
-  const int chp = 2 * a.A <= 16 ? 16 : 32;
-  if (!gz || 2 * a.A > 32) return false;
-  return !last || (a.H == 1 && rr_heads_fit(a.bits_max, chp, 2 * a.A));
-}
-
-hipError_t launch_update_rr(const BlockParams<P16>& bp0, bool last, hipStream_t st) {
-  BlockParams<P16> bp = bp0;
-  bp.strips = (bp.a.F + kRrFO - 1) / kRrFO;
-  bp.pair = 0;
-  const int items = bp.a.B * bp.a.U * bp.strips;
-  const int grid = items < cu_count() ? items : cu_count();
-  const bool ch32 = 2 * bp.a.A > 16;
+hipError_t launch_update_rr(const BlockParams<P16>& bp, const StagePlan& sp, hipStream_t st) {
+  const int items = sp.items, grid = sp.grid;
 #ifdef NRX_STAMPS
   {
     // NRX_STAMP_RR = i: stamp the i-th RR launch of the process (0-based)
@@ -33,12 +19,12 @@ hipError_t launch_update_rr(const BlockParams<P16>& bp0, bool last, hipStream_t 
     (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_nrx_stamp_on), &on, sizeof(int), 0, hipMemcpyHostToDevice, st);
   }
 #endif
-  if (last) {
-    if (ch32) k_update_rr<32, TAIL_READOUT_WB><<<grid, 512, kRrLds, st>>>(bp, items);
-    else k_update_rr<16, TAIL_READOUT_WB><<<grid, 512, kRrLds, st>>>(bp, items);
+  if (sp.tail == TAIL_READOUT_WB) {
+    if (sp.chp == 32) k_update_rr<32, TAIL_READOUT_WB><<<grid, 512, sp.lds, st>>>(bp, items);
+    else k_update_rr<16, TAIL_READOUT_WB><<<grid, 512, sp.lds, st>>>(bp, items);
   } else {
-    if (ch32) k_update_rr<32, TAIL_AGG><<<grid, 512, kRrLds, st>>>(bp, items);
-    else k_update_rr<16, TAIL_AGG><<<grid, 512, kRrLds, st>>>(bp, items);
+    if (sp.chp == 32) k_update_rr<32, TAIL_AGG><<<grid, 512, sp.lds, st>>>(bp, items);
+    else k_update_rr<16, TAIL_AGG><<<grid, 512, sp.lds, st>>>(bp, items);
   }
   return hipGetLastError();
 }

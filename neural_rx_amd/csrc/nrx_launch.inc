@@ -4,63 +4,38 @@
 #pragma once
 namespace nrx {
 
-// per-tier entry points (one translation unit each)
-hipError_t run_tier_p16(const FwdArgs<_Float16, float, _Float16>& a, const ModelW<_Float16, float>& W, int num_it,
-                        hipStream_t st, Prof* prof, int update_rr);
-hipError_t run_tier_p16m(const FwdArgs<_Float16, float, _Float16>& a, const ModelW<_Float16, float>& W, int num_it,
-                         hipStream_t st, Prof* prof);
-hipError_t run_tier_p16s(const FwdArgs<_Float16, float, _Float16>& a, const ModelW<_Float16, float>& W, int num_it,
-                         hipStream_t st, Prof* prof);
-hipError_t run_tier_p64(const FwdArgs<double, double, float>& a, const ModelW<double, double>& W, int num_it,
+// per-tier entry points (one translation unit each); every launcher executes the FwdPlan it is handed
+// (plan_forward, nrx_dispatch.hip) and decides nothing
+using Args16 = FwdArgs<_Float16, float, _Float16>;
+using Model16 = ModelW<_Float16, float>;
+hipError_t run_tier_p16(const Args16& a, const Model16& W, const FwdPlan& pl, hipStream_t st, Prof* prof);
+hipError_t run_tier_p16m(const Args16& a, const Model16& W, const FwdPlan& pl, hipStream_t st, Prof* prof);
+hipError_t run_tier_p16s(const Args16& a, const Model16& W, const FwdPlan& pl, hipStream_t st, Prof* prof);
+hipError_t run_tier_p64(const FwdArgs<double, double, float>& a, const ModelW<double, double>& W, const FwdPlan& pl,
                         hipStream_t st, Prof* prof);
-hipError_t setup_tier_p16();
-hipError_t setup_tier_p16m();
-hipError_t setup_tier_p16s();
-hipError_t setup_tier_p64();
+hipError_t setup_tier_p16(), setup_tier_p16m(), setup_tier_p16s(), setup_tier_p64();
 // k_forward by MODE (0: bench-type, 1: general GZ, 2: staged z images); a2p = 8 / 16 / 32
 hipError_t launch_kforward_m0(int a2p, const FusedParams<P16>& fp, int grid, hipStream_t st);
 hipError_t launch_kforward_m1(int a2p, const FusedParams<P16>& fp, int grid, hipStream_t st);
 hipError_t launch_kforward_m2(int a2p, const FusedParams<P16>& fp, int grid, hipStream_t st);
+hipError_t setup_kforward_m0(), setup_kforward_m1(), setup_kforward_m2();
 // the register-resident update stage (nrx_k_rr.hip, DESIGN.md section A.13)
-bool update_rr_applicable(const FwdArgs<_Float16, float, _Float16>& a, bool gz, bool inline_combine, bool last);
-hipError_t launch_update_rr(const BlockParams<P16>& bp, bool last, hipStream_t st);
+hipError_t launch_update_rr(const BlockParams<P16>& bp, const StagePlan& sp, hipStream_t st);
 hipError_t setup_update_rr();
 // the whole-column launches (nrx_k_col.hip, DESIGN.md section 4)
-bool col_init_applicable(const FwdArgs<_Float16, float, _Float16>& a);
-bool update_col_applicable(const FwdArgs<_Float16, float, _Float16>& a, bool gz, bool last, int sched);
-hipError_t launch_init_col(const BlockParams<P16>& bp, hipStream_t st);
-hipError_t launch_update_col(const BlockParams<P16>& bp, bool last, hipStream_t st);
+hipError_t launch_init_col(const BlockParams<P16>& bp, const StagePlan& sp, hipStream_t st);
+hipError_t launch_update_col(const BlockParams<P16>& bp, const StagePlan& sp, hipStream_t st);
+hipError_t launch_fwd_col(const Args16& args, const Model16& W, const FwdPlan& pl, const FusedCtl& fc, hipStream_t st,
+                          Prof* prof);
 hipError_t setup_col();
-bool fwd_col_applicable(const FwdArgs<_Float16, float, _Float16>& a, int num_it, const FusedCtl& fc);
-hipError_t launch_fwd_col(const FwdArgs<_Float16, float, _Float16>& args, const ModelW<_Float16, float>& W, int num_it,
-                          hipStream_t st, Prof* prof, const FusedCtl& fc);
-hipError_t setup_kforward_m0();
-hipError_t setup_kforward_m1();
-hipError_t setup_kforward_m2();
-
-
-// CUs of the current device for the pairing / strip-tier heuristics, queried once per
-// device on first use (ADVICE r02: a single cached value was wrong for other devices)
-constexpr int kMaxDevices = 64;
-static int g_cu_count[kMaxDevices];
-static int cu_count() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 256;
-  if (g_cu_count[dev] <= 0) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
-    g_cu_count[dev] = cus;
-  }
-  return g_cu_count[dev];
-}
 
 // ---- the stage plan every forward launcher shares (Launch<P>::run, run_fused, launch_fwd_col)
 // A forward is a list of stages: StateInit m = 0 .. num_init - 1 into s_out (m > 0 accumulating), then
 // num_it updates on the ping-ponged state / aggregate planes.  The tail of a stage runs the NEXT
 // iteration's aggregation MLP (the last StateInit: iteration 0's) or, in the last update, the readout.
 // plan_stage fills what stage s's kernels read of it, in place: a, w, m, tail, agg and the heads.
-// ro_tail (TAIL_READOUT or TAIL_READOUT_WB) is the caller's choice, and so are the launch-wide fields
-// strips, gz, inline_combine, norm_pre, pair and order_rev.  What no kernel of the stage reads is
+// ro_tail (TAIL_READOUT or TAIL_READOUT_WB) is the caller's choice; the launch-wide fields strips, gz,
+// inline_combine, norm_pre, pair and order_rev come from the FwdPlan.  What no kernel of the stage reads is
 // zero: agg of the readout stage, m of an update.
 template <class P>
 static void plan_stage(BlockParams<P>& bp, const FwdArgs<typename P::WT, typename P::BT, typename P::S>& args,
@@ -86,15 +61,13 @@ static void plan_stage(BlockParams<P>& bp, const FwdArgs<typename P::WT, typenam
 }
 
 // The k_norm pre-pass: slots too long for the StateInit items to norm themselves (kNormFusedMaxQ) get
-// their norm from a launch of its own.  Returns BlockParams::norm_pre.
+// their norm from a launch of its own, where the plan says so (FwdPlan::norm_pre = BlockParams::norm_pre).
 template <class A>
-static bool norm_prepass(const A& args, hipStream_t st, Prof* prof) {
-  const int nq = args.F * kT * 2 * args.A / 4;
-  if (nq <= kNormFusedMaxQ) return false;
+static void norm_prepass(const A& args, const FwdPlan& pl, hipStream_t st, Prof* prof) {
+  if (!pl.norm_pre) return;
   if (prof) prof->begin(K_NORM, st);
-  k_norm<<<args.B, 1024, 0, st>>>(args.y, nq, args.norm);
+  k_norm<<<args.B, 1024, 0, st>>>(args.y, args.F * kT * 2 * args.A / 4, args.norm);
   if (prof) prof->end(K_NORM, st);
-  return true;
 }
 
 #ifdef NRX_STAMPS
@@ -143,230 +116,114 @@ struct Launch {
     else k_init<P, A2P, TAIL_NONE><<<grid, 512, L, st>>>(bp);
   }
 
-  static hipError_t run(const A& args, const MW& W, int num_it, hipStream_t st, Prof* prof, int update_rr = 0) {
-    const int strips = (args.F + P::FO - 1) / P::FO;
-    constexpr int L = strip_lds_bytes<P>();
-    const bool ch32 = 2 * args.A > 16;
+  // one stage's launch: the launcher kind and the kernel variant the plan names
+  static hipError_t launch_stage(const BlockParams<P>& bp, const StagePlan& sp, bool init, hipStream_t st) {
+    const dim3 grid(sp.grid);
+    const bool ch32 = sp.chp == 32;
+    if constexpr (std::is_same<P, P16>::value) {   // the RR and column kernels exist for the 24-row tier only
+      if (sp.kind == STAGE_COL) return init ? launch_init_col(bp, sp, st) : launch_update_col(bp, sp, st);
+      if (sp.kind == STAGE_RR) return launch_update_rr(bp, sp, st);
+    }
+    if (init) {
+      if (sp.chp == 8) launch_init<8>(grid, sp.lds, st, bp, sp.tail == TAIL_AGG);
+      else if (sp.chp == 16) launch_init<16>(grid, sp.lds, st, bp, sp.tail == TAIL_AGG);
+      else launch_init<32>(grid, sp.lds, st, bp, sp.tail == TAIL_AGG);
+    } else if (sp.tail == TAIL_READOUT_WB) {   // paired readout items, the heads staged into WB
+      if constexpr (P::WLDS) {
+        if (ch32) k_update<P, 32, TAIL_READOUT_WB><<<grid, 512, sp.lds, st>>>(bp);
+        else k_update<P, 16, TAIL_READOUT_WB><<<grid, 512, sp.lds, st>>>(bp);
+      }
+    } else if (sp.tail == TAIL_READOUT) {
+      if (ch32) k_update<P, 32, TAIL_READOUT><<<grid, 512, sp.lds, st>>>(bp);
+      else k_update<P, 16, TAIL_READOUT><<<grid, 512, sp.lds, st>>>(bp);
+    } else {
+      if (ch32) k_update<P, 32, TAIL_AGG><<<grid, 512, sp.lds, st>>>(bp);
+      else k_update<P, 16, TAIL_AGG><<<grid, 512, sp.lds, st>>>(bp);
+    }
+    return hipSuccess;
+  }
+
+  static hipError_t run(const A& args, const MW& W, const FwdPlan& pl, hipStream_t st, Prof* prof) {
     auto B_ = [&](int k) { if (prof) prof->begin(k, st); };
     auto E_ = [&](int k) { if (prof) prof->end(k, st); };
     BlockParams<P> bp{};
-    bp.inline_combine = args.U <= kInlineUsers;
-    if constexpr (std::is_same<P, P16>::value)   // 24-row strips, the workspace within GZ's offsets
-      bp.gz = NRX_UPDATE_GZ != 0 && args.ws_bytes < kGzOob && args.pe16 != nullptr;
-    bp.strips = strips;
-    bp.norm_pre = norm_prepass(args, st, prof);
-    int launch_no = 0;
+    bp.inline_combine = pl.inline_combine;
+    bp.gz = pl.gz;
+    norm_prepass(args, pl, st, prof);
+    bp.norm_pre = pl.norm_pre;
     // U > kInlineUsers: the leave-one-out combine runs as its own launch on the sp rows
     auto combine = [&](typename P::S* sp) {
-      if (bp.inline_combine) return;
+      if (!pl.combine_launches()) return;
       dim3 g((args.F * kT * (kDS / P::EPC) + 255) / 256, args.B);
       B_(K_COMBINE);
       k_combine<P><<<g, 256, 0, st>>>(sp, args.active, args.U, args.F);
       E_(K_COMBINE);
     };
-    const dim3 grid(strips * args.U * args.B);
-    // StateInit, one launch per m (Var-IO), by the whole-column kernel (2A = 8: weights staged once per
-    // workgroup) where the schedule gives it the stage, else by the strip kernel
-    bool col_init = false;
-    if constexpr (std::is_same<P, P16>::value)
-      col_init = (update_rr & kSchedColInit) && col_init_applicable(args);
-    B_(col_init ? K_INIT_COL : K_INIT);
-    for (int m = 0; m < args.num_init; ++m) {
-      plan_stage(bp, args, W, num_it, m, TAIL_READOUT);
-      bp.order_rev = launch_no++ & 1;
-      if (col_init) {
-        if constexpr (std::is_same<P, P16>::value) {
-          const hipError_t e = launch_init_col(bp, st);
-          if (e != hipSuccess) return e;
-        }
-        continue;
-      }
-      stamp_select(-1 - m, st);
-      const bool tl = bp.tail == TAIL_AGG;
-      const int a2p = init_a2p(args.A);
-      if (a2p == 8) launch_init<8>(grid, L, st, bp, tl);
-      else if (a2p == 16) launch_init<16>(grid, L, st, bp, tl);
-      else launch_init<32>(grid, L, st, bp, tl);
+    // (bp.tail keeps TAIL_READOUT whichever readout variant runs the last stage)
+    auto stage = [&](int s) {
+      const StagePlan& sp = pl.st[s];
+      plan_stage(bp, args, W, pl.num_it, s, TAIL_READOUT);
+      bp.strips = sp.strips;
+      bp.pair = sp.pair;
+      bp.order_rev = sp.order_rev;
+      return launch_stage(bp, sp, s < pl.num_init, st);
+    };
+    // StateInit, one launch per m (Var-IO), charged to the profiler as one stage
+    B_(pl.st[0].kid);
+    for (int m = 0; m < pl.num_init; ++m) {
+      if (pl.st[m].kind == STAGE_STRIP) stamp_select(-1 - m, st);
+      if (const hipError_t e = stage(m); e != hipSuccess) return e;
     }
-    E_(col_init ? K_INIT_COL : K_INIT);
+    E_(pl.st[0].kid);
     combine(bp.a.a_out);
-    for (int i = 0; i < num_it; ++i) {
-      const bool last = i == num_it - 1;
-      plan_stage(bp, args, W, num_it, args.num_init + i, TAIL_READOUT);
-      bp.order_rev = launch_no++ & 1;
-      bool rr = false, col = false;
-      if constexpr (std::is_same<P, P16>::value) {
-        col = (update_rr & (last ? kSchedColRo : kSchedColAgg)) && update_col_applicable(args, bp.gz != 0, last, update_rr);
-        rr = !col && (update_rr & (last ? kSchedRrRo : kSchedRrAgg)) &&
-             update_rr_applicable(args, bp.gz != 0, bp.inline_combine != 0, last);
-      }
-      const int kid = col ? K_UPDATE_COL : rr ? K_UPDATE_RR : K_UPDATE;
-      B_(kid);
+    for (int i = 0; i < pl.num_it; ++i) {
+      const int s = pl.num_init + i;
+      B_(pl.st[s].kid);
       stamp_select(i, st);
-      if (col) {
-        // whole-column update stage: 48-position items, weights staged once per workgroup
-        if constexpr (std::is_same<P, P16>::value) {
-          const hipError_t e = launch_update_col(bp, last, st);
-          if (e != hipSuccess) return e;
-        }
-      } else if (rr) {
-        // register-resident update stage: 16-row strips, weights staged once per workgroup
-        if constexpr (std::is_same<P, P16>::value) {
-          const hipError_t e = launch_update_rr(bp, last, st);
-          if (e != hipSuccess) return e;
-        }
-      } else if (last) {
-        // paired readout items (heads staged into WB) under the same conditions as the
-        // aggregation pairing below, for one LLR head that fits WB
-        bool pair_ro = false;
-        if constexpr (P::WLDS) {
-          const int items = (int)grid.x;
-          pair_ro = NRX_PAIR != 0 && NRX_ZDMA != 0 && NRX_PAIR_RO != 0 && args.U <= 2 && bp.inline_combine &&
-                    items % 16 == 0 && items >= 2 * cu_count() && args.H == 1 &&
-                    heads_fit_wb(args.bits_max, ch32 ? 32 : 16, 2 * args.A);
-          if (pair_ro) {
-            constexpr int L_wb = strip_lds_bytes<P>(true);
-            bp.pair = 1;
-            const dim3 g2(items / 2);
-            if (ch32) k_update<P, 32, TAIL_READOUT_WB><<<g2, 512, L_wb, st>>>(bp);
-            else k_update<P, 16, TAIL_READOUT_WB><<<g2, 512, L_wb, st>>>(bp);
-            bp.pair = 0;
-          }
-        }
-        if (!pair_ro) {
-          if (ch32) k_update<P, 32, TAIL_READOUT><<<grid, 512, L, st>>>(bp);
-          else k_update<P, 16, TAIL_READOUT><<<grid, 512, L, st>>>(bp);
-        }
-      } else {
-        // two items per workgroup when there are at least two per CU (CU count of the
-        // device, one workgroup per CU by LDS) and the halves keep the XCD grouping of
-        // work_item (items % 16 == 0)
-        const int items = (int)grid.x;
-        bp.pair = P::WLDS && NRX_PAIR != 0 && NRX_ZDMA != 0 && args.U <= 2 && bp.inline_combine &&
-                  items % 16 == 0 && items >= 2 * cu_count();
-        const dim3 g2(bp.pair ? items / 2 : items);
-        if (ch32) k_update<P, 32, TAIL_AGG><<<g2, 512, L, st>>>(bp);
-        else k_update<P, 16, TAIL_AGG><<<g2, 512, L, st>>>(bp);
-        bp.pair = 0;
-      }
-      E_(kid);
-      if (!last) combine(bp.a.a_out);
+      if (const hipError_t e = stage(s); e != hipSuccess) return e;
+      E_(pl.st[s].kid);
+      if (i < pl.num_it - 1) combine(bp.a.a_out);
     }
     return hipGetLastError();
   }
 };
 
-#ifndef NRX_SMALL_STRIPS
-#define NRX_SMALL_STRIPS 1
-#endif
-// Small grids: the forward is latency-bound and a workgroup's time scales with its rows, so
-// the narrowest strips whose items all get a CU of their own are taken (24-row strips
-// otherwise).  The readout heads must fit the strip image (X layout: H LLR heads + ChEst,
-// 25 KB each).
+// k_forward (PATH_KFWD0 .. 2): U <= 8 (with a workspace under 1 GB conv1 reads z from memory, GZ;
+// otherwise the z image is staged in LDS), 1..M StateInit stages (Var-IO), up to three LLR heads, one of them in
+// the paired-readout WB layout (TAIL_READOUT_WB) or all in the strip image (heads_x).  U = 3..8: a combine stage
+// (k_combine's f32 pass, one item per (slot, strip)) before each update, whose conv1 then reads the a_u plane.
 template <class P>
-static bool small_strips_fit(const FwdArgs<_Float16, float, _Float16>& a) {
-  const long items = (long)a.B * a.U * ((a.F + P::FO - 1) / P::FO);
-  return items <= cu_count() && (a.H + 1) * (kHeadSlot + 1024) <= strip_slots<P>() * slot_pitch<P>();
-}
-// XCDs (XCCs) of the current device, queried once per device: k_forward keeps one work
-// queue per XCD and needs every XCD to hold the same number of CUs (ADVICE r03: 32 per XCD
-// was assumed)
-static int g_xcc_count[kMaxDevices];
-static int xcc_count() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 0;
-  if (g_xcc_count[dev] <= 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeNumberOfXccs, dev) != hipSuccess || n <= 0) n = -1;
-    g_xcc_count[dev] = n;
-  }
-  return g_xcc_count[dev];
-}
-
-// k_forward covers: U <= 8 (with a workspace under 1 GB conv1 reads z from memory, GZ;
-// otherwise the z image is staged in LDS), 1..M StateInit stages (Var-IO), up to three LLR heads,
-// 2A <= 32, num_init + num_it <= kFusedMaxStages; 24-row strips with at least two items per
-// CU (the small-grid tiers keep the three launches: through k_forward they were slower for
-// batch-1 latency, profiles/r03/ab_fused_small_latency.txt); a device whose XCDs hold equal CU
-// counts (1..8 XCDs, the queue is picked by the hardware XCC id).  U = 3..8: a combine stage
-// (k_combine's f32 pass, one item per (slot, strip)) before each update, whose conv1 then
-// reads the combined a_u plane.
-// one LLR head whose readout fits the paired-readout WB layout (TAIL_READOUT_WB)
-template <class P>
-static bool heads_in_wb(const FwdArgs<_Float16, float, _Float16>& a) {
-  const int chp = 2 * a.A <= 16 ? 16 : 32;
-  return a.H == 1 && heads_fit_wb(a.bits_max, chp, 2 * a.A) &&
-         strip_slots<P>() * slot_pitch<P>() + kHW2 + 256 * (a.bits_max + chp) <= fused_lds<P>();
-}
-
-template <class P>
-static bool fused_gz(const FwdArgs<_Float16, float, _Float16>& a) {
-  return a.ws_bytes < kGzOob && a.pe16;
-}
-template <class P>
-static int fused_mode(const FwdArgs<_Float16, float, _Float16>& a) {
-  // U > kInlineUsers: combine stages, which the general kernels run
-  return !fused_gz<P>(a) ? 2 : (a.num_init > 1 || !heads_in_wb<P>(a) || a.U > kInlineUsers ? 1 : 0);
-}
-
-template <class P>
-static bool fused_applicable(const FwdArgs<_Float16, float, _Float16>& a, int num_it, const FusedCtl& fc) {
-  if (!fc.sync || !fc.enabled) return false;
-  const int cus = cu_count(), nx = xcc_count();
-  if (nx < 1 || nx > 8 || cus % nx != 0) return false;
-  const long items = (long)a.B * a.U * ((a.F + P::FO - 1) / P::FO);
-  // readout heads: one LLR head in WB (TAIL_READOUT_WB), or up to three + ChEst in the strip
-  // image (TAIL_READOUT, X layout)
-  const bool heads = heads_in_wb<P>(a) || (a.H <= 3 && (a.H + 1) * (kHeadSlot + 1024) <= strip_slots<P>() * slot_pitch<P>());
-  const int nls = a.num_init + num_it * (a.U > kInlineUsers ? 2 : 1);
-  // the default (enabled == 1) takes the GZ schedules (MODE 0, 1) with at least four stages
-  // (cfg4, cfg4'): the staged-z kernel (cfg3, cfg5) and the three-stage bench forward (cfg2)
-  // measured slower than the three launches on most boxes (DESIGN.md section A.12,
-  // profiles/r04/ab_cfg2_fused_vs_three.txt)
-  if (fc.enabled == 1 && (fused_mode<P>(a) == 2 || a.num_init + num_it < 4 || a.U > 2)) return false;
-  // ... and not where the three column launches apply: they measured faster than k_forward at
-  // every shape both run (cfg2 / cfg4 / cfg4', profiles/r06/configs)
-  if (fc.enabled == 1 && (fc.update_rr & kSchedColAgg) && fused_gz<P>(a) &&
-      update_col_applicable(a, true, false, fc.update_rr))
-    return false;
-  return items >= 2L * cus && a.U <= kFusedMaxUsers && a.num_init + num_it <= kFusedMaxStages &&
-         nls <= kFusedMaxLS && 2 * a.A <= 32 && a.B <= kFusedMaxB && a.bits_max <= 16 && heads;
-}
-
-template <class P>
-static hipError_t run_fused(const FwdArgs<_Float16, float, _Float16>& args, const ModelW<_Float16, float>& W,
-                            int num_it, hipStream_t st, Prof* prof, const FusedCtl& fc) {
+static hipError_t run_fused(const Args16& args, const Model16& W, const FwdPlan& pl, const FusedCtl& fc, hipStream_t st,
+                            Prof* prof) {
   FusedParams<P> fp{};
   fp.sync = reinterpret_cast<FusedSync*>(fc.sync);
-  fp.ninit = args.num_init;
-  fp.nst = args.num_init + num_it;
-  fp.heads_x = !heads_in_wb<P>(args);
-  fp.gz = fused_gz<P>(args);
-  const bool comb = args.U > kInlineUsers;
+  fp.ninit = pl.num_init;
+  fp.nst = pl.num_init + pl.num_it;
+  fp.heads_x = pl.heads_x;
+  fp.gz = pl.gz;
   fp.nls = 0;
   for (int s = 0; s < fp.ninit; ++s) {
     fp.kind[fp.nls] = 0;
     fp.pidx[fp.nls++] = s;
   }
-  for (int i = 0; i < num_it; ++i) {
-    if (comb) {
+  for (int i = 0; i < pl.num_it; ++i) {
+    if (!pl.inline_combine) {
       fp.kind[fp.nls] = 2;
       fp.pidx[fp.nls++] = fp.ninit + i;
     }
     fp.kind[fp.nls] = 1;
     fp.pidx[fp.nls++] = fp.ninit + i;
   }
-  const int cus = cu_count();
-  fp.nq = xcc_count();
+  fp.nq = pl.nq;
   fp.spin_limit = fc.spin_limit;
   fp.dbg_err = fc.dbg_err;
-  const bool norm_pre = norm_prepass(args, st, prof);
+  norm_prepass(args, pl, st, prof);
   for (int s = 0; s < fp.nst; ++s) {
     BlockParams<P>& bp = fp.st[s];   // in place: FusedParams is several KB (pair, order_rev, gz stay 0)
-    plan_stage(bp, args, W, num_it, s, fp.heads_x ? TAIL_READOUT : TAIL_READOUT_WB);
-    bp.inline_combine = comb ? 0 : 1;   // U > 2: the combine stages write a_u in place
-    bp.norm_pre = norm_pre;
-    bp.strips = (args.F + P::FO - 1) / P::FO;
+    plan_stage(bp, args, W, pl.num_it, s, pl.heads_x ? TAIL_READOUT : TAIL_READOUT_WB);
+    bp.inline_combine = pl.inline_combine;   // U > 2: the combine stages write a_u in place
+    bp.norm_pre = pl.norm_pre;
+    bp.strips = pl.st[s].strips;
   }
 #ifdef NRX_STAMPS
   {
@@ -376,12 +233,9 @@ static hipError_t run_fused(const FwdArgs<_Float16, float, _Float16>& args, cons
   }
 #endif
   if (prof) prof->begin(K_FUSED, st);
-  const int a2p = init_a2p(args.A);
-  const int mode0 = fused_mode<P>(args);
-  const int mode = a2p == 32 && mode0 == 0 ? 1 : mode0;   // 2A = 32 has the general kernels only
-  hipError_t e = mode == 0 ? launch_kforward_m0(a2p, fp, cus, st)
-                 : mode == 1 ? launch_kforward_m1(a2p, fp, cus, st)
-                             : launch_kforward_m2(a2p, fp, cus, st);
+  hipError_t e = pl.path == PATH_KFWD0   ? launch_kforward_m0(pl.a2p, fp, pl.grid, st)
+                 : pl.path == PATH_KFWD1 ? launch_kforward_m1(pl.a2p, fp, pl.grid, st)
+                                         : launch_kforward_m2(pl.a2p, fp, pl.grid, st);
   if (e != hipSuccess) return e;
   if (prof) prof->end(K_FUSED, st);
   return hipGetLastError();

@@ -149,7 +149,7 @@ int build(const nrx_desc* d, const float* const* w, int kc, DeviceModel<WT, BT>*
     const int a2 = 2 * d->num_rx_ant;
     ipos[c] = c < a2 ? c : (c < a2 + 2 ? 2 * a2p + (c - a2) : a2p + (c - a2 - 2));
   }
-  const int icinp = pow2_at_least(round_up(2 * a2p + 2, kc), 32);
+  const int icinp = init_padded_cin(d, kc);
   out->init_cinp = icinp;
   int k = 0;
   auto sep = [&](int cin, int cout, int cinp, int coutp, const std::vector<int>* pos = nullptr) {
@@ -216,6 +216,10 @@ int build(const nrx_desc* d, const float* const* w, int kc, DeviceModel<WT, BT>*
 }
 
 }  // namespace
+
+int init_padded_cin(const nrx_desc* d, int kc) {
+  return pow2_at_least(round_up(2 * init_a2p(d->num_rx_ant) + 2, kc), 32);
+}
 
 std::vector<int64_t> weight_sizes(const nrx_desc* d) {
   std::vector<int64_t> s;

@@ -27,6 +27,8 @@ inline int bits_max(const nrx_desc* d) {
 inline int num_heads(const nrx_desc* d) { return d->var_mcs_masking ? 1 : d->num_mcs; }
 inline int head_bits(const nrx_desc* d, int h) { return d->var_mcs_masking ? bits_max(d) : d->bits[h]; }
 
+// padded StateInit input width (FwdArgs::init_cinp) for MFMA K chunks of kc
+int init_padded_cin(const nrx_desc* d, int kc);
 // element counts of the weight arrays nrx_create expects, in Keras get_weights() order
 std::vector<int64_t> weight_sizes(const nrx_desc* d);
 // multiply-adds x 2 per resource element and user of a forward of num_it iterations

@@ -35,33 +35,7 @@
 #define NRX_RR_ZBRANCH 1
 #endif
 
-constexpr int kRrFO = 16;                       // output subcarriers per item
-constexpr int kRrSlots = kRrFO + 2 * kHalo;     // strip positions 0..21 (f = 16 strip - 3 + p)
-constexpr int kRrExRow = 4 * kT * 4 * 16;       // one exchange row: 4 chunks x 14 symbols x 4 groups x 16 B
-constexpr int kRrExChunk = kT * 4 * 16;         // 896 B per K chunk
-constexpr int kRrExRows = 14;                   // first / last row of each wave but wave 0's first, wave 7's last
-
-// LDS plan (dynamic, bytes): the three layer images (pw^T | taps | bias, WLds layout; conv3's
-// image carries the aggregation MLP at +16 KB / +24 KB and its biases at kWTailBias, the strip
-// kernels' WB layout, so EpiConv3 reads it unchanged), a block of -inf (conv1 / conv2 bias of the
-// pad lanes), a zero block the pad lanes read as exchange rows, the exchange rows (which the
-// readout launch reuses for its heads after conv3).
-constexpr int kRrW1 = 0;
-constexpr int kRrW2 = kRrW1 + kWTailBias;       // 35 584 B per 128-output image
-constexpr int kRrW3 = kRrW2 + kWTailBias;
-constexpr int kRrNeg = kRrW3 + kWBytes;         // conv3 + MLP image: 36 096 B
-// the pad lanes' bias row starts kRrNegOff into a 768-byte block of -inf: the layers' bias rows
-// sit at a multiple of 256 B, so the same offset would put a bias read and a -inf read of one
-// ds_read_b128 lane group on the same banks
-constexpr int kRrNegOff = 128;
-constexpr int kRrZero = kRrNeg + 768;
-constexpr int kRrX = kRrZero + kRrExChunk * 4;  // the pad lanes read zeros at every chunk offset
-constexpr int kRrLds = kRrX + kRrExRows * kRrExRow;
-static_assert(kRrLds <= 160 * 1024, "RR LDS plan exceeds the CU's LDS");
-// the readout heads (TAIL_READOUT_WB layout) are staged into the exchange region after conv3
-__host__ __device__ constexpr bool rr_heads_fit(int bits_max, int chp, int a2) {
-  return bits_max <= 16 && a2 <= chp && chp <= 32 && kHW2 + 256 * (bits_max + chp) <= kRrExRows * kRrExRow;
-}
+// (the item geometry kRrFO .. and the LDS plan kRrW1 .. kRrLds, rr_heads_fit: nrx_geom.h)
 
 // Diagnostic builds (NRX_STAMPS): s_memtime of lane 0 of waves 0 and 4 at the phase ends of the
 // workgroup's items k < 4: g_nrx_rr_stamps[wg][16 k + 2 m + (wave == 4)], m = 0 item start,

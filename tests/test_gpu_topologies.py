@@ -189,10 +189,8 @@ def _align256(x):
 
 
 def dispatch_model(spec, B, U, F, num_it, mask, fused, cus):
-    """(tier, {profile kernel: launches}) of one f16 forward: launch_forward_f16
-    (nrx_dispatch.hip), small_strips_fit / fused_applicable / Launch<P16>::run (nrx_launch.inc),
-    col_init_applicable / update_col_applicable / fwd_col_applicable (nrx_k_col.hip),
-    update_rr_applicable (nrx_k_rr.hip) restated; ``fused`` = 0 off, 1 default, 2 forced."""
+    """(tier, {profile kernel: launches}) of one f16 forward: plan_forward (nrx_dispatch.hip)
+    restated; ``fused`` = 0 off, 1 default, 2 forced."""
     a2, H, ninit, bmax = 2 * spec.num_rx_ant, spec.num_llr_heads, spec.num_init, spec.bits_max
     n = dict.fromkeys(_lib.KERNELS, 0)
     n["norm"] = 1 if F * 14 * a2 // 4 > 8192 else 0                        # kNormFusedMaxQ
