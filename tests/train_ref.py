@@ -90,8 +90,29 @@ def forward(params: List[torch.Tensor], spec, y, pe, h_hat, active, mcs_mask, nu
     return outs
 
 
-def losses(outs, spec, active, mcs_mask, bits, h, dmrs_symbols):
-    """(loss_data, loss_chest) of the readouts ``outs`` of ``forward``; ``h`` None: loss_chest = 0"""
+class _StableBCE(torch.autograd.Function):
+    """l(z, bit) with the derivative formed without cancellation: sigmoid(z) for bit 0, -sigmoid(-z) for bit 1,
+    each from e = exp(-|z|) as e / (1 + e) on its small side and 1 / (1 + e) on its large one.  Autograd on the
+    three terms of l gives the same number in float64; in float32 it adds 1 - bit and -+ e / (1 + e) in whatever
+    order the graph has, and at a confident, correct LLR (the derivative is the small side, 1e-5) that costs digits."""
+
+    @staticmethod
+    def forward(ctx, z, bit):
+        ctx.save_for_backward(z, bit)
+        return z.clamp_min(0) - bit * z + torch.log1p(torch.exp(-z.abs()))
+
+    @staticmethod
+    def backward(ctx, g):
+        z, bit = ctx.saved_tensors
+        e = torch.exp(-z.abs())
+        big, small = 1.0 / (1.0 + e), e / (1.0 + e)
+        d = torch.where(bit != 0, -torch.where(z >= 0, small, big), torch.where(z >= 0, big, small))
+        return g * d, None
+
+
+def losses(outs, spec, active, mcs_mask, bits, h, dmrs_symbols, stable_loss=False):
+    """(loss_data, loss_chest) of the readouts ``outs`` of ``forward``; ``h`` None: loss_chest = 0.
+    ``stable_loss``: the derivative of l by ``_StableBCE``, not by autograd on its terms"""
     B, U, F, T = bits.shape[:4]
     data = [t for t in range(T) if t not in set(dmrs_symbols)]
     ld = torch.zeros((), dtype=active.dtype)
@@ -101,7 +122,8 @@ def losses(outs, spec, active, mcs_mask, bits, h, dmrs_symbols):
             nb = spec.bits[m]
             z = z[:, :, :, data]
             bit = bits[:, :, :, data, :nb].to(z.dtype)
-            ell = z.clamp_min(0) - bit * z + torch.log1p(torch.exp(-z.abs()))
+            ell = _StableBCE.apply(z, bit) if stable_loss else \
+                z.clamp_min(0) - bit * z + torch.log1p(torch.exp(-z.abs()))
             wgt = (active * mcs_mask[:, :, m])[:, :, None, None, None]
             ld = ld + (wgt * ell).sum() / (B * U * F * len(data) * nb)
         if h is not None:
@@ -110,9 +132,11 @@ def losses(outs, spec, active, mcs_mask, bits, h, dmrs_symbols):
 
 
 def loss_and_grad(weights: Sequence[np.ndarray], spec, y, pe, h_hat, active, mcs_mask, bits, h,
-                  dmrs_symbols=(2, 11), num_it=None, multiloss=False, w_chest=0.0, dtype=torch.float64):
+                  dmrs_symbols=(2, 11), num_it=None, multiloss=False, w_chest=0.0, dtype=torch.float64,
+                  stable_loss=False):
     """The losses, the Keras-ordered gradient list of ``loss_data + w_chest loss_chest`` (zeros for the arrays of
-    unused iterations) and the last readout, all numpy.  ``mcs_mask`` None: one-hot on MCS 0."""
+    unused iterations) and the last readout, all numpy.  ``mcs_mask`` None: one-hot on MCS 0.  ``bits`` may be
+    wider than ``bits_max``: the columns beyond are not labels.  ``stable_loss``: see ``losses``."""
     t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dtype)     # noqa: E731
     params = [t(a).requires_grad_(True) for a in weights]
     B, U = active.shape
@@ -121,7 +145,8 @@ def loss_and_grad(weights: Sequence[np.ndarray], spec, y, pe, h_hat, active, mcs
         mcs_mask[..., 0] = 1.0
     act, mask = t(active), t(mcs_mask)
     outs = forward(params, spec, t(y), t(pe), t(h_hat), act, mask, num_it, all_states=multiloss)
-    ld, lc = losses(outs, spec, act, mask, torch.from_numpy(np.ascontiguousarray(bits)), t(h), dmrs_symbols)
+    ld, lc = losses(outs, spec, act, mask, torch.from_numpy(np.ascontiguousarray(bits)), t(h), dmrs_symbols,
+                    stable_loss)
     (ld + w_chest * lc).backward()
     grads = [np.zeros(a.shape, a.detach().numpy().dtype) if a.grad is None else a.grad.numpy() for a in params]
     llrs, h_ref = outs[-1]
@@ -217,3 +242,149 @@ def training_batch(case, seed=0):
     h = rng.standard_normal((B, U, F, 14, 2 * sp.num_rx_ant)).astype(np.float32)
     return dict(y=case.y, pe=case.pe, h_hat=case.h_hat if sp.use_h_hat else None, active=case.active,
                 mcs_mask=case.mcs_mask, bits=bits, h=h)
+
+
+# ---------------------------------------------------------------- the cases beyond the first corner
+def slab_positions(P, max_slabs=256):
+    """PC of nrx_train.hip ``make_plan``: the positions one workgroup of k_wgrad / k_dwgrad reduces, P spread over
+    at most ``max_slabs`` (kMaxSlabs) chunks and rounded up to the 32-position step"""
+    return ((P + max_slabs - 1) // max_slabs + 31) // 32 * 32
+
+
+def topo_activity(users):
+    """three slots: every user active, the last one alone, every user but the last (U = 2: [[1,1],[0,1],[1,0]]):
+    a slot with two or more active users, one with exactly one, an inactive (slot, user)"""
+    act = np.ones((3, users), np.float32)
+    act[1, :-1] = 0
+    act[2, -1] = 0
+    return act
+
+
+def _seeded_rt(name, batch, F, active, seed=7):
+    """the nrx_rt topology on seeded weights, U = 2, random inputs on an F-subcarrier grid (F = 1: the first
+    subcarrier of the F = 2 grid, the second user's pilots lying on odd subcarriers)"""
+    from tests.test_gpu_topologies import topo_case
+    case = topo_case({}, 2, max(F, 2), batch, seed, active=active, name=name)
+    if F < 2:
+        case.y, case.pe, case.h_hat = (np.ascontiguousarray(a) for a in (case.y[:, :F], case.pe[:, :F], case.h_hat[:, :, :F]))
+    return case
+
+
+def _topo(name):
+    from tests.test_gpu_topologies import SEEDS, TOPOLOGIES, VARIO_A4, topo_case
+    t = VARIO_A4 if name == "vario_a4" else TOPOLOGIES[name]
+    U = t["users"]
+    mask = "soft" if name == "a6_mask8_u16" else t.get("mask")
+    case = topo_case(t["spec"], U, 5, 3, SEEDS.get(name, 11), active=topo_activity(U) if U >= 2 else None,
+                     mcs_mask=mask, name=name)
+    sw = dict(w_chest=0.5)
+    if "run_it" in t:
+        sw["num_it"] = t["run_it"]
+    if name in ("a6_mask8_u16", "a3_noh_3heads_u5"):
+        sw["multiloss"] = True
+    return case, training_batch(case), sw, {}
+
+
+def _slab64(name):
+    from tests.helpers import make_case
+    active = np.ones((9, 3), np.float32)
+    active[4, 1] = 0
+    case = make_case(config="nrx_rt", batch=9, users=3, prbs=2, active=active)
+    return case, training_batch(case), dict(w_chest=0.02), {}
+
+
+def _grid(F):
+    def build(name):
+        case = _seeded_rt(name, 2, F, [[1, 1], [1, 0]])
+        return case, training_batch(case), dict(w_chest=0.5), {}
+    return build
+
+
+def _dmrs(symbols):
+    def build(name):
+        case = _seeded_rt(name, 2, 5, [[1, 1], [0, 1]])
+        return case, training_batch(case), dict(w_chest=0.5, dmrs_symbols=tuple(symbols)), {}
+    return build
+
+
+def _none_mask_vario(name):
+    from tests.test_gpu_topologies import VARIO_A4, topo_case
+    case = topo_case(VARIO_A4["spec"], 2, 5, 3, 11, active=topo_activity(2), name=name)
+    return case, dict(training_batch(case), mcs_mask=None), dict(w_chest=0.5), {}
+
+
+def _none_mask_masked(name):
+    from tests.helpers import make_case
+    case = make_case(config="nrx_large_var_mcs_64qam_masking", batch=2, users=2, prbs=1, active=[[1, 1], [1, 0]],
+                     seeded_weights=True)
+    return case, dict(training_batch(case), mcs_mask=None), dict(num_it=2, w_chest=0.5), {}
+
+
+def _bits_wide(name):
+    case = _seeded_rt(name, 2, 5, [[1, 1], [1, 0]])
+    batch = training_batch(case)
+    B, U, F, T, nb = batch["bits"].shape
+    batch["bits"] = np.concatenate([batch["bits"], np.ones((B, U, F, T, 11 - nb), np.uint8)], axis=-1)
+    return case, batch, dict(w_chest=0.5), {}
+
+
+def _dead_slots(name):
+    """slot 1 is all zero (ns = 0) with one active user, slot 2 has no active user; ``alt``: the same batch with
+    other labels (bits and h) in slot 2, which must not change anything"""
+    case = _seeded_rt(name, 3, 5, [[1, 1], [1, 0], [0, 0]])
+    case.y[1], case.h_hat[1] = 0, 0
+    batch = training_batch(case)
+    alt = dict(batch, bits=batch["bits"].copy(), h=batch["h"].copy())
+    alt["bits"][2] ^= 1
+    alt["h"][2] = 3.0 - 2.0 * alt["h"][2]
+    return case, batch, dict(w_chest=0.5), dict(alt=alt)
+
+
+CONFIDENT_SHIFT = 12.0
+
+
+def _confident(name):
+    """every LLR confident and correct: the head's last bias moved by +-12 (even / odd bit index) and the labels
+    set to match, so that every derivative of l is the small side of the sigmoid"""
+    case = _seeded_rt(name, 2, 5, [[1, 1], [1, 0]])
+    nb = case.spec.bits_max
+    sign = np.where(np.arange(nb) % 2 == 0, 1.0, -1.0).astype(np.float32)
+    bias = case.weights[-5]                              # ..., head (w1, b1, w2, b2), ChEst (w1, b1, w2, b2)
+    assert bias.shape == (nb,)
+    case.weights[-5] = bias + CONFIDENT_SHIFT * sign
+    batch = training_batch(case)
+    batch["bits"][...] = (sign > 0).astype(np.uint8)
+    return case, batch, dict(w_chest=0.0), dict(stable32=True)
+
+
+TOPO_NAMES = ("a1_qpsk_u1", "a3_noh_3heads_u5", "a4_noh_u2", "a6_mask8_u16", "a8_64qam_u3", "a9_b5_u7", "vario_a4")
+# name -> builder(name) of (case, batch, switches, extras); extras: stable32 (the float32 yardstick is the
+# oracle with the cancellation-free loss derivative), alt (a second batch the test compares with)
+MORE_CASES = {
+    "rt_slab64": _slab64,                                # P = 9072: PC = 64, two steps per chunk, a 16-row tail
+    **{"topo_" + n: (lambda name, n=n: _topo(n)) for n in TOPO_NAMES},
+    "grid_f1": _grid(1), "grid_f2": _grid(2), "grid_f13": _grid(13),
+    "dmrs_2": _dmrs((2,)), "dmrs_2_3_10_11": _dmrs((2, 3, 10, 11)), "dmrs_0_13": _dmrs((0, 13)),
+    "dmrs_0_to_12": _dmrs(range(13)),
+    "none_mask_vario": _none_mask_vario, "none_mask_masked": _none_mask_masked,
+    "bits_wide": _bits_wide, "dead_slots": _dead_slots, "confident": _confident,
+}
+_MORE, _REFS = {}, {}
+
+
+def more_case(name):
+    """``(case, batch, switches, extras)`` of ``MORE_CASES[name]``, built once; nobody writes to it"""
+    if name not in _MORE:
+        _MORE[name] = MORE_CASES[name](name)
+    return _MORE[name]
+
+
+def more_references(name):
+    """``(float64 result, float32 result)`` of ``loss_and_grad`` on ``more_case(name)``, computed once"""
+    if name not in _REFS:
+        case, batch, sw, extras = more_case(name)
+        ref = loss_and_grad(case.weights, case.spec, **batch, **sw)
+        ref32 = loss_and_grad(case.weights, case.spec, **batch, **sw, dtype=torch.float32,
+                              stable_loss=bool(extras.get("stable32")))
+        _REFS[name] = (ref, ref32)
+    return _REFS[name]
