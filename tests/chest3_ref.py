@@ -22,6 +22,8 @@ CASES = {
     "K3": (4, 16, 36, (2, 7, 11), 2, 2, "corr"),        # nd = 3, N a full tile, inactive users
     "K4": (2, 3, 132, (2, 11), 2, None, "random"),      # several M tiles, complex non-symmetric V_s, K = 66
     "K5": (2, 1, 12, (2, 11), 2, None, "corr"),         # A = 1
+    "K6": (2, 4, 24, (2, 3, 10, 11), 2, None, "corr"),  # nd = 4 (two double-symbol DMRS)
+    "K7": (2, 4, 24, (2,), 2, None, "corr"),            # nd = 1 with vector stores (K2 is its scalar twin)
 }
 
 

@@ -23,6 +23,9 @@ CASES = {
     "K3": (4, 16, 36, (2, 7, 11), 2, 2),      # nd = 3, 2A = 32, inactive users
     "K4": (2, 4, 132, (2, 11), 2, None),      # several M tiles, K = 264 not a tile multiple
     "K5": (2, 1, 12, (2, 11), 2, None),       # 2A = 2
+    "K6": (2, 4, 24, (2, 3, 10, 11), 2, None),    # nd = 4 (two double-symbol DMRS), vector stores
+    "K7": (2, 3, 24, (2, 3, 10, 11), 2, None),    # nd = 4, scalar stores
+    "K8": (2, 4, 24, (2,), 2, None),              # nd = 1 with vector stores (K2 is its scalar twin)
 }
 SEED = 7
 EBNO_DB = 5.0

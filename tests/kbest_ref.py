@@ -215,6 +215,13 @@ CASES = {
     "K4": (2, 4, 12, (6,), False, 14.0, 3, None, (2, 11), False, (66, 90, 5184)),
     "K5": (8, 8, 12, (2,), False, -2.0, 2, None, (2, 11), False, (107, 335, 4608)),
     "K6": (4, 16, 12, (2, 4, 6), True, 0.0, 4, 2, (2, 11), False, (103, 116, 4032)),
+    # U = 5, 6, 7 (10, 12, 14 levels) with vector Gram loads, and U = 5 with an odd antenna count
+    "K7": (5, 8, 12, (2,), False, 0.0, 2, None, (2, 11), False, (5, 29, 2880)),
+    "K8": (6, 8, 12, (2,), False, 0.0, 2, None, (2, 11), False, (5, 70, 3456)),
+    "K9": (7, 8, 12, (2,), False, 0.0, 2, None, (2, 11), False, (7, 123, 4032)),
+    "K10": (5, 5, 12, (4,), False, 10.0, 2, None, (2, 11), False, (30, 328, 5760)),
+    # 456 * 12 * 12 = 65 664 data REs, 128 more than the search grid holds: some waves take a second RE
+    "K11": (2, 4, 12, (2,), False, 2.0, 456, None, (2, 11), True, (4376, 6181, 262656)),
 }
 # K6 runs at 0 dB: at 12 dB (two active users on sixteen antennas) 99.8 % of its LLRs sit on the clip
 # and test no arithmetic.

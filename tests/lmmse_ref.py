@@ -103,6 +103,15 @@ CASES = {
     "C4": (1, 2, 13, (2,), False, 4.0, 1, None, (2,), {"ls": (39, 338), "perfect": (20, 338)}),
     "C5": (2, 4, 12, (4,), False, 8.0, 5, None, (2, 11), {"ls": (432, 5760), "perfect": (143, 5760)}),
     "C6": (3, 4, 12, (4,), False, 8.0, 2, None, (2, 11), {"perfect": (119, 3456)}),
+    # U = 5, 6, 7 with dwordx4 / dwordx2 loads (A = 8) and with scalar loads (A % 4 != 0)
+    "C7": (5, 8, 12, (4,), False, 8.0, 2, None, (2, 11), {"perfect": (27, 5760)}),
+    "C8": (6, 8, 12, (6,), False, 12.0, 2, None, (2, 11), {"perfect": (437, 10368)}),
+    "C9": (7, 8, 12, (2,), False, 2.0, 2, None, (2, 11), {"perfect": (71, 4032)}),
+    "C10": (5, 6, 12, (4,), False, 8.0, 2, None, (2, 11), {"perfect": (169, 5760)}),
+    "C11": (6, 10, 12, (4,), False, 8.0, 2, None, (2, 11), {"perfect": (19, 6912)}),
+    "C12": (7, 10, 12, (6,), False, 12.0, 2, None, (2, 11), {"perfect": (184, 12096)}),
+    # U = 1 with dwordx4 loads (C4 is its scalar twin)
+    "C13": (1, 4, 12, (2,), False, 4.0, 2, None, (2, 11), {"perfect": (4, 576)}),
 }
 SEED = 7
 

@@ -59,7 +59,7 @@ def test_error_map_equals_the_kronecker_error(no):
         d.err_var(0.0)
 
 
-@pytest.mark.parametrize("dmrs", [(2, 11), (2,), (2, 7, 11)])
+@pytest.mark.parametrize("dmrs", [(2, 11), (2,), (2, 7, 11), (2, 3, 10, 11)])
 def test_identity_space_covariance_gives_the_2d_filter(dmrs):
     p = _params(F=13, A=2, dmrs=dmrs)
     R_f, R_t = R.model_covariance(13)

@@ -23,7 +23,7 @@ def _cx(a):
 
 
 @pytest.mark.parametrize("F", [13, 24])
-@pytest.mark.parametrize("dmrs", [(2,), (2, 11), (2, 7, 11)])
+@pytest.mark.parametrize("dmrs", [(2,), (2, 11), (2, 7, 11), (2, 3, 10, 11)])
 def test_eigen_design_equals_the_kronecker_solve(F, dmrs):
     """chest.lmmse_design (nd frequency filters on the eigenvectors of R_t[D, D]) is the brute-force
     2-D filter, and its error map the brute-force one, to 1e-10"""

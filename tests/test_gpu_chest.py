@@ -10,6 +10,9 @@ cdm_group[u] = u % 2, 5 dB):
     K3  U 4  A 16  F 36   DMRS (2, 7, 11)  B 2, 2 active    nd = 3, 2A = 32, inactive users written zero
     K4  U 2  A 4   F 132  DMRS (2, 11)     B 2              several M tiles, K = 264 not a tile multiple
     K5  U 2  A 1   F 12   DMRS (2, 11)     B 2              2A = 2: N far below a tile
+    K6  U 2  A 4   F 24   DMRS (2, 3, 10, 11)  B 2          nd = 4, vector stores (k_chest_lmmse<4, true>)
+    K7  U 2  A 3   F 24   DMRS (2, 3, 10, 11)  B 2          nd = 4, scalar stores (k_chest_lmmse<4, false>)
+    K8  U 2  A 4   F 24   DMRS (2,)        B 2              nd = 1, vector stores (k_chest_lmmse<1, true>)
 
 Estimator gate (the gate of tests/test_gpu_lmmse.py).  e = max |gpu - ref| / max(1, |ref|) against
 the float64 oracle over EVERY element of the output; floor = the same expression for the oracle's
@@ -32,6 +35,15 @@ Figures of an MI355X run (as the test prints them: floor from numpy, e from the 
     K4    lin        2.0e-7   1.7e-7   8.0e-6
     K5    lmmse      1.5e-7   2.3e-7   8.0e-6
     K5    lin        1.5e-7   1.5e-7   8.0e-6
+    K6    lmmse      4.1e-7   3.7e-7   8.0e-6
+    K6    lin        3.8e-7   3.6e-7   8.0e-6
+    K7    lmmse      3.3e-7   3.1e-7   8.0e-6
+    K7    lin        3.6e-7   3.6e-7   8.0e-6
+    K8    lmmse      2.9e-7   2.5e-7   8.0e-6
+    K8    lin        6.8e-8   6.0e-8   8.0e-6
+
+Into an output that is only 4-byte aligned (scalar stores), lmmse / lin: K1 e 3.8e-7 / 2.0e-7, K3 5.9e-7 / 2.2e-7,
+K6 3.7e-7 / 3.6e-7, K7 3.1e-7 / 3.6e-7, each under its case's gate of 8.0e-6.
 
 Covariance: every lag of K1 / K2 / K4 within N 2^-52 sf[0] of numpy float64 (N = products in the
 lag: the float64 summation bound); measured max |gpu - ref| / bound: K1 0.001, K2 0.004, K4 < 0.001.
@@ -164,15 +176,18 @@ def test_only_the_own_pilots_are_read(kind):
 
 
 def test_unaligned_output_takes_the_scalar_path():
+    """K3 and K6 have A % 4 == 0, so only the alignment sends them to <3, false> and <4, false>"""
     import torch
-    for kind in KINDS:
-        ref, floor = _reference("K1", kind)
-        buf = torch.full((ref.size + 1,), float("nan"), dtype=torch.float32, device="cuda")
-        out = buf[1:].view(ref.shape)
-        assert out.data_ptr() % 16 == 4
-        got = _run("K1", kind, out=out).cpu().numpy()
-        e = float(np.max(np.abs(got - ref) / np.maximum(1.0, np.abs(ref))))
-        assert e <= 8.0 * max(floor, 1e-6), (kind, e)
+    for name in ("K1", "K3", "K6", "K7"):
+        for kind in KINDS:
+            ref, floor = _reference(name, kind)
+            buf = torch.full((ref.size + 1,), float("nan"), dtype=torch.float32, device="cuda")
+            out = buf[1:].view(ref.shape)
+            assert out.data_ptr() % 16 == 4
+            got = _run(name, kind, out=out).cpu().numpy()
+            e = float(np.max(np.abs(got - ref) / np.maximum(1.0, np.abs(ref))))
+            print(f"{name} {kind} unaligned: floor {floor:.2e}  e {e:.2e}")
+            assert e <= 8.0 * max(floor, 1e-6), (name, kind, e)
 
 
 # ---- covariance --------------------------------------------------------------------------------

@@ -10,6 +10,8 @@ cdm_group[u] = u % 2, 5 dB; R_s = rx_correlation(A, 0.9), or a random complex He
     K3  U 4  A 16  F 36   DMRS (2, 7, 11)  B 2, 2 active    nd = 3, N a full tile, inactive users written zero
     K4  U 2  A 3   F 132  DMRS (2, 11)     B 2              several M tiles, complex non-symmetric V_s, K = 66
     K5  U 2  A 1   F 12   DMRS (2, 11)     B 2              A = 1
+    K6  U 2  A 4   F 24   DMRS (2, 3, 10, 11)  B 2          nd = 4: k_chest3_pilot<4>, k_chest3_expand<4, *>
+    K7  U 2  A 4   F 24   DMRS (2,)        B 2              nd = 1, vector stores: k_chest3_expand<1, true>
 
 Gate (the gate of tests/test_gpu_chest.py, unchanged).  e = max |gpu - ref| / max(1, |ref|) over
 EVERY element against the float64 numpy application of the same f32-rounded tables
@@ -27,6 +29,10 @@ max |lmmse3 - lmmse| / max(1, |lmmse|) between the two kernels, under its own ca
     K3    3.2e-7   5.5e-7   8.0e-6   7.5e-7
     K4    3.7e-7   3.5e-7   8.0e-6   8.3e-7
     K5    1.9e-7   2.7e-7   8.0e-6   3.6e-7
+    K6    2.5e-7   2.6e-7   8.0e-6   3.6e-7
+    K7    2.6e-7   1.8e-7   8.0e-6   3.0e-7
+
+Into an output that is only 4-byte aligned (scalar stores): K1 e 2.8e-7, K3 5.5e-7, K6 2.6e-7.
 
 Quality at 5 dB (U 2, A 4, F 48, covariance from 256 slots, 64 test slots), NMSE nearest / 2-D lmmse /
 lmmse3: double_tdl_high 0.1490 / 0.0147 / 0.0072 (ratio 0.495; model value 0.49), double_tdl_low
@@ -152,14 +158,17 @@ def test_only_the_own_pilots_are_read():
 
 
 def test_unaligned_output_takes_the_scalar_path():
+    """K3 and K6 reach k_chest3_expand<3, false> and <4, false> this way only (A is a multiple of 4)"""
     import torch
-    ref, floor = _reference("K1")
-    buf = torch.full((ref.size + 1,), float("nan"), dtype=torch.float32, device="cuda")
-    out = buf[1:].view(ref.shape)
-    assert out.data_ptr() % 16 == 4
-    got = _run("K1", out=out).cpu().numpy()
-    e = float(np.max(np.abs(got - ref) / np.maximum(1.0, np.abs(ref))))
-    assert e <= 8.0 * max(floor, 1e-6), e
+    for name in ("K1", "K3", "K6"):
+        ref, floor = _reference(name)
+        buf = torch.full((ref.size + 1,), float("nan"), dtype=torch.float32, device="cuda")
+        out = buf[1:].view(ref.shape)
+        assert out.data_ptr() % 16 == 4
+        got = _run(name, out=out).cpu().numpy()
+        e = float(np.max(np.abs(got - ref) / np.maximum(1.0, np.abs(ref))))
+        print(f"{name} lmmse3 unaligned: floor {floor:.2e}  e {e:.2e}")
+        assert e <= 8.0 * max(floor, 1e-6), (name, e)
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -10,6 +10,15 @@ err_var = 0, k = 64, llr_clip = 20, slots from the GPU generator with ``want_h=T
     K4  U 2  A 4   64-QAM  14 dB  B 3  pruned (4096 leaves)
     K5  U 8  A 8   QPSK    -2 dB  B 2  pruned, 16 levels
     K6  U 4  A 16  2/4/6 drawn, 2 active ports, 0 dB, B 4: mixed L, inactive users
+    K7  U 5  A 8   QPSK     0 dB  B 2  pruned, 10 levels: k_kbest_gram<5, true>
+    K8  U 6  A 8   QPSK     0 dB  B 2  pruned, 12 levels: k_kbest_gram<6, true>
+    K9  U 7  A 8   QPSK     0 dB  B 2  pruned, 14 levels: k_kbest_gram<7, true>
+    K10 U 5  A 5   16-QAM  10 dB  B 2  pruned; odd A: k_kbest_gram<5, false>
+    K11 U 2  A 4   QPSK     2 dB  B 456  exhaustive (16 leaves); 65 664 data REs on a search grid of 65 536
+                                          waves: 128 waves take a second RE
+
+tests/dispatch_cases.py names, for every ``case`` of ``launch_kbest`` and both values of ``vec``, the case that
+runs it; the scalar Gram kernels of U = 1, 2, 3, 4, 6, 7, 8 run through the unaligned test.
 
 Gate.  e = max |llr_gpu - llr_ref| / max(1, |llr_ref|) against the float64 reference (ML for K1 and
 K2, kbest_ref for the rest); floor = the same expression for kbest_ref's own float32 run against
@@ -32,9 +41,20 @@ same table):
     K4            1.4e-5   1.4e-5   1.1e-4   0          66 / 5184
     K5            4.8e-6   6.1e-6   8.0e-5   0         107 / 4608
     K6            5.3e-6   5.9e-6   8.0e-5   0         103 / 4032
+    K7            2.5e-6   1.7e-6   8.0e-5   0           5 / 2880
+    K8            2.3e-6   3.7e-6   8.0e-5   0           5 / 3456
+    K9            3.8e-6   5.8e-6   8.0e-5   0           7 / 4032
+    K10           2.7e-5   2.9e-5   2.2e-4   0          30 / 5760
+    K11           4.3e-6   4.0e-6   8.0e-5   0        4376 / 262656
     K3 k = 1      0        0        8.0e-5   0
     K3 k = 16     2.9e-5   2.8e-5   2.3e-4   0
     K3 unaligned  2.9e-5   5.9e-5   2.3e-4   0
+    K1 unaligned  1.4e-6   1.4e-6   8.0e-5   0
+    K4 unaligned  1.4e-5   1.9e-5   1.1e-4   0
+    K2 unaligned  2.0e-6   1.6e-6   8.0e-5   0
+    K8 unaligned  2.3e-6   3.8e-6   8.0e-5   0
+    K9 unaligned  3.8e-6   5.8e-6   8.0e-5   0
+    K5 unaligned  4.8e-6   6.1e-6   8.0e-5   0
 """
 import functools
 
@@ -189,12 +209,10 @@ def test_wider_bits_stride(bs):
 
 
 def test_unaligned_tensors_take_the_scalar_paths():
-    """y, h and llr that are only 4-byte aligned: scalar loads and stores, same LLRs"""
+    """y, h and llr that are only 4-byte aligned: scalar loads and stores, same LLRs.  Every one of these
+    cases has an even A, so this is what takes U = 1, 2, 3, 4, 6, 7 and 8 to k_kbest_gram<U, false>."""
     import torch
     from neural_rx_amd.kbest import KBestDetector
-    p, no = _params("K3")
-    sb, _ = _slots("K3")
-    ref, floor, used, _ = _reference("K3")
 
     def shifted(t):
         buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
@@ -203,10 +221,14 @@ def test_unaligned_tensors_take_the_scalar_paths():
         assert v.data_ptr() % 16 == 4 and v.is_contiguous()
         return v
 
-    out = shifted(torch.full(ref.shape, float("nan"), dtype=torch.float32, device="cuda"))
-    llr = KBestDetector()(shifted(sb.y), shifted(sb.h), sb.active, sb.mcs, p.mcs_bits, no, p.dmrs_symbols, out=out)
-    torch.cuda.synchronize()
-    _gate_check("K3 unaligned", llr.cpu().numpy()[0], ref[0], floor, used, False)
+    for name in ("K3", "K1", "K4", "K2", "K8", "K9", "K5"):
+        p, no = _params(name)
+        sb, _ = _slots(name)
+        ref, floor, used, _ = _reference(name)
+        out = shifted(torch.full(ref.shape, float("nan"), dtype=torch.float32, device="cuda"))
+        llr = KBestDetector()(shifted(sb.y), shifted(sb.h), sb.active, sb.mcs, p.mcs_bits, no, p.dmrs_symbols, out=out)
+        torch.cuda.synchronize()
+        _gate_check(f"{name} unaligned", llr.cpu().numpy()[0], ref[0], floor, used, K.CASES[name][9])
 
 
 def test_batch_split_is_bit_identical():

@@ -10,6 +10,16 @@ generator with ``want_h=True``):
     C4  U 1  A 2   F 13  QPSK     4 dB  B 1  scalar loads, odd width, partial wave, one DMRS symbol
     C5  U 2  A 4   F 12  16-QAM   8 dB  B 5  840 REs: grid tail of a 256-thread block
     C6  U 3  A 4   F 12  16-QAM   8 dB  B 2  non-power-of-two U (perfect CSI)
+    C7  U 5  A 8   F 12  16-QAM   8 dB  B 2  k_lmmse<5, true>   (C7..C13: perfect CSI)
+    C8  U 6  A 8   F 12  64-QAM  12 dB  B 2  k_lmmse<6, true>
+    C9  U 7  A 8   F 12  QPSK     2 dB  B 2  k_lmmse<7, true>: two antennas per step at a U other than 8
+    C10 U 5  A 6   F 12  16-QAM   8 dB  B 2  k_lmmse<5, false>
+    C11 U 6  A 10  F 12  16-QAM   8 dB  B 2  k_lmmse<6, false>
+    C12 U 7  A 10  F 12  64-QAM  12 dB  B 2  k_lmmse<7, false>: scalar loads at U >= 7
+    C13 U 1  A 4   F 12  QPSK     4 dB  B 2  k_lmmse<1, true> (C4 is its scalar twin)
+
+tests/dispatch_cases.py names, for every ``case`` of ``launch_lmmse`` and both values of ``vec``, the case that
+runs it; U = 2, 3, 4, 8 reach the scalar kernels through the unaligned test.
 
 Gate.  e = max |llr_gpu - llr_ref| / max(1, |llr_ref|) against the float64 reference; floor = the
 same expression for the reference's own float32 run against its float64 run (reference against
@@ -33,6 +43,18 @@ the GPU generator's slots):
     C5    ls       1.1e-5   1.3e-5   8.6e-5   0
     C5    perfect  2.0e-5   1.1e-5   1.6e-4   0
     C6    perfect  1.0e-5   8.5e-6   8.0e-5   0
+    C7    perfect  1.8e-5   1.5e-5   1.5e-4   0
+    C8    perfect  5.5e-5   5.9e-5   4.4e-4   0
+    C9    perfect  1.8e-5   1.3e-5   1.4e-4   0
+    C10   perfect  1.3e-5   1.3e-5   1.0e-4   0
+    C11   perfect  2.5e-5   2.1e-5   2.0e-4   0
+    C12   perfect  4.8e-5   6.3e-5   3.8e-4   0
+    C13   perfect  4.1e-7   3.3e-7   8.0e-5   0
+    unaligned (scalar loads and stores), perfect CSI:
+    C1             6.2e-6   6.1e-6   8.0e-5   0
+    C6             1.0e-5   9.6e-6   8.0e-5   0
+    C3             3.5e-6   3.4e-6   8.0e-5   0
+    C2             5.1e-5   5.2e-5   4.1e-4   24 (0.17 %)
 
 The GPU bit-error counts equal the reference's (and the table's) on every case.  min mu over the
 active RE-users is >= 0.17 on every case (asserted >= 1e-3), far from the mu < 1e-6 rule.
@@ -163,12 +185,10 @@ def test_wider_and_odd_bits_stride(bs):
 
 
 def test_unaligned_tensors_take_the_scalar_paths():
-    """y, h and llr that are only 4-byte aligned: scalar loads and stores, same LLRs"""
+    """y, h and llr that are only 4-byte aligned: scalar loads and stores, same LLRs.  C6, C3 and C2 have
+    A % 4 == 0, so this is what takes U = 3, 4 and 8 to k_lmmse<U, false>."""
     import torch
     from neural_rx_amd.baseline import LMMSEDetector
-    p, no = _params("C1")
-    sb, _ = _slots("C1")
-    ref, _, floor, used = _reference("C1", "perfect")
 
     def shifted(t):
         buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
@@ -177,10 +197,14 @@ def test_unaligned_tensors_take_the_scalar_paths():
         assert v.data_ptr() % 16 == 4 and v.is_contiguous()
         return v
 
-    out = shifted(torch.full(ref.shape, float("nan"), dtype=torch.float32, device="cuda"))
-    llr = LMMSEDetector()(shifted(sb.y), shifted(sb.h), sb.active, sb.mcs, p.mcs_bits, no, p.dmrs_symbols, out=out)
-    torch.cuda.synchronize()
-    _gate_check("C1 perfect unaligned", llr.cpu().numpy()[0], ref[0], floor, used)
+    for name in ("C1", "C6", "C3", "C2"):
+        p, no = _params(name)
+        sb, _ = _slots(name)
+        ref, _, floor, used = _reference(name, "perfect")
+        out = shifted(torch.full(ref.shape, float("nan"), dtype=torch.float32, device="cuda"))
+        llr = LMMSEDetector()(shifted(sb.y), shifted(sb.h), sb.active, sb.mcs, p.mcs_bits, no, p.dmrs_symbols, out=out)
+        torch.cuda.synchronize()
+        _gate_check(f"{name} perfect unaligned", llr.cpu().numpy()[0], ref[0], floor, used)
 
 
 def test_all_zero_channel():

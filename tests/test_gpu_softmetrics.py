@@ -16,6 +16,12 @@ by 0, +-1e-30, +-87, +-89, +-1e4, NaN, +inf and -inf; random bits.  FS = the str
                                                                     strip, S at its limit
     S7  H 1  B 6  U 2   F 12         stride 8  MCS drawn of 1..8   M at its limit (the ordered pass's rows are
                                                                     a template argument: 1, 2, 3, 4, 8)
+    S8  H 1  B 6  U 2   F 12         stride 8  MCS drawn of 2/4/6/8 four MCS rows: k_llr_reduce<4>
+    S9  H 1  B 300 U 2  F 12         stride 4  MCS drawn of 2/4    the ordered pass beyond its first pass: two
+                                                                    chunks of 256 slots, and tiles of 81 staged
+                                                                    records (7168 / (8 * 9 + 16)) of which a wave
+                                                                    loads 4 per step; inactive users on both
+                                                                    sides of the chunk boundary
 
 Gates.  cnt and nonfinite equal the reference exactly.  For every cell with cnt > 0 and every scale
 |bmi_gpu - bmi_ref| <= 1e-6: the linear term of the loss is exact in float64; the bounded term is
@@ -24,8 +30,8 @@ times that budget and does not depend on the size of the LLRs (hence the +-1e4 a
 The NMSE sums are held to 1e-10 relative: n 2^-53 with n < 2^17 terms, rounded up.
 
 Figures of an MI355X run (as the tests print them): max |bmi_gpu - bmi_ref| between 2.1e-10 (S1a)
-and 2.5e-9 (S3) over the cases, with cell BMIs down to -426 because of the wrong-signed +-1e4 entries;
-NMSE sums within 2.3e-16 relative.
+and 3.5e-9 (S7) over the cases (S8 3.3e-9, S9 7.3e-10), with cell BMIs down to -833 because of the
+wrong-signed +-1e4 entries; NMSE sums within 2.3e-16 relative.
 """
 import functools
 
@@ -49,6 +55,8 @@ CASES = {
     "S5": (1, 5, 16, 12, 2, (2,), (2, 11), (), SM.DEFAULT_SCALES),
     "S6": (1, 2, 2, FS + 1, 7, (6,), (2, 11), (), tuple(2.0 ** (0.25 * (j - 8)) for j in range(16))),
     "S7": (1, 6, 2, 12, 8, (1, 2, 3, 4, 5, 6, 7, 8), (2, 11), ((3, 0),), SM.DEFAULT_SCALES),
+    "S8": (1, 6, 2, 12, 8, (2, 4, 6, 8), (2, 11), (), SM.DEFAULT_SCALES),
+    "S9": (1, 300, 2, 12, 4, (2, 4), (2, 11), ((0, 1), (255, 0), (256, 0), (299, 1)), SM.DEFAULT_SCALES),
 }
 BMI_GATE = 1e-6
 

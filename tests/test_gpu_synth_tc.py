@@ -147,6 +147,25 @@ def test_channel_against_the_statement(doppler, delay, l_min, l_max, ta):
         assert res > 1e-3
 
 
+# (A, F): the block shapes of k_tc_h, FB = min(4, 256 / (14 A)) subcarriers per workgroup.  The shapes above run
+# FB = 4 with F % FB == 0 only.  A = 5: FB = 3, 17 workgroups, the last with two subcarriers (the ff < F and f >= F
+# guards); A = 16: FB = 1; A = 8: FB = 2.  A = 5 and 8 also take the generator through k_timechan<8, 2>, A = 16
+# through <16, 1>.  An MI355X run: y, h and h_hat equal the statement's f32 values bit for bit at all three shapes;
+# r_out within 2.8e-14, 3.8e-14 and 3.5e-14 of it (scale 5.4 to 6.4).
+H_BLOCKS = [(5, 50), (16, 48), (8, 46)]
+
+
+@pytest.mark.parametrize("A_,F_", H_BLOCKS)
+def test_channel_against_the_statement_at_other_block_shapes(A_, F_):
+    doppler, delay = 20e3, 300e-9
+    kw = dict(num_rx_ant=A_, num_subcarriers=F_, max_doppler_hz=doppler, max_delay_s=delay)
+    p = _params(_tc(l_min=-6, l_max=None, timing_advance=0), **kw)
+    g = _gpu(p)
+    assert g["h"].shape == (B, U, F_, 14, 2 * A_)
+    ref = R.generate(_spec(p), N, CP, -6, -1, 0)
+    _against(g, ref, _gpu(_params(**kw)))
+
+
 def test_exact_workspace_and_aerial_outputs():
     p = _params(_tc())
     g = _gpu(p)

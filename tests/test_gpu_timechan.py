@@ -11,6 +11,16 @@ Shapes.  B = 3, U = 2, L = 3, NS = 4, fs = 64 * 30 kHz, Doppler up to +-20 kHz a
 less than one tile), 2500 (no multiple of any tile, several workgroups per row) and 256 (exactly one tile of the
 widest kernel); spans (0, 0), (-3, 5), (-6, 40) and 256 taps.  The output is the NaN-poisoned body of a guarded
 buffer (tests/memguard.py): every element written, nothing beyond.
+
+EDGES (below) adds the ends of every loop and table of the kernel, at both Doppler ranges and under the same gate:
+A = 4, 8, 16 and 1, NS = 16 and 1, L = 1 and 8, U = 1.  Figures of an MI355X run (e_ref from numpy, the kernel's
+error against the longdouble statement, the gate), at 20 kHz with rx_mix / at 400 Hz without:
+
+    A   NS  L  U  Ls    taps     e_ref     kernel    gate     |  e_ref     kernel    gate
+    4   16  1  1  954   -3..5    4.56e-14  1.60e-14  3.65e-13 |  3.54e-15  2.66e-15  5.13e-14
+    8   16  3  2  954   -3..5    5.84e-14  3.36e-14  4.67e-13 |  5.99e-15  4.99e-15  1.07e-13
+    16  16  8  2  256   -6..40   5.36e-14  2.10e-14  4.29e-13 |  3.26e-14  9.17e-15  2.61e-13
+    1   1   8  2  2500  -3..5    5.15e-13  3.64e-13  4.12e-12 |  7.87e-15  7.80e-15  1.62e-13
 """
 import functools
 
@@ -38,8 +48,21 @@ CASES = [
 ]
 
 
+# (A, NS, L, U, Ls, l_min, l_max, max delay in samples), each at both Doppler ranges: the edges of the kernel's
+# shapes.  A = 4, 8, 16 fill k_timechan<4, 4>, <8, 2>, <16, 1> to their last accumulator and make the last chunk of
+# four antennas a full one (A = 16: all four chunks); NS = 16 fills the 64 rows of the sinusoid tables of a chunk,
+# NS = 1 leaves one row per antenna; L = 1 and 8 and U = 1 are the ends of the path and user loops; A = 1 is one
+# antenna in a chunk of four.  rx_mix is on at 20 kHz and off at 400 Hz.
+EDGES = [
+    (4, 16, 1, 1, 954, -3, 5, 3.0),
+    (8, 16, 3, 2, 954, -3, 5, 3.0),
+    (16, 16, 8, 2, 256, -6, 40, 30.0),
+    (1, 1, 8, 2, 2500, -3, 5, 3.0),
+]
+
+
 @functools.lru_cache(maxsize=None)
-def _inputs(A, Ls, dmax, fmax=20e3, seed=11):
+def _inputs(A, Ls, dmax, fmax=20e3, seed=11, U=U, L=L, NS=NS):
     rng = np.random.default_rng(seed + 131 * A + Ls)
     cn = lambda *s: rng.standard_normal(s) + 1j * rng.standard_normal(s)  # noqa: E731
     x = cn(B, U, Ls)
@@ -51,9 +74,9 @@ def _inputs(A, Ls, dmax, fmax=20e3, seed=11):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(A, Ls, l_min, l_max, mixed, dmax, fmax):
+def _reference(A, Ls, l_min, l_max, mixed, dmax, fmax, U=U, L=L, NS=NS):
     """(longdouble result, e_ref): computed once per case, shared and left unchanged"""
-    x, tau, g0, fd, mix = _inputs(A, Ls, dmax, fmax)
+    x, tau, g0, fd, mix = _inputs(A, Ls, dmax, fmax, U=U, L=L, NS=NS)
     m = mix if mixed else None
     r64 = R.time_channel(x, tau, g0, fd, FS, N0, l_min, l_max, m)
     rld = R.time_channel(x, tau, g0, fd, FS, N0, l_min, l_max, m, real=np.longdouble)
@@ -78,16 +101,28 @@ def _run(x, tau, g0, fd, mix, l_min, l_max, n0=N0):
 
 @pytest.mark.parametrize("A,Ls,l_min,l_max,mixed,dmax,fmax", CASES)
 def test_against_the_statement(A, Ls, l_min, l_max, mixed, dmax, fmax):
-    x, tau, g0, fd, mix = _inputs(A, Ls, dmax, fmax)
-    rld, e_ref = _reference(A, Ls, l_min, l_max, mixed, dmax, fmax)
+    _gate_check(A, Ls, l_min, l_max, mixed, dmax, fmax)
+
+
+def _gate_check(A, Ls, l_min, l_max, mixed, dmax, fmax, **shape):
+    x, tau, g0, fd, mix = _inputs(A, Ls, dmax, fmax, **shape)
+    rld, e_ref = _reference(A, Ls, l_min, l_max, mixed, dmax, fmax, **shape)
     got = _run(x, tau, g0, fd, mix if mixed else None, l_min, l_max)
+    assert got.shape == rld.shape
     assert np.isfinite(got.view(np.float64)).all()                       # every element written
     scale = float(np.abs(rld).max())
     err = float(np.abs(got - rld).max())
     gate = 8.0 * max(e_ref, 1e-15 * scale)
-    print(f"A={A} Ls={Ls} taps {l_min}..{l_max} mix={mixed} fd<={fmax:g}: e_ref {e_ref:.3g} kernel {err:.3g} gate {gate:.3g} "
-          f"max|r| {scale:.3g}")
+    tag = "".join(f" {k}={v}" for k, v in shape.items())
+    print(f"A={A}{tag} Ls={Ls} taps {l_min}..{l_max} mix={mixed} fd<={fmax:g}: e_ref {e_ref:.3g} kernel {err:.3g} "
+          f"gate {gate:.3g} max|r| {scale:.3g}")
     assert err <= gate
+
+
+@pytest.mark.parametrize("fmax", [20e3, 400.0])
+@pytest.mark.parametrize("A,NS,L,U,Ls,l_min,l_max,dmax", EDGES)
+def test_edges_of_the_kernel_shapes(A, NS, L, U, Ls, l_min, l_max, dmax, fmax):
+    _gate_check(A, Ls, l_min, l_max, fmax == 20e3, dmax, fmax, U=U, L=L, NS=NS)
 
 
 def test_an_integer_delay_without_doppler_shifts_and_scales():
