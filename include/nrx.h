@@ -709,6 +709,24 @@ int nrx_generate_slots_tc(const nrx_gen_desc* desc, const nrx_gen_chan* chan, co
                           const nrx_gen_tc* tc, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* The slot generator with one noise variance per slot: the noise of slot b has the variance no_slot[b] per
+ * complex resource element where every other call uses desc.no.  Nothing else changes: the draws, the channel,
+ * the bits and every stage are those of nrx_generate_slots_tc, so slot slot_offset + b generated with
+ * no_slot[b] = x is bit for bit the slot that a call with desc.no = x gives at that global index, in every
+ * output (y, h_hat, h, bits, active, mcs and the Aerial outputs).  noise == NULL or no_slot == NULL is exactly
+ * nrx_generate_slots_tc: the same launches, workspace (nrx_gen_workspace_size_tc) and bits.
+ * no_slot is device data that the host never reads: the caller keeps every entry finite and >= 0 (as for the
+ * Aerial position lists, nothing here can check it).  A no_slot that is not 8-byte aligned is
+ * NRX_ERR_INVALID_ARG; the other checks are those of nrx_generate_slots_tc, all before the first HIP call. */
+typedef struct nrx_gen_noise {
+  const double* no_slot;       /* device, [B]: noise variance per complex RE of slot b; NULL: desc.no */
+} nrx_gen_noise;
+
+int nrx_generate_slots_no(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                          const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
+                          const nrx_gen_tc* tc, const nrx_gen_noise* noise, const nrx_gen_out* out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* Uncoded error counters of one batch (sim_ber's counting, scripts/evaluate.py:193-202,
  * with the active-port masking of E2E_Model._mask_active_dmrs, e2e_model.py:195-209):
  * counts[u][0..3] += (bit errors, bits, block errors, blocks) over the active (slot, user)
@@ -1257,6 +1275,30 @@ typedef struct nrx_train_io {
 int nrx_train_workspace_size(const nrx_desc* desc, const nrx_train_io* io, size_t* bytes);
 int nrx_train_grad(const nrx_desc* desc, const nrx_train_io* io, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* One step's gradient from several calls: nrx_train_grad on a micro-batch of a step whose whole batch has
+ * batch_total slots.  batch_total replaces shape.batch in every loss denominator,
+ *   1 / (batch_total U F (14 - n_dmrs) bits_m)  for loss_data and  1 / (batch_total U F 14 2A)  for loss_chest,
+ * and in their derivatives, so every term has the weight it has in the whole batch: the sum over micro-batches of
+ * any sizes (equal or not) whose B add up to batch_total is the loss and the gradient of the whole batch, with
+ * nothing to rescale afterwards.  accumulate = 0: grad and loss are overwritten, as nrx_train_grad does;
+ * accumulate = 1: grad is not zeroed and every weight-gradient sum is added onto what it holds (in f64, rounded
+ * once per sum), loss is added onto in f64.  The first call of a step overwrites, the others accumulate; the
+ * launches and their order are those of nrx_train_grad, nothing is atomic, and a repeated sequence of calls gives
+ * the same bits.  The arrays of iterations beyond num_it are written by no call: they stay exactly zero through a
+ * sequence that starts with accumulate = 0.  llr / h_ref are those of the micro-batch of the call.
+ * acc == NULL, accumulate = 0 with batch_total == shape.batch, and accumulate = 1 with batch_total == shape.batch
+ * onto a zeroed grad and loss all give the bits of nrx_train_grad.  The workspace is that of
+ * nrx_train_workspace_size for the call's own shape: a step needs the workspace of its largest micro-batch only.
+ * accumulate outside 0/1 is NRX_ERR_INVALID_ARG; batch_total < shape.batch or > 65535 is NRX_ERR_SHAPE; the
+ * other checks are those of nrx_train_grad, all before the first HIP call. */
+typedef struct nrx_train_acc {
+  int32_t accumulate;          /* 0: grad and loss are overwritten; 1: added onto what they hold */
+  int32_t batch_total;         /* B of the whole step: replaces shape.batch in every loss denominator */
+} nrx_train_acc;
+
+int nrx_train_grad_acc(const nrx_desc* desc, const nrx_train_io* io, const nrx_train_acc* acc, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* One Adam step (Keras: tf.keras.optimizers.Adam, defaults 1e-3 / 0.9 / 0.999 / 1e-7) on n f32 elements, with
  * t = step:   m = b1 m + (1 - b1) g;   v = b2 v + (1 - b2) g^2;

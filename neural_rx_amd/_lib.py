@@ -157,6 +157,10 @@ class nrx_gen_tc(ctypes.Structure):
                 + _i32("l_min", "l_max", "timing_advance", "pad_") + _ptr("r_out", "x_out"))
 
 
+class nrx_gen_noise(ctypes.Structure):
+    _fields_ = _ptr("no_slot")
+
+
 class nrx_count_io(ctypes.Structure):
     _fields_ = GRID + _i32("num_heads") + MCS + _ptr("llr", "bits", "mcs", "active", "counts")
 
@@ -221,6 +225,10 @@ class nrx_train_io(ctypes.Structure):
                 + _ptr("y", "pe", "h_hat", "active", "mcs_mask", "bits", "h", "weights", "grad", "loss", "llr", "h_ref"))
 
 
+class nrx_train_acc(ctypes.Structure):
+    _fields_ = _i32("accumulate", "batch_total")
+
+
 class nrx_adam_io(ctypes.Structure):
     _fields_ = ([("n", ctypes.c_int64)] + _ptr("w", "g", "m", "v") + _f64("lr", "beta1", "beta2", "eps")
                 + [("step", ctypes.c_int64)])
@@ -273,6 +281,7 @@ def _signatures():
         "nrx_time_channel": (RC, [P(nrx_tc_io), V]),
         "nrx_gen_workspace_size_tc": (RC, [gen, chan, cfo, dmrs, cir, td, tc, PZ]),
         "nrx_generate_slots_tc": (RC, [gen, chan, cfo, dmrs, cir, td, tc, out] + run),
+        "nrx_generate_slots_no": (RC, [gen, chan, cfo, dmrs, cir, td, tc, P(nrx_gen_noise), out] + run),
         "nrx_count_errors": (RC, [P(nrx_count_io), V]),
         "nrx_cfo_estimate": (RC, [P(nrx_cfo_io), V]),
         "nrx_cfo_rotate": (RC, [P(nrx_cfo_io), V]),
@@ -300,6 +309,7 @@ def _signatures():
         "nrx_ldpc_count": (RC, [P(nrx_ldpc_count_io), V]),
         "nrx_train_workspace_size": (RC, [desc, P(nrx_train_io), PZ]),
         "nrx_train_grad": (RC, [desc, P(nrx_train_io)] + run),
+        "nrx_train_grad_acc": (RC, [desc, P(nrx_train_io), P(nrx_train_acc)] + run),
         "nrx_adam_step": (RC, [P(nrx_adam_io), V]),
     }
 

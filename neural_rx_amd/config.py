@@ -265,3 +265,100 @@ def data_re_indices(cfg: NRXConfig, num_subcarriers: int, num_symbols: int = 14)
     dm = set(dmrs_symbols(cfg))
     ts = [t for t in range(num_symbols) if t not in dm]
     return np.array([t * num_subcarriers + f for t in ts for f in range(num_subcarriers)], np.int32)
+
+
+@dataclasses.dataclass(frozen=True)
+class ScheduleStage:
+    """One entry of a ``training_schedule``: ``num_iter`` Adam steps under these settings."""
+
+    num_iter: int
+    learning_rate: float
+    batch_size: int
+    min_training_snr_db: Tuple[float, ...]    # per number of active users, min_num_tx .. max_num_tx
+    max_training_snr_db: Tuple[float, ...]
+    double_readout: bool
+    apply_multiloss: bool
+    weighting_double_readout: float
+
+    @property
+    def w_chest(self) -> float:
+        """the weight of the channel-readout loss: 0 without the double readout"""
+        return self.weighting_double_readout if self.double_readout else 0.0
+
+
+@dataclasses.dataclass(frozen=True)
+class TrainingSchedule:
+    """The ``[training]`` block's ``training_schedule`` and the user range of ``[neural_receiver]``."""
+
+    stages: Tuple[ScheduleStage, ...]
+    min_num_tx: int
+    max_num_tx: int
+
+    def scaled(self, scale: float) -> "TrainingSchedule":
+        """every ``num_iter`` multiplied by ``scale`` (rounded, at least 1 step)"""
+        return dataclasses.replace(self, stages=tuple(
+            dataclasses.replace(s, num_iter=max(1, int(round(s.num_iter * scale)))) for s in self.stages))
+
+    @property
+    def total_steps(self) -> int:
+        return sum(s.num_iter for s in self.stages)
+
+    def stage_of(self, step: int) -> Tuple[int, ScheduleStage]:
+        """``(index, stage)`` of global step ``step`` (0-based)"""
+        for i, s in enumerate(self.stages):
+            if step < s.num_iter:
+                return i, s
+            step -= s.num_iter
+        raise IndexError("step beyond the schedule")
+
+
+_SCHEDULE_FIELDS = ("num_iter", "learning_rate", "batch_size", "min_training_snr_db", "max_training_snr_db",
+                    "double_readout", "apply_multiloss", "weighting_double_readout")
+
+
+def parse_schedule(path: str) -> TrainingSchedule:
+    """The training schedule of a reference-format ``.cfg`` (``training_schedule``, ``min_num_tx``,
+    ``max_num_tx``), read like ``parse_cfg``: ``configparser`` + ``ast.literal_eval``, never ``eval``.  A stage
+    with ``train_tx = True`` is refused: trainable transmitters are not implemented."""
+    cp = configparser.ConfigParser(inline_comment_prefixes=("#",))
+    cp.optionxform = str
+    with open(path) as f:
+        cp.read_file(f)
+    sec = {}
+    for s in cp.sections():
+        for k, v in cp.items(s):
+            sec[k] = v
+    if "training_schedule" not in sec:
+        raise ValueError(f"{path}: no training_schedule")
+    sched = ast.literal_eval(sec["training_schedule"])
+    if not isinstance(sched, dict):
+        raise ValueError(f"{path}: training_schedule must be a dict of lists")
+    missing = [k for k in _SCHEDULE_FIELDS if k not in sched]
+    if missing:
+        raise ValueError(f"{path}: training_schedule lacks {', '.join(missing)}")
+    n = len(sched["num_iter"])
+    if n < 1 or any(len(sched[k]) != n for k in _SCHEDULE_FIELDS) or len(sched.get("train_tx", [False] * n)) != n:
+        raise ValueError(f"{path}: every list of training_schedule needs one entry per stage")
+    if any(sched.get("train_tx", ())):
+        raise ValueError(f"{path}: train_tx = True (a trainable transmitter) is not supported; only the receiver "
+                         f"is trained")
+    max_tx = int(ast.literal_eval(sec["max_num_tx"]))
+    min_tx = int(ast.literal_eval(sec.get("min_num_tx", str(max_tx))))
+    if not 1 <= min_tx <= max_tx:
+        raise ValueError(f"{path}: need 1 <= min_num_tx <= max_num_tx, got {min_tx}, {max_tx}")
+    stages = []
+    for i in range(n):
+        lo = tuple(float(x) for x in sched["min_training_snr_db"][i])
+        hi = tuple(float(x) for x in sched["max_training_snr_db"][i])
+        if len(lo) != max_tx - min_tx + 1 or len(hi) != len(lo) or any(b < a for a, b in zip(lo, hi)):
+            raise ValueError(f"{path}: stage {i} needs one SNR range (min <= max) per number of active users "
+                             f"{min_tx}..{max_tx}")
+        num_iter = int(sched["num_iter"][i])
+        if num_iter != sched["num_iter"][i] or num_iter < 0 or int(sched["batch_size"][i]) < 1:
+            raise ValueError(f"{path}: stage {i}: num_iter must be a whole number >= 0 and batch_size >= 1")
+        stages.append(ScheduleStage(
+            num_iter=num_iter, learning_rate=float(sched["learning_rate"][i]), batch_size=int(sched["batch_size"][i]),
+            min_training_snr_db=lo, max_training_snr_db=hi, double_readout=bool(sched["double_readout"][i]),
+            apply_multiloss=bool(sched["apply_multiloss"][i]),
+            weighting_double_readout=float(sched["weighting_double_readout"][i])))
+    return TrainingSchedule(stages=tuple(stages), min_num_tx=min_tx, max_num_tx=max_tx)

@@ -922,8 +922,17 @@ int nrx_generate_slots_tc(const nrx_gen_desc* desc, const nrx_gen_chan* chan, co
                           const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
                           const nrx_gen_tc* tc, const nrx_gen_out* out, void* workspace, size_t workspace_bytes,
                           void* stream) {
+  return nrx_generate_slots_no(desc, chan, cfo, dmrs, cir, td, tc, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+int nrx_generate_slots_no(const nrx_gen_desc* desc, const nrx_gen_chan* chan, const nrx_gen_cfo* cfo,
+                          const nrx_gen_dmrs* dmrs, const nrx_gen_cir* cir, const nrx_gen_td* td,
+                          const nrx_gen_tc* tc, const nrx_gen_noise* noise, const nrx_gen_out* out, void* workspace,
+                          size_t workspace_bytes, void* stream) {
   GenPlan p{};
   if (int rc = plan_gen(desc, chan, cfo, dmrs, cir, td, tc, &p)) return rc;
+  p.no_slot = noise ? noise->no_slot : nullptr;
+  if ((uintptr_t)p.no_slot & 7) return fail(NRX_ERR_INVALID_ARG, "no_slot must be 8-byte aligned");
   if (!out || !out->y) return fail(NRX_ERR_INVALID_ARG, "null tensor pointer");
   if (out->bits)
     if (int rc = check_bits_stride(out->bits_stride, desc->mcs_bits, desc->num_mcs)) return rc;
@@ -1389,9 +1398,21 @@ int nrx_train_workspace_size(const nrx_desc* desc, const nrx_train_io* io, size_
 
 int nrx_train_grad(const nrx_desc* desc, const nrx_train_io* io, void* workspace, size_t workspace_bytes,
                    void* stream) {
+  return nrx_train_grad_acc(desc, io, nullptr, workspace, workspace_bytes, stream);
+}
+
+int nrx_train_grad_acc(const nrx_desc* desc, const nrx_train_io* io, const nrx_train_acc* acc, void* workspace,
+                       size_t workspace_bytes, void* stream) {
   if (int rc = check_train(desc, io)) return rc;
+  if (acc) {
+    if (int rc = check_range("accumulate", acc->accumulate, 0, 1, NRX_ERR_INVALID_ARG)) return rc;
+    if (acc->batch_total < io->shape.batch || acc->batch_total > 65535)
+      return fail(NRX_ERR_SHAPE, "batch_total must be shape.batch..65535");
+  }
   if (int rc = check_workspace(workspace, workspace_bytes, train_workspace_bytes(*desc, *io), 256)) return rc;
-  return launched(launch_train_grad(*desc, *io, workspace, (hipStream_t)stream), "training launch");
+  return launched(launch_train_grad(*desc, *io, acc && acc->accumulate, acc ? acc->batch_total : io->shape.batch,
+                                    workspace, (hipStream_t)stream),
+                  "training launch");
 }
 
 int nrx_adam_step(const nrx_adam_io* io, void* stream) {

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(64) void k_cir_scale(CirWs w, int64_t nbu, int npar
 
 // block = FB subcarriers x (A * T) threads; grid = (ceil(F / FB), B): k_gen_rx on the replayed channel
 __global__ __launch_bounds__(256) void k_cir_rx(nrx_gen_desc d, CirWs w, int normalize, const double2* __restrict__ x,
-                                                int FB, float* __restrict__ y, float* __restrict__ h,
+                                                const double* __restrict__ no_slot, int FB, float* __restrict__ y, float* __restrict__ h,
                                                 float* __restrict__ y_re, float* __restrict__ y_im) {
   const int U = d.num_tx, A = d.num_rx_ant, F = d.num_subcarriers, T = d.num_symbols;
   const int b = blockIdx.y;
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void k_cir_rx(nrx_gen_desc d, CirWs w, int nor
   }
   const U4 r = draw(d, b, ST_NOISE, (uint32_t)((a * F + f) * T + t));
   const double2 z = box_muller(r.x, r.y);
-  const double sd = sqrt(d.no / 2.0);
+  const double sd = sqrt((no_slot ? no_slot[b] : d.no) / 2.0);
   yr += sd * z.x;
   yi += sd * z.y;
   const size_t ft = ((size_t)b * F + f) * T + t;
@@ -264,8 +264,8 @@ __global__ __launch_bounds__(256) void k_cir_rx(nrx_gen_desc d, CirWs w, int nor
 
 size_t cir_workspace_bytes(const nrx_gen_desc& d) { return cir_ws(d, nullptr, nullptr); }
 
-hipError_t launch_cir_rx(const nrx_gen_desc& d, const nrx_gen_cir& c, const double* x, void* ws, float* y, float* h,
-                         float* y_re, float* y_im, hipStream_t st) {
+hipError_t launch_cir_rx(const nrx_gen_desc& d, const nrx_gen_cir& c, const double* x, void* ws,
+                         const double* no_slot, float* y, float* h, float* y_re, float* y_im, hipStream_t st) {
   CirWs w;
   cir_ws(d, &w, ws);
   const int F = d.num_subcarriers, A = d.num_rx_ant;
@@ -280,7 +280,7 @@ hipError_t launch_cir_rx(const nrx_gen_desc& d, const nrx_gen_cir& c, const doub
   int FB = 256 / at;
   if (FB > 4) FB = 4;
   k_cir_rx<<<dim3((unsigned)((F + FB - 1) / FB), (unsigned)d.batch), FB * at, 0, st>>>(
-      d, w, c.normalize, reinterpret_cast<const double2*>(x), FB, y, h, y_re, y_im);
+      d, w, c.normalize, reinterpret_cast<const double2*>(x), no_slot, FB, y, h, y_re, y_im);
   return hipGetLastError();
 }
 

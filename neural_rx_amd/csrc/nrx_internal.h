@@ -239,6 +239,7 @@ struct GenPlan {
   const nrx_gen_cir* cir;
   const nrx_gen_td* td;
   const nrx_gen_tc* tc;
+  const double* no_slot;             // device [B] noise variance per slot (nrx_generate_slots_no), or null: d.no
   // byte offsets: behind the generator's own block at 0 the block of the one sample-domain stage (the x' of a
   // cfo, the x' and samples of a td, the buffers of a tc), the pilot table and the replayed channel
   size_t stage, pilots, cir_ws, total;
@@ -256,8 +257,8 @@ hipError_t launch_export_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, floa
 // Channel impulse response replay (nrx_cir.hip); cir validated by nrx_generate_slots_cir.  x: [B][U][F][14]
 // complex f64, the grid the channel acts on; ws: cir_workspace_bytes of the caller's workspace
 size_t cir_workspace_bytes(const nrx_gen_desc& d);
-hipError_t launch_cir_rx(const nrx_gen_desc& d, const nrx_gen_cir& c, const double* x, void* ws, float* y, float* h,
-                         float* y_re, float* y_im, hipStream_t st);
+hipError_t launch_cir_rx(const nrx_gen_desc& d, const nrx_gen_cir& c, const double* x, void* ws,
+                         const double* no_slot, float* y, float* h, float* y_re, float* y_im, hipStream_t st);
 
 // Despreading LS estimator (nrx_ls.hip); io validated by nrx_ls_estimate / nrx_generate_slots_dmrs
 hipError_t launch_ls_estimate(const nrx_ls_io& io, hipStream_t st);
@@ -310,8 +311,8 @@ size_t tc_workspace_bytes(const nrx_gen_desc& d, const nrx_gen_tc& tc);
 hipError_t launch_tc_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_tc& tc, const double* tau,
                           const double* spdp, double* gt, void* ws, hipStream_t st);
 hipError_t launch_tc_rx(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_tc& tc, const double* x,
-                        const double* tau, const double* gt, void* ws, float* y, float* h, float* y_re, float* y_im,
-                        hipStream_t st);
+                        const double* tau, const double* gt, void* ws, const double* no_slot, float* y, float* h,
+                        float* y_re, float* y_im, hipStream_t st);
 
 // LMMSE + max-log baseline detector (nrx_lmmse.hip); io validated by nrx_lmmse_detect
 hipError_t launch_lmmse(const nrx_lmmse_io& io, hipStream_t st);
@@ -359,7 +360,9 @@ hipError_t launch_ldpc_count(const nrx_ldpc_count_io& io, hipStream_t st);
 // Training (nrx_train.hip); desc and io validated by the nrx_train_* / nrx_adam_step entry points.  c1, c2: the
 // bias corrections 1 - beta^step
 size_t train_workspace_bytes(const nrx_desc& d, const nrx_train_io& io);
-hipError_t launch_train_grad(const nrx_desc& d, const nrx_train_io& io, void* ws, hipStream_t st);
+// accumulate: grad and loss are added onto, not overwritten; batch_total: the B of every loss denominator
+hipError_t launch_train_grad(const nrx_desc& d, const nrx_train_io& io, bool accumulate, int batch_total, void* ws,
+                             hipStream_t st);
 hipError_t launch_adam(const nrx_adam_io& io, double c1, double c2, hipStream_t st);
 
 hipError_t launch_llr_demap(const float* llr, int B, int U, int F, int T, int bits_stride, int bits,

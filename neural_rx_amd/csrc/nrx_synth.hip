@@ -278,7 +278,8 @@ __global__ __launch_bounds__(256) void k_gen_tx(nrx_gen_desc d, GenWs w, uint8_t
 }
 
 // block = FB subcarriers x (A * T) threads; grid = (ceil(F / FB), B)
-__global__ __launch_bounds__(256) void k_gen_rx(nrx_gen_desc d, GenWs w, int FB, float* __restrict__ y,
+__global__ __launch_bounds__(256) void k_gen_rx(nrx_gen_desc d, GenWs w, const double* __restrict__ no_slot, int FB,
+                                                float* __restrict__ y,
                                                 float* __restrict__ h, float* __restrict__ y_re,
                                                 float* __restrict__ y_im) {
   __shared__ double2 e[4][kMaxUsers * 8];   // phasor of (u, l) at the block's subcarriers
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(256) void k_gen_rx(nrx_gen_desc d, GenWs w, int FB,
   }
   const U4 r = draw(d, b, ST_NOISE, (uint32_t)((a * F + f) * T + t));
   const double2 z = box_muller(r.x, r.y);
-  const double sd = sqrt(d.no / 2.0);
+  const double sd = sqrt((no_slot ? no_slot[b] : d.no) / 2.0);
   yr += sd * z.x;
   yi += sd * z.y;
   const size_t ft = ((size_t)b * F + f) * T + t;
@@ -669,15 +670,16 @@ hipError_t launch_generate(const GenPlan& p, const nrx_gen_out& o, void* ws, hip
   }
   if (p.tc) {
     if (hipError_t e = launch_tc_rx(d, c, *p.tc, reinterpret_cast<const double*>(w.x), w.tau,
-                                    reinterpret_cast<const double*>(w.gt), stage, o.y, o.h, o.y_real, o.y_imag, st))
+                                    reinterpret_cast<const double*>(w.gt), stage, p.no_slot, o.y, o.h, o.y_real, o.y_imag,
+                                    st))
       return e;
   } else if (p.cir) {
-    if (hipError_t e = launch_cir_rx(d, *p.cir, reinterpret_cast<const double*>(wr.x), (char*)ws + p.cir_ws, o.y, o.h,
-                                     o.y_real, o.y_imag, st))
+    if (hipError_t e = launch_cir_rx(d, *p.cir, reinterpret_cast<const double*>(wr.x), (char*)ws + p.cir_ws, p.no_slot,
+                                     o.y, o.h, o.y_real, o.y_imag, st))
       return e;
   } else {
-    k_gen_rx<<<dim3((unsigned)((F + FB - 1) / FB), (unsigned)B), FB * at, 0, st>>>(d, wr, FB, o.y, o.h, o.y_real,
-                                                                                   o.y_imag);
+    k_gen_rx<<<dim3((unsigned)((F + FB - 1) / FB), (unsigned)B), FB * at, 0, st>>>(d, wr, p.no_slot, FB, o.y, o.h,
+                                                                                   o.y_real, o.y_imag);
   }
   if (cfo && cfo->h_with_phase && o.h)
     if (hipError_t e = launch_cfo_h_phase(d, *cfo, o.h, st)) return e;

@@ -302,7 +302,8 @@ __global__ __launch_bounds__(256) void k_tc_h(nrx_gen_desc d, TcGen tg, int FB, 
 
 // y = the demodulated antenna grids yg [B][A][F][14] + the generator's grid noise (the draws of k_gen_rx);
 // one thread per (b, f, t, a)
-__global__ __launch_bounds__(256) void k_tc_y(nrx_gen_desc d, const double2* __restrict__ yg, float* __restrict__ y,
+__global__ __launch_bounds__(256) void k_tc_y(nrx_gen_desc d, const double2* __restrict__ yg,
+                                              const double* __restrict__ no_slot, float* __restrict__ y,
                                               float* __restrict__ y_re, float* __restrict__ y_im) {
   const int A = d.num_rx_ant, F = d.num_subcarriers, T = kT;
   const int64_t n = (int64_t)d.batch * F * T * A;
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(256) void k_tc_y(nrx_gen_desc d, const double2* __r
   const double2 g = yg[(((size_t)b * A + a) * F + f) * T + t];
   const U4 r = draw(d, b, ST_NOISE, (uint32_t)((a * F + f) * T + t));
   const double2 z = box_muller(r.x, r.y);
-  const double sd = sqrt(d.no / 2.0);
+  const double sd = sqrt((no_slot ? no_slot[b] : d.no) / 2.0);
   const float yr = (float)(g.x + sd * z.x), yi = (float)(g.y + sd * z.y);
   y[ft * 2 * A + a] = yr;
   y[ft * 2 * A + A + a] = yi;
@@ -399,8 +400,8 @@ hipError_t launch_tc_taps(const nrx_gen_desc& d, const nrx_gen_chan& c, const nr
 }
 
 hipError_t launch_tc_rx(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_gen_tc& tc, const double* x,
-                        const double* tau, const double* gt, void* ws, float* y, float* h, float* y_re, float* y_im,
-                        hipStream_t st) {
+                        const double* tau, const double* gt, void* ws, const double* no_slot, float* y, float* h,
+                        float* y_re, float* y_im, hipStream_t st) {
   TcWs w;
   tc_layout(d, tc, &w, ws);
   const TcGen g = tc_gen(d, c, tc);
@@ -415,7 +416,7 @@ hipError_t launch_tc_rx(const nrx_gen_desc& d, const nrx_gen_chan& c, const nrx_
   nrx_ofdm_io demod = stage_ofdm(d, tc, (int)A, w.yg, w.r);
   demod.timing_advance = tc.timing_advance;
   if (hipError_t e = launch_ofdm(demod, /*modulate=*/false, st)) return e;
-  k_tc_y<<<(unsigned)((B * F * kT * A + 255) / 256), 256, 0, st>>>(d, w.yg, y, y_re, y_im);
+  k_tc_y<<<(unsigned)((B * F * kT * A + 255) / 256), 256, 0, st>>>(d, w.yg, no_slot, y, y_re, y_im);
   if (h) {
     const int at = (int)(A * kT);
     int FB = 256 / at;

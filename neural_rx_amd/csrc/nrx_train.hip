@@ -168,7 +168,8 @@ __global__ __launch_bounds__(kTB) void k_wgrad(WgradArgs g) {
   }
 }
 
-// grad[e] += sum over the S slabs, in slab order, in f64 (grad was zeroed at the start of the call)
+// grad[e] += sum over the S slabs, in slab order, in f64 (grad was zeroed at the start of the call, or holds
+// the sum of the calls before this one when the call accumulates)
 __global__ void k_slab_sum(const float* slab, int S, int n, float* grad) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
@@ -387,18 +388,19 @@ __global__ __launch_bounds__(kTB) void k_loss_chest(const float* href, const flo
 }
 
 // loss[0] = the nd data launches' partials, loss[1] = the nc chest launches', each column of launches summed in
-// launch order, then the fixed tree
-__global__ __launch_bounds__(kTB) void k_loss_sum(const double* pd, int nd, const double* pc, int nc, double* loss) {
+// launch order, then the fixed tree; with `accumulate` the two sums are added onto what loss holds
+__global__ __launch_bounds__(kTB) void k_loss_sum(const double* pd, int nd, const double* pc, int nc, int accumulate,
+                                                   double* loss) {
   __shared__ double sh[kTB];
   double s = 0.0;
   for (int i = 0; i < nd; ++i) s += pd[(size_t)i * kLossBlocks + threadIdx.x];
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) loss[0] = s;
+  if (threadIdx.x == 0) loss[0] = accumulate ? loss[0] + s : s;
   __syncthreads();
   s = 0.0;
   for (int i = 0; i < nc; ++i) s += pc[(size_t)i * kLossBlocks + threadIdx.x];
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) loss[1] = s;
+  if (threadIdx.x == 0) loss[1] = accumulate ? loss[1] + s : s;
 }
 
 // ---------------------------------------------------------------- Adam
@@ -603,12 +605,17 @@ size_t train_workspace_bytes(const nrx_desc& d, const nrx_train_io& io) {
   return p.bytes;
 }
 
-hipError_t launch_train_grad(const nrx_desc& d, const nrx_train_io& io, void* ws, hipStream_t st) {
+// The loss denominators carry batch_total, the B of the whole step, in place of this call's B: every term of a
+// micro-batch then has the weight it has in the whole batch, and the sum over the calls is the step's loss and
+// gradient with nothing to rescale.  An accumulating call skips the memset and adds its loss in f64; the slab
+// sums add onto grad in their fixed order either way.
+hipError_t launch_train_grad(const nrx_desc& d, const nrx_train_io& io, bool accumulate, int batch_total, void* ws,
+                             hipStream_t st) {
   Plan p;
   make_plan(d, io, ws, &p);
   Run run{p, io, st};
   const int P = p.P;
-  run.err = hipMemsetAsync(io.grad, 0, p.num_weights * sizeof(float), st);
+  if (!accumulate) run.err = hipMemsetAsync(io.grad, 0, p.num_weights * sizeof(float), st);
   if (!run.ok()) return run.err;
 
   // ---- forward
@@ -636,7 +643,7 @@ hipError_t launch_train_grad(const nrx_desc& d, const nrx_train_io& io, void* ws
       g.m_lo = d.var_mcs_masking ? 0 : h, g.m_hi = d.var_mcs_masking ? p.M : h + 1;
       for (int m = 0; m < p.M; ++m) {
         g.bits_m[m] = d.bits[m];
-        g.inv_den[m] = 1.0 / ((double)p.B * p.U * p.F * n_data * d.bits[m]);
+        g.inv_den[m] = 1.0 / ((double)batch_total * p.U * p.F * n_data * d.bits[m]);
       }
       g.dmrs_mask = io.dmrs_symbol_mask, g.hb = p.hb[h], g.FT = p.FT, g.P = P;
       g.dllr = p.ro[r].dllr[h], g.part = p.part_d + (size_t)nd++ * kLossBlocks;
@@ -644,7 +651,8 @@ hipError_t launch_train_grad(const nrx_desc& d, const nrx_train_io& io, void* ws
     }
     if (io.h)
       k_loss_chest<<<kLossBlocks, kTB, 0, st>>>(p.ro[r].href, io.h, io.active, p.FT, p.A2, P,
-                                                1.0 / ((double)P * p.A2), io.w_chest, p.ro[r].dh,
+                                                1.0 / ((double)batch_total * p.U * p.FT * p.A2), io.w_chest,
+                                                p.ro[r].dh,
                                                 p.part_c + (size_t)nc++ * kLossBlocks);
   };
   for (int i = 0; i < p.I; ++i) {
@@ -657,7 +665,7 @@ hipError_t launch_train_grad(const nrx_desc& d, const nrx_train_io& io, void* ws
     if (io.multiloss || i == p.I - 1) readout(io.multiloss ? i : 0, p.state[i + 1]);
   }
   if (!run.ok()) return run.err;
-  k_loss_sum<<<1, kTB, 0, st>>>(p.part_d, nd, p.part_c, nc, io.loss);
+  k_loss_sum<<<1, kTB, 0, st>>>(p.part_d, nd, p.part_c, nc, accumulate, io.loss);
   const Plan::Readout& last = p.ro[p.R - 1];
   if (io.llr) {
     const int bm = bits_max(&d);

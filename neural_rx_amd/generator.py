@@ -440,16 +440,23 @@ class SlotGenerator:
         self._bufs = {key: sb}
         return sb
 
-    def __call__(self, batch: int, no: float, slot_offset: int = 0, stream=None, out: Optional[SlotBatch] = None,
+    def __call__(self, batch: int, no, slot_offset: int = 0, stream=None, out: Optional[SlotBatch] = None,
                  workspace=None, cir_index=None) -> SlotBatch:
-        """``workspace``: a uint8 device tensor of at least ``workspace_bytes(batch)`` bytes, any
+        """``no``: the noise variance per complex resource element, one float for the batch or a float64
+        device tensor ``[batch]`` with one value per slot (finite and >= 0: the host never reads it), which
+        goes through ``nrx_generate_slots_no``.  ``workspace``: a uint8 device tensor of at least ``workspace_bytes(batch)`` bytes, any
         content, to run this call in instead of the generator's own.  ``cir_index``: the examples
         ``[batch, U]`` int32 (device) of a ``CIRChannel(select="index")``."""
         torch = _torch()
         sb = out if out is not None else self._alloc(batch)
         nbytes = self.workspace_bytes(batch) if workspace is None else 0      # the C call sizes a caller's
         ws = self._ws.get(nbytes, f"cuda:{self.device}", workspace)
-        d = self.p.desc(batch, no, slot_offset)
+        noise = None
+        if hasattr(no, "data_ptr"):
+            require("no", no, (batch,), torch.float64, sb.y.device)
+            noise = _lib.nrx_gen_noise()
+            noise.no_slot = no.data_ptr()
+        d = self.p.desc(batch, 0.0 if noise is not None else no, slot_offset)
         o = _lib.nrx_gen_out()
         o.y, o.h_hat, o.h, o.active = ptr(sb.y), ptr(sb.h_hat), ptr(sb.h), ptr(sb.active)
         o.mcs_mask, o.mcs, o.bits, o.bits_stride = ptr(sb.mcs_mask), ptr(sb.mcs), ptr(sb.bits), self.p.bits_max
@@ -470,9 +477,12 @@ class SlotGenerator:
             self._tc.r_out = ptr(sb.r_tc)
         # one entry point: the older nrx_generate_slots* are this call with NULL for the blocks they lack.
         # A dataset is the channel, so chan stays NULL with it (GenParams refuses the two together).
-        _lib.check(self._lib.nrx_generate_slots_tc(
-            ref(d), ref(self._chan), ref(self._cfo), ref(self._dmrs), ref(self._cir), ref(self._td), ref(self._tc),
-            ref(o), ws.data_ptr(), ws.numel(), stream_of(sb.y, stream)))
+        blocks = (ref(d), ref(self._chan), ref(self._cfo), ref(self._dmrs), ref(self._cir), ref(self._td), ref(self._tc))
+        run = (ref(o), ws.data_ptr(), ws.numel(), stream_of(sb.y, stream))
+        if noise is None:
+            _lib.check(self._lib.nrx_generate_slots_tc(*blocks, *run))
+        else:
+            _lib.check(self._lib.nrx_generate_slots_no(*blocks, ref(noise), *run))
         return sb
 
     def export_taps(self, batch: int, slot_offset: int = 0, stream=None) -> CIRDataset:
