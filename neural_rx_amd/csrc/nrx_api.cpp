@@ -258,7 +258,8 @@ struct nrx_handle {
   hipStream_t last_stream = nullptr;
   bool have_last = false;
   FusedCtl fused_ctl() const { return FusedCtl{fused_sync, spin_limit, dbg_err}; }
-  Sched sched() const { return Sched{update_rr, fused_enabled}; }
+  int small_tiers = 1;      // nrx_debug_small_tiers (tests)
+  Sched sched() const { return Sched{update_rr, fused_enabled, small_tiers}; }
 };
 
 // The forward workspace: the slot norms, four state / aggregate planes [B][U][F][14][56] of the storage type
@@ -1475,13 +1476,24 @@ int nrx_update_schedule(nrx_handle* h, int32_t update_rr) {
   return NRX_OK;
 }
 
+// Tests only (not in include/nrx.h): the small-grid strip tiers (8 / 16-row strips) off or on for this handle, so that
+// a test can run the 24-row tier's kernels -- the column launches among them -- on a handful of slots.  enable < 0
+// leaves the setting.  Every tier computes the same bits.
+int nrx_debug_small_tiers(nrx_handle* h, int32_t enable) {
+  if (!h) return fail(NRX_ERR_INVALID_ARG, "null argument");
+  if (enable >= 0) h->small_tiers = enable != 0;
+  return NRX_OK;
+}
+
 // The launch plan of a forward, without a handle (tests only, like nrx_probe_buffer_oob: not in include/nrx.h): the
 // checks, the chunking and the plan_forward of nrx_forward, at cus / xccs (cus == 0: the current device's; else no
 // HIP call).  Into out[cap], 16 int32 per chunk (b0, n, -1, FwdPlan's 11 fields up to nq, one_launch, combine launches)
-// and per stage s (b0, n, s, StagePlan's 11 fields, 0, 0).  Returns the int32 count of the whole plan or an error code.
-int nrx_debug_forward_plan(const nrx_desc* desc, const nrx_shape* shape, int32_t precision, int32_t num_it,
-                           int32_t sched_mask, int32_t fused_mode, int32_t cus, int32_t xccs, int32_t* out,
-                           int32_t cap) {
+// and per stage s (b0, n, s, StagePlan's 11 fields up to order_rev, its variant, 0).  Returns the int32 count of the whole plan or an error code.
+// nrx_debug_forward_plan_io: the same for a caller that hands the optional tensors named by io_flags (1: h_ref, 2: an
+// MCS mask), which the plan of the column launches looks at (StagePlan::variant).
+static int debug_forward_plan(const nrx_desc* desc, const nrx_shape* shape, int32_t precision, int32_t num_it,
+                              int32_t sched_mask, int32_t fused_mode, int32_t cus, int32_t xccs, int32_t io_flags,
+                              int32_t* out, int32_t cap) {
   if (int rc = check_desc(desc)) return rc;
   if (int rc = check_shape(shape)) return rc;
   if (precision != NRX_PREC_F16 && precision != NRX_PREC_F32X) return fail(NRX_ERR_INVALID_ARG, "unknown precision");
@@ -1489,8 +1501,10 @@ int nrx_debug_forward_plan(const nrx_desc* desc, const nrx_shape* shape, int32_t
   if (sched_mask < 0 || sched_mask > kSchedMax || fused_mode < 0 || fused_mode > 2 || cus < 0 || (!out && cap > 0))
     return fail(NRX_ERR_INVALID_ARG, "bad schedule, device counts or output");
   if (cus == 0) device_counts(&cus, &xccs);
-  const nrx_io io{*shape, num_it, precision};
+  nrx_io io{*shape, num_it, precision};
   void* ws = reinterpret_cast<void*>(uintptr_t(256));   // a dummy base: pe16 non-null, nothing is dereferenced
+  if (io_flags & 1) io.h_ref = reinterpret_cast<float*>(ws);
+  if (io_flags & 2) io.mcs_mask = reinterpret_cast<const float*>(ws);
   int n_out = 0;
   auto put = [&](int b0, int n, int s, const void* plan, int x, int y) {
     int rec[16] = {b0, n, s};
@@ -1499,7 +1513,9 @@ int nrx_debug_forward_plan(const nrx_desc* desc, const nrx_shape* shape, int32_t
     for (int k = 0; k < 16; ++k, ++n_out)
       if (n_out < cap) out[n_out] = rec[k];
   };
-  static_assert(offsetof(FwdPlan, st) == 11 * sizeof(int) && sizeof(StagePlan) == 11 * sizeof(int), "record layout");
+  static_assert(offsetof(FwdPlan, st) == 11 * sizeof(int) && offsetof(StagePlan, variant) == 11 * sizeof(int) &&
+                    sizeof(StagePlan) == 12 * sizeof(int),
+                "record layout");
   (void)each_chunk(shape, precision, [&](int b0, int n) {
     FwdPlan pl;
     if (precision == NRX_PREC_F16) {
@@ -1513,10 +1529,23 @@ int nrx_debug_forward_plan(const nrx_desc* desc, const nrx_shape* shape, int32_t
       pl = plan_forward(a, num_it);
     }
     put(b0, n, -1, &pl, pl.one_launch(), pl.combine_launches());
-    for (int s = 0; s < pl.num_init + pl.num_it; ++s) put(b0, n, s, &pl.st[s], 0, 0);
+    for (int s = 0; s < pl.num_init + pl.num_it; ++s) put(b0, n, s, &pl.st[s], pl.st[s].variant, 0);
     return 0;
   });
   return n_out;
+}
+
+int nrx_debug_forward_plan(const nrx_desc* desc, const nrx_shape* shape, int32_t precision, int32_t num_it,
+                           int32_t sched_mask, int32_t fused_mode, int32_t cus, int32_t xccs, int32_t* out,
+                           int32_t cap) {
+  return debug_forward_plan(desc, shape, precision, num_it, sched_mask, fused_mode, cus, xccs, 0, out, cap);
+}
+
+int nrx_debug_forward_plan_io(const nrx_desc* desc, const nrx_shape* shape, int32_t precision, int32_t num_it,
+                              int32_t sched_mask, int32_t fused_mode, int32_t cus, int32_t xccs, int32_t io_flags,
+                              int32_t* out, int32_t cap) {
+  if (io_flags < 0 || io_flags > 3) return fail(NRX_ERR_INVALID_ARG, "io_flags: 1 h_ref, 2 mcs_mask");
+  return debug_forward_plan(desc, shape, precision, num_it, sched_mask, fused_mode, cus, xccs, io_flags, out, cap);
 }
 
 int nrx_profile_read(nrx_handle* h, int32_t kernel, int64_t* launches, double* total_ms) {

@@ -336,14 +336,14 @@ struct ColStage {
 // TAIL_AGG: conv3's epilogue writes s' and act*sp.  TAIL_READOUT_WB: once every wave is past
 // conv2 the heads are staged over the conv1 / conv2 images (dead for this item; restaged by the
 // caller before a next item), and conv3's epilogue runs the readouts.
-template <int CHP, int TAILM, bool FIRST = false>
+template <int CHP, int TAILM, bool FIRST = false, class LT = ColGeneric>
 __device__ __forceinline__ void col_upd_item(const BlockParams<P16>& prm, char* smem, int wave, int b, int u, int strip,
                                              int k, ColStage<kUPD_CINP, TAILM>* stage = nullptr) {
   constexpr int PR = 2;
   col_ts(k, 0);
   const int lane = nrx_tid() & 63, t = lane & 15, g = lane >> 4;
   const int p0 = kColRO * wave;
-  const int strips = prm.strips;
+  const int strips = prm.strips;   // (lean: 1, read all the same -- as a constant it cost 10 VGPRs of spills)
   const int f_start = col_fstart(strip, strips);
   const int F = prm.a.F;
   const int f_own0 = f_start + p0;
@@ -397,7 +397,7 @@ __device__ __forceinline__ void col_upd_item(const BlockParams<P16>& prm, char* 
   }
   __syncthreads();
   col_ts(k, 4);
-  EpiConv3<P16, WS3, CHP, TAILM> epi{&prm, nullptr, WB, w3, b, u, f_start, col_pos_hi(strips), 0, 1.f, false,
+  EpiConv3<P16, WS3, CHP, TAILM, LT> epi{&prm, nullptr, WB, w3, b, u, f_start, col_pos_hi(strips), 0, 1.f, false,
                                      (float)prm.a.active[(size_t)b * prm.a.U + u], -1, 0, 0};
   epi.pos_lo = col_pos_lo(strips);
   if constexpr (TAILM == TAIL_READOUT_WB) col_conv3_ro<NRX_COL_PR3>(own, nb, epi, lane, t, g, p0);
@@ -411,7 +411,7 @@ __device__ __forceinline__ void col_upd_item(const BlockParams<P16>& prm, char* 
 // loops over several.  The loop's code kept thread-derived addresses live across the first item
 // and cost that item 22 (readout) / 4 (aggregation) VGPRs of spills; without it the single-item
 // kernel spills 4 / 1.
-template <int CHP, int TAILM, bool MULTI>
+template <int CHP, int TAILM, bool MULTI, class LT = ColGeneric>
 __device__ __forceinline__ void col_update_stage(const BlockParams<P16>& prm, int items) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   rr_ts(0, 7);
@@ -423,7 +423,7 @@ __device__ __forceinline__ void col_update_stage(const BlockParams<P16>& prm, in
     stage.load_w1(prm);
     int b, u, strip;
     work_item(blockIdx.x, prm.a.B, prm.a.U, prm.strips, prm.order_rev, b, u, strip);
-    col_upd_item<CHP, TAILM, true>(prm, smem, wave, b, u, strip, k, &stage);   // grid <= items
+    col_upd_item<CHP, TAILM, true, LT>(prm, smem, wave, b, u, strip, k, &stage);   // grid <= items
   }
   if constexpr (MULTI) {
     for (int i = blockIdx.x; i < items; i += gridDim.x, ++k) {
@@ -450,9 +450,9 @@ __device__ __forceinline__ void col_update_stage(const BlockParams<P16>& prm, in
   rr_ts_edge(1);
 }
 
-template <int CHP, int TAILM>
+template <int CHP, int TAILM, class LT = ColGeneric>
 __global__ __launch_bounds__(512) void k_update_col(BlockParams<P16> prm, int items) {
-  col_update_stage<CHP, TAILM, false>(prm, items);
+  col_update_stage<CHP, TAILM, false, LT>(prm, items);
 }
 template <int CHP, int TAILM>
 __global__ __launch_bounds__(512) void k_update_col_multi(BlockParams<P16> prm, int items) {
@@ -494,50 +494,103 @@ __device__ __forceinline__ half8 col_init_z(const ColInitRow& r, float ns, bool 
   return o;
 }
 
+// Lean variants (ColLean: one strip, a model with h_hat, 2A = 8): each lane picks its source plane once -- y
+// (g != 1) or h_hat (g = 1) of its slot (and user), a 64-bit base -- and a row adds one unsigned 32-bit offset; pe
+// goes through a wave-uniform plane base.  Same clamping as col_init_load.
+struct ColInitLane {
+  const char* src;
+  const char* pe;
+};
+__device__ __forceinline__ ColInitLane col_init_lane(const FwdArgs<_Float16, float, _Float16>& a, int b, int u, int g) {
+  const size_t plane = (size_t)a.F * kT * 8;
+  const float* y = a.y + (size_t)b * plane;
+  const float* h = a.h_hat + ((size_t)b * a.U + u) * plane;
+  return ColInitLane{reinterpret_cast<const char*>(g == 1 ? h : y),
+                     reinterpret_cast<const char*>(a.pe + (size_t)u * a.F * kT * 2)};
+}
+__device__ __forceinline__ ColInitRow col_init_load_lean(const ColInitLane& ln, int F, int f, int t) {
+  const bool ok = f >= 0 && f < F && t < kT;
+  const unsigned re = (unsigned)((ok ? f : 0) * kT + (ok ? t : 0));
+  ColInitRow r;
+  r.v0 = *reinterpret_cast<const floatx4*>(ln.src + re * 32u);
+  r.v1 = *reinterpret_cast<const floatx4*>(ln.src + re * 32u + 16u);
+  r.pe = *reinterpret_cast<const float2*>(ln.pe + re * 8u);
+  return r;
+}
+// col_init_z with the source picked per lane group: sc = ns for the y / h_hat lanes (g < 2) and 1 for the pe lanes
+// (g = 2: pe * 1 = pe), whose two pe values replace the lane's first two elements; the eight elements are converted
+// without selects and the four packed words masked (word 0: g < 3, words 1..3: g < 2; none outside the grid).  The
+// values are col_init_z's: f32_rounded(y * ns) -> f16, pe -> f16, zero elsewhere.
+__device__ __forceinline__ half8 col_init_z_lean(const ColInitRow& r, float sc, bool ok, int g) {
+  float v[8] = {r.v0[0], r.v0[1], r.v0[2], r.v0[3], r.v1[0], r.v1[1], r.v1[2], r.v1[3]};
+  if (g == 2) v[0] = r.pe.x, v[1] = r.pe.y;
+  half8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = (_Float16)f32_rounded(v[e] * sc);
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 w = __builtin_bit_cast(u32x4, o);
+  const bool k0 = ok && g < 3, k1 = ok && g < 2;
+  w[0] = k0 ? w[0] : 0u;
+#pragma unroll
+  for (int i = 1; i < 4; ++i) w[i] = k1 ? w[i] : 0u;
+  return __builtin_bit_cast(half8, w);
+}
+
 // One item (slot b, user u, strip) of StateInit m = prm.m on the calling wave (A2P = 8): the state
 // is the sum over the launches m of wm * SI_m(z) (Var-IO), and the last launch's TAIL_AGG stores
 // act * sp of iteration 0.
-template <int TAILM, bool FIRST = false>
+template <int TAILM, bool FIRST = false, class LT = ColGeneric>
 __device__ __forceinline__ void col_init_item(const BlockParams<P16>& prm, char* smem, int wave, int b, int u,
                                               int strip, int k, ColStage<32, TAILM>* stage = nullptr) {
   constexpr int PR = 2;
+  constexpr bool LEAN = LT::kLean;
   col_ts(k, 0);
   const auto& a = prm.a;
   const int lane = nrx_tid() & 63, t = lane & 15, g = lane >> 4;
   const int p0 = kColRO * wave;
-  const int strips = prm.strips;
+  const int strips = LEAN ? 1 : prm.strips;
   const int f_start = col_fstart(strip, strips);
-  const int F = a.F, A2 = 2 * a.A;
+  const int F = a.F, A2 = LEAN ? 8 : 2 * a.A;
+  const bool norm_pre = LEAN ? false : prm.norm_pre != 0;
   const int f_own0 = f_start + p0;
   const RrNb nb = rr_nb(smem, wave, t, g);
   // the slot norm's y loads and the wave's z rows (positions p0 - 1 .. p0 + 6) go out together
   const float* yslot = a.y + (size_t)b * F * kT * A2;
   const int nqs = F * kT * A2 / 4;
   NormPre npre;
-  if (!prm.norm_pre) npre = slot_norm_issue(yslot, nqs);
+  if (!norm_pre) npre = slot_norm_issue(yslot, nqs);
   ColInitRow zr[kColRO + 2];
+  if constexpr (LEAN) {
+    const ColInitLane ln = col_init_lane(a, b, u, g);
 #pragma unroll
-  for (int i = 0; i < kColRO + 2; ++i) zr[i] = col_init_load(a, b, u, f_own0 - 1 + i, t, g);
+    for (int i = 0; i < kColRO + 2; ++i) zr[i] = col_init_load_lean(ln, F, f_own0 - 1 + i, t);
+  } else {
+#pragma unroll
+    for (int i = 0; i < kColRO + 2; ++i) zr[i] = col_init_load(a, b, u, f_own0 - 1 + i, t, g);
+  }
   if constexpr (FIRST) stage->load_rest(prm);   // behind conv1's image (caller: load_w1), the norm and z rows
   // Var-IO weight of StateInit m (prm.m; masking: one StateInit of weight 1).  The launch of
   // StateInit m > 0 adds its weighted output to the state the earlier ones wrote (EpiConv3 mode 1,
   // first = m == 0), as the strip kernel's launches do; an item of weight 0 runs its math (0 *
   // finite: the same state bits as the strip kernel's skipped item)
-  const int m = prm.m;
+  // (lean: the one StateInit, m = 0; its weight is 1 under masking and without a mask)
+  const int m = LEAN ? 0 : prm.m;
   // (no mask: one-hot on MCS 0, as the strip kernels take it)
   const float wm = a.masking ? 1.f : (a.mcs_mask ? a.mcs_mask[((size_t)b * a.U + u) * a.M + m] : (m == 0 ? 1.f : 0.f));
   if constexpr (FIRST) {
     stage->store_w1(smem);   // the weights were loaded before the norm / z rows above; slot_norm's
-    if (prm.norm_pre) __syncthreads();   // barrier (or this one) publishes them before conv1
+    if (norm_pre) __syncthreads();   // barrier (or this one) publishes them before conv1
   }
-  const float ns = prm.norm_pre ? (float)a.norm[b]
+  const float ns = norm_pre ? (float)a.norm[b]
                                 : (float)slot_norm(npre, yslot, nqs, reinterpret_cast<double*>(smem + kColRed));
   col_ts(k, 5);
   half8 zin[kColRO + 2][1];
+  const float zsc = g == 2 ? 1.f : ns;   // (lean) the lane group's scale
 #pragma unroll
   for (int i = 0; i < kColRO + 2; ++i) {
     const int f = f_own0 - 1 + i;
-    zin[i][0] = col_init_z(zr[i], ns, f >= 0 && f < F && t < kT, g, a.use_h != 0);
+    if constexpr (LEAN) zin[i][0] = col_init_z_lean(zr[i], zsc, f >= 0 && f < F && t < kT, g);
+    else zin[i][0] = col_init_z(zr[i], ns, f >= 0 && f < F && t < kT, g, a.use_h != 0);
   }
   dpp_in_fence(zin);   // the conversions are VALU writes the depthwise's DPP reads
   // pe16 rows of this item's outputs for the update items' conv1 (every slot writes the same bytes)
@@ -583,7 +636,7 @@ __device__ __forceinline__ void col_init_item(const BlockParams<P16>& prm, char*
   col_ts(k, 4);
   using WS3 = WLds<P16, kHID, kDSP>;
   const WS3 w3{smem + kRrW3};
-  EpiConv3<P16, WS3, 16, TAILM> epi{&prm, nullptr, smem + kRrW3, w3, b, u, f_start, col_pos_hi(strips), 1, wm, m == 0,
+  EpiConv3<P16, WS3, 16, TAILM, LT> epi{&prm, nullptr, smem + kRrW3, w3, b, u, f_start, col_pos_hi(strips), 1, wm, m == 0,
                                     (float)a.active[(size_t)b * a.U + u], -1, 0, 0};
   epi.pos_lo = col_pos_lo(strips);
   col_conv3<NRX_COL_PR3>(own, nb, epi, lane, t, g, p0);
@@ -591,7 +644,7 @@ __device__ __forceinline__ void col_init_item(const BlockParams<P16>& prm, char*
 }
 
 // StateInit of a whole stage; k_init_col (one item per workgroup) / k_init_col_multi as above
-template <int TAILM, bool MULTI>
+template <int TAILM, bool MULTI, class LT = ColGeneric>
 __device__ __forceinline__ void col_init_stage(const BlockParams<P16>& prm, int items) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   rr_ts(0, 7);
@@ -601,8 +654,8 @@ __device__ __forceinline__ void col_init_stage(const BlockParams<P16>& prm, int 
     ColStage<32, TAILM> stage;
     stage.load_w1(prm);
     int b, u, strip;
-    work_item(blockIdx.x, prm.a.B, prm.a.U, prm.strips, prm.order_rev, b, u, strip);
-    col_init_item<TAILM, true>(prm, smem, wave, b, u, strip, 0, &stage);   // grid <= items
+    work_item(blockIdx.x, prm.a.B, prm.a.U, LT::kLean ? 1 : prm.strips, prm.order_rev, b, u, strip);
+    col_init_item<TAILM, true, LT>(prm, smem, wave, b, u, strip, 0, &stage);   // grid <= items
   }
   if constexpr (MULTI) {
     int k = 1;
@@ -615,9 +668,9 @@ __device__ __forceinline__ void col_init_stage(const BlockParams<P16>& prm, int 
   rr_ts_edge(1);
 }
 
-template <int TAILM>
+template <int TAILM, class LT = ColGeneric>
 __global__ __launch_bounds__(512) void k_init_col(BlockParams<P16> prm, int items) {
-  col_init_stage<TAILM, false>(prm, items);
+  col_init_stage<TAILM, false, LT>(prm, items);
 }
 template <int TAILM>
 __global__ __launch_bounds__(512) void k_init_col_multi(BlockParams<P16> prm, int items) {

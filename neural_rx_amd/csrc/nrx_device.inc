@@ -1015,7 +1015,8 @@ __device__ __forceinline__ int head_b2(int h) { return head_b1(h) + 512; }
 // finite values from zero inputs) so the MLP chains of the rows interleave; only the
 // stores are predicated.  The skip / Var-IO partial sum is prefetched before the conv3
 // math (prefetch()), so its global latency hides behind it.
-template <class P, class WS, int CHP, int TAILM>
+// LT (ColGeneric / ColLean, nrx_geom.h): the launch-uniform facts a lean column kernel holds as constants.
+template <class P, class WS, int CHP, int TAILM, class LT = ColGeneric>
 struct EpiConv3 {
   using S = typename P::S;
   using Real = typename P::Real;
@@ -1064,12 +1065,45 @@ struct EpiConv3 {
   __device__ void next_hook();
 
   __device__ bool row_ok(int p, int t) const {
+    if constexpr (LT::kLean) return p < prm->a.F && t < kT;   // one strip: position = subcarrier
     return p >= pos_lo && p < pos_hi && f_start + p < prm->a.F && t < kT;
   }
 
   template <int R>
   __device__ void prefetch(PrefT<R>& pf, int p0, int t, int g) const {
     const auto& a = prm->a;
+    if constexpr (LT::kLean) {
+      // One wave-uniform plane base and a 32-bit byte offset per row; every load goes out unpredicated from an
+      // address clamped inside the plane (row 0 / symbol 0 for rows that are not stored, channels 52..55 for the
+      // padding channels 56..63).  What a clamped load brings is finite state data that only reaches rows that are
+      // never stored and channels run() forces to zero, so no select follows.  StateInit (the one launch, the
+      // first): nothing to read.
+      static_assert(sizeof(S) == 2, "lean variants are f16");
+      if (mode != 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+          for (int n = 0; n < NTS; ++n) pf.prev[r][n] = half4{0, 0, 0, 0};
+        return;
+      }
+      const char* plane = reinterpret_cast<const char*>(a.s_in + srow(b, u, 0, 0, a.U, a.F));
+      // (the scheduling barriers keep the loads where the predicated ones stood: moved freely they lengthened live
+      // ranges into spills)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const bool ok = row_ok(p0 + r, t);
+        const unsigned ro = (unsigned)sre(ok ? p0 + r : 0, ok ? t : 0) * 2u + 8u * (unsigned)g;
+#pragma unroll
+        for (int n = 0; n < NTS; ++n) {
+          unsigned o = ro + 32u * n;
+          if (n == NTS - 1) o = ro + (g >= 2 ? 32u * n - 8u * (unsigned)(g - 1) : 32u * n);   // 16 n + 4 g <= 52
+          pf.prev[r][n] = *reinterpret_cast<const half4*>(plane + o);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      return;
+    }
     const bool need = mode == 0 || !first;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -1171,7 +1205,7 @@ struct EpiConv3 {
       w1 = WB + (ch ? kHW1C : 0);
       b1 = reinterpret_cast<const float*>(WB + kHB1 + (ch ? kHID * 4 : 0));
       b2 = reinterpret_cast<const float*>(WB + kHB2 + (ch ? 16 * 4 : 0));
-      w2 = WB + kHW2 + (ch ? prm->a.bits_max * 256 : 0);
+      w2 = WB + kHW2 + (ch ? (LT::kLean ? 4 : prm->a.bits_max) * 256 : 0);
     } else {
       w1 = X + head_w1(hh);
       b1 = reinterpret_cast<const float*>(X + head_b1(hh));
@@ -1203,6 +1237,23 @@ struct EpiConv3 {
     const auto& a = prm->a;
     const int F = a.F, U = a.U;
     const int lane = nrx_tid() & 63;
+    // Lean StateInit: the one StateInit's weight is 1 unless the caller hands a single-MCS mask that says otherwise;
+    // wm is wave-uniform, so the multiplies (x * 1 = x, bit for bit) sit behind one uniform branch per call.
+    typename P::Acc accw[R][NTS];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int n = 0; n < NTS; ++n) accw[r][n] = acc[r][n];
+    if constexpr (LT::kLean) {
+      if (mode == 1 && wm != (Real)1) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+          for (int n = 0; n < NTS; ++n)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) accw[r][n][j] *= wm;
+      }
+    }
     // ---- new state rows s (C layout, channels >= 56 forced to 0), rounded to S
     Real sv[R][NTS][4];
 #pragma unroll
@@ -1212,8 +1263,8 @@ struct EpiConv3 {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int co = 16 * n + P::co(g, j);
-          Real v = (Real)acc[r][n][j];
-          if (mode == 1) v *= wm;
+          Real v = (Real)accw[r][n][j];
+          if (!LT::kLean && mode == 1) v *= wm;
           v += (Real)pf.prev[r][n][j];
           if (co >= kDS) v = 0;
           sv[r][n][j] = (Real)(S)v;
@@ -1336,6 +1387,20 @@ struct EpiConv3 {
         } else {
           head_rows<1, RB>(sbr, DGlb<P, kDSP>{prm->llr[hh][0]}, DGlb<P, kHID>{prm->llr[hh][1]}, lane, g, o);
         }
+        if constexpr (LT::kLean) {
+          // one head of bits_max = 4 on one strip: a wave-uniform (b, u) plane base, an unsigned 32-bit row offset,
+          // one exec region per row (stored rows, lanes g = 0: the 4 LLRs of a symbol as one 16-byte store)
+          char* plane = reinterpret_cast<char*>(a.llr + ((size_t)b * U + u) * F * kT * LT::kBits);
+          const int nb = a.head_bits[0];
+#pragma unroll
+          for (int r = 0; r < RB; ++r) {
+            if (okr[r] && g == 0)
+              *reinterpret_cast<floatx4*>(plane + (unsigned)((p0r + r) * kT + t) * (unsigned)(LT::kBits * 4)) =
+                  floatx4{nb > 0 ? (float)o[r][0][0] : 0.f, nb > 1 ? (float)o[r][0][1] : 0.f,
+                          nb > 2 ? (float)o[r][0][2] : 0.f, nb > 3 ? (float)o[r][0][3] : 0.f};
+          }
+          return;
+        }
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
           if (!okr[r]) continue;
@@ -1369,6 +1434,19 @@ struct EpiConv3 {
         } else {
           head_rows<CHP / 16, RB>(sbr, DGlb<P, kDSP>{prm->chest[0]}, DGlb<P, kHID>{prm->chest[1]}, lane, g, o);
         }
+        if constexpr (LT::kLean) {
+          // 2A = 8 (one tile): lanes g < 2 hold channels 4 g .. 4 g + 3, one 16-byte store each
+          static_assert(CHP == 16 && LT::kA2 == 8, "lean ChEst store");
+          char* plane = reinterpret_cast<char*>(a.h_ref + ((size_t)b * U + u) * F * kT * LT::kA2);
+#pragma unroll
+          for (int r = 0; r < RB; ++r) {
+            if (okr[r] && g < 2)
+              *reinterpret_cast<floatx4*>(plane + (unsigned)((p0r + r) * kT + t) * (unsigned)(LT::kA2 * 4) +
+                                          16u * (unsigned)g) =
+                  floatx4{(float)o[r][0][0], (float)o[r][0][1], (float)o[r][0][2], (float)o[r][0][3]};
+          }
+          return;
+        }
         const int A2 = 2 * a.A;
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
@@ -1378,7 +1456,15 @@ struct EpiConv3 {
         }
       }
     };
-    if (NRX_RO_STRAIGHT && a.H == 1) {
+    if constexpr (LT::kLean) {
+      // one LLR head, then ChEst where the launch has an h_ref; the scheduling barriers stand where the generic
+      // body branches (one region over both heads spilled 25 VGPRs)
+      __builtin_amdgcn_sched_barrier(0);
+      one_head(0, false);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (LT::kHref) one_head(1, true);
+      __builtin_amdgcn_sched_barrier(0);
+    } else if (NRX_RO_STRAIGHT && a.H == 1) {
       one_head(0, false);
       if (a.h_ref) one_head(1, true);
     } else {
@@ -1928,8 +2014,8 @@ __device__ __forceinline__ void zload_dma_u2(const BlockParams<P>& prm, char* X,
   }
 }
 
-template <class P, class WS, int CHP, int TAILM>
-__device__ void EpiConv3<P, WS, CHP, TAILM>::next_hook() {
+template <class P, class WS, int CHP, int TAILM, class LT>
+__device__ void EpiConv3<P, WS, CHP, TAILM, LT>::next_hook() {
   if constexpr (kNextHook || kNextHookRO) {
     if (!next_ready()) return;   // fused forward: the next item's inputs were not complete
     zload_dma_u2<P, kDmaWaves>(nprm ? *nprm : *prm, X, nb, nu, nfs);

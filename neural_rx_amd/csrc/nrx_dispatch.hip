@@ -61,9 +61,9 @@ FwdPlan plan_forward(const FwdArgs<_Float16, float, _Float16>& a, int num_it, co
   auto small_fit = [&](int fo, int image) {
     return (long)a.B * a.U * ((a.F + fo - 1) / fo) <= cus && (a.H + 1) * (kHeadSlot + 1024) <= image;
   };
-  if (NRX_SMALL_STRIPS != 0 && small_fit(P16S::FO, strip_slots<P16S>() * slot_pitch<P16S>()))
+  if (NRX_SMALL_STRIPS != 0 && sc.small && small_fit(P16S::FO, strip_slots<P16S>() * slot_pitch<P16S>()))
     return plan_strips<P16S>(pl, PATH_P16S, a, cus);
-  if (NRX_SMALL_STRIPS != 0 && small_fit(P16M::FO, strip_slots<P16M>() * slot_pitch<P16M>()))
+  if (NRX_SMALL_STRIPS != 0 && sc.small && small_fit(P16M::FO, strip_slots<P16M>() * slot_pitch<P16M>()))
     return plan_strips<P16M>(pl, PATH_P16M, a, cus);
   constexpr int image = strip_slots<P16>() * slot_pitch<P16>();
   // conv1 can read [a | s | pe] from memory (GZ): the workspace within its 32-bit offsets
@@ -140,6 +140,13 @@ FwdPlan plan_forward(const FwdArgs<_Float16, float, _Float16>& a, int num_it, co
     sp.grid = sp.items < cus ? sp.items : cus;
     sp.one = col && sp.items <= sp.grid;
     sp.lds = col ? kColLds : kRrLds;
+    // The lean variants of the one-item column kernels: every launch-uniform fact they hold as a constant (ColLean,
+    // nrx_geom.h).  One strip; the slot norm fused; a model with h_hat; one StateInit (masking, or one MCS: its weight
+    // is 1 unless a single-MCS mask says otherwise, which the kernel checks once per item); one LLR head of bits_max = 4; 2A = 8 (CHP = 16).  The readout without h_ref
+    // is a variant of its own; the other stages ignore h_ref.
+    const bool lean = NRX_COL_LEAN != 0 && sp.one && cstrips == 1 && !pl.norm_pre && a.use_h && a.num_init == 1 &&
+                      (a.masking || a.M == 1) && a.H == 1 && a.bits_max == 4 && a2 == 8;
+    if (col && lean) sp.variant = last && !a.h_ref ? COL_LEAN_NO_HREF : COL_LEAN;
   }
   return pl;
 }

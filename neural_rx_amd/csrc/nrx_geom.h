@@ -100,5 +100,22 @@ constexpr int kColLds = kColRed + 64;
 static_assert(kColLds <= 160 * 1024, "column LDS plan exceeds the CU's LDS");
 __host__ __device__ constexpr int col_strips(int F) { return F <= kColPos ? 1 : (F + kColFO - 1) / kColFO; }
 constexpr int kColMaxStages = 1 + kMaxIt;
+// Variants of the one-item column kernels (StagePlan::variant, set by plan_forward alone).  A lean variant takes as
+// compile-time constants what is uniform over the launch and fixed by the bench family: one strip (no halo: every
+// position 0 .. 47 is an output row of subcarrier f = position), the slot norm fused into StateInit, a model that
+// takes h_hat, one StateInit (masking or one MCS), one LLR head of bits_max = 4, 2A = 8; the readout with or without the
+// ChEst store (h_ref).  COL_GENERIC reads all of them from BlockParams at run time.
+enum ColVariant { COL_GENERIC = 0, COL_LEAN = 1, COL_LEAN_NO_HREF = 2 };
+struct ColGeneric {
+  static constexpr bool kLean = false, kHref = true;
+};
+template <bool HREF>
+struct ColLean {
+  static constexpr bool kLean = true, kHref = HREF;
+  static constexpr int kBits = 4, kA2 = 8;
+};
+#ifndef NRX_COL_LEAN
+#define NRX_COL_LEAN 1   // 0: the plan never picks a lean variant (A/B switch)
+#endif
 
 }  // namespace nrx

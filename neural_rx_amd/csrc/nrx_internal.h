@@ -149,6 +149,8 @@ struct FusedCtl {
 struct Sched {
   int mask;    // stage mask of the f16 forward (nrx_update_schedule; NRX_UPDATE_RR at nrx_create), bits below
   int fused;   // one-launch forwards (nrx_fused_config; NRX_FUSED): 0 off, 1 where measured faster, 2 where applicable
+  int small = 1;   // the 8 / 16-row strip tiers for grids that leave CUs idle (tests switch them off to run the
+                   // 24-row tier's kernels on a few slots: nrx_debug_small_tiers)
 };
 // schedule-mask bits of the three-launch f16 forward (nrx_update_schedule)
 constexpr int kSchedRrAgg = 1, kSchedRrRo = 2, kSchedColAgg = 4, kSchedColRo = 8, kSchedColInit = 16;
@@ -189,6 +191,7 @@ struct StagePlan {       // stage s: StateInit m = s < num_init, else update i =
   int items, strips;     // work items of the stage = B * U * strips
   int grid, lds;         // workgroups and dynamic LDS bytes of its launch (one-launch paths: FwdPlan's)
   int order_rev;         // BlockParams::order_rev: alternates with the launches
+  int variant;           // ColVariant of a one-item column launch (nrx_geom.h): generic, or lean (with / without h_ref)
 };
 struct FwdPlan {
   int path;              // FwdPath

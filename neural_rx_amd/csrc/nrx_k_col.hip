@@ -27,7 +27,11 @@ hipError_t launch_init_col(const BlockParams<P16>& bp, const StagePlan& sp, hipS
   col_stamp_select(st);
   // the last StateInit launch runs iteration 0's aggregation MLP (TAIL_AGG), earlier ones (Var-IO) none
   const bool agg = sp.tail == TAIL_AGG;
-  if (sp.one) {
+  // the plan's variant (lean: one item per workgroup, TAIL_AGG; plan_forward)
+  if (sp.variant != COL_GENERIC) {
+    if (!sp.one || !agg) return hipErrorInvalidValue;
+    k_init_col<TAIL_AGG, ColLean<true>><<<grid, 512, sp.lds, st>>>(bp, items);
+  } else if (sp.one) {
     if (agg) k_init_col<TAIL_AGG><<<grid, 512, sp.lds, st>>>(bp, items);
     else k_init_col<TAIL_NONE><<<grid, 512, sp.lds, st>>>(bp, items);
   } else {
@@ -41,7 +45,12 @@ hipError_t launch_update_col(const BlockParams<P16>& bp, const StagePlan& sp, hi
   const int items = sp.items, grid = sp.grid, L = sp.lds;
   const bool ch32 = sp.chp == 32, one = sp.one;   // one item per workgroup, or the looping kernel
   col_stamp_select(st);
-  if (sp.tail == TAIL_READOUT_WB) {
+  if (sp.variant != COL_GENERIC) {   // lean: one item per workgroup, CHP = 16 (plan_forward)
+    if (!one || ch32) return hipErrorInvalidValue;
+    if (sp.tail != TAIL_READOUT_WB) k_update_col<16, TAIL_AGG, ColLean<true>><<<grid, 512, L, st>>>(bp, items);
+    else if (sp.variant == COL_LEAN) k_update_col<16, TAIL_READOUT_WB, ColLean<true>><<<grid, 512, L, st>>>(bp, items);
+    else k_update_col<16, TAIL_READOUT_WB, ColLean<false>><<<grid, 512, L, st>>>(bp, items);
+  } else if (sp.tail == TAIL_READOUT_WB) {
     if (ch32) {
       if (one) k_update_col<32, TAIL_READOUT_WB><<<grid, 512, L, st>>>(bp, items);
       else k_update_col_multi<32, TAIL_READOUT_WB><<<grid, 512, L, st>>>(bp, items);
@@ -106,6 +115,10 @@ hipError_t setup_col() {
   set((const void*)k_update_col_multi<16, TAIL_READOUT_WB>);
   set((const void*)k_update_col_multi<32, TAIL_READOUT_WB>);
   set((const void*)k_fwd_col<16>);
+  set((const void*)k_init_col<TAIL_AGG, ColLean<true>>);
+  set((const void*)k_update_col<16, TAIL_AGG, ColLean<true>>);
+  set((const void*)k_update_col<16, TAIL_READOUT_WB, ColLean<true>>);
+  set((const void*)k_update_col<16, TAIL_READOUT_WB, ColLean<false>>);
   return e;
 }
 
